@@ -2,6 +2,15 @@
 """Benchmark of the MI355X cBIC-score hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4] [--mode shard|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+result line.  --dump-outputs DIR also writes the lists the last timed step
+produced (offsets, sets, scores) as DIR/<name>.npy.  --full adds every other
+leg described below (checks against the oracle fixtures, roofline and
+per-kernel figures, single-call time, exchange split, order-graph search,
+CPU baselines, C4) to the same line; --no-cpu-baseline, --no-search and
+--no-c4 take legs out of a --full run.
 
 One step = one full cBIC scoring pass over one dataset (every parent set of
 size <= k of every variable through the layer-synchronous HIP scorer,
@@ -474,6 +483,28 @@ def lists_vs_fixture(cfg, variables, offs, sets):
     return checked, bad
 
 
+DUMP_LIMIT = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def dump_outputs(path, offsets, sets, scores, seed=9200):
+    """--dump-outputs: the lists of the last timed step as a caller receives
+    them (ulg_cbic_fetch, or the exchange's gathered lists): offsets.npy
+    (float64, one entry per variable + 1), sets.npy (the parent-set masks as
+    float64, exact for n <= 53) and scores.npy (float32), in the library's
+    order.  Lists above DUMP_LIMIT are cut to the same seeded sample of
+    positions in sets and scores (ascending)."""
+    offsets = np.asarray(offsets).astype(np.float64)
+    sets = np.asarray(sets).astype(np.uint64).astype(np.float64)
+    scores = np.asarray(scores, dtype=np.float32)
+    room = (DUMP_LIMIT - offsets.nbytes - 1024) // (sets.itemsize + scores.itemsize)
+    if len(sets) > room:
+        keep = np.sort(np.random.default_rng(seed).choice(len(sets), size=room, replace=False))
+        sets, scores = sets[keep], scores[keep]
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("offsets", offsets), ("sets", sets), ("scores", scores)):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="GPUs (ranks); default 1, or WORLD_SIZE under a launcher")
@@ -481,6 +512,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--mode", default="shard", choices=["shard", "weak"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's lists as DIR/offsets.npy, sets.npy, scores.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-search", action="store_true")
     ap.add_argument("--no-c4", action="store_true", help="skip the extra C4 object (N=1 only)")
@@ -496,6 +531,8 @@ def main():
                          "--option score_streams=... says otherwise (default 3 when every layer is unrolled, "
                          "k <= 8; 1 for the wide layers of C1/C4, whose calls synchronise anyway)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.slots is None:
         args.slots = 3 if CONFIGS[args.config]["k"] <= 8 else 1
     if args.slots > 1 and not any(o.startswith("score_streams=") for o in args.option):
@@ -639,6 +676,53 @@ def main():
     else:
         scored_all = float(scored_total)
 
+    res = {
+        "metric": METRIC,
+        "value": scored_all / elapsed,
+        "unit": "parent-set scores/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak" if args.mode == "weak" else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": f"synthetic: seeded linear-Gaussian SEM (synth.gaussian_sem, seed "
+                f"{'9200+rank' if args.mode == 'weak' else '9200, one dataset'}), {skel_note}",
+        "config": {"workload": f"{args.config.upper()} cBIC scoring: n={n}, N={N}, max-parents k={k}, "
+                               f"lambda={lam}, {skel_note}, "
+                               + (f"all {n} variables per GPU" if args.mode == "weak" else
+                                  f"{n} variables balanced over {ws} GPU(s), one all-gather of the lists"),
+                   "config_id": args.config, "mode": args.mode,
+                   "parallelism": f"variable shard x{ws}" if args.mode == "shard" else f"replicas x{ws}",
+                   "steps_in_flight": slots,
+                   "parent_sets_per_step_per_rank": units_rank},
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        for c2 in sctx[1:]:
+            c2.close()
+        ctx.close()
+        if dist:
+            dist.destroy_process_group()
+
+    if args.dump_outputs is not None and rank == 0:
+        # timed step i ran on slot i % slots: the last one's lists, as its
+        # caller holds them (this rank's own, or the job's after the exchange)
+        last = (args.steps - 1) % slots
+        if sex[last] is not None:
+            o_, st_, sc_ = sex[last].assemble()
+            dump_outputs(args.dump_outputs, o_, st_.cpu().numpy(), sc_.cpu().numpy())
+        else:
+            st_, _ = sctx[last].score_finish()
+            dump_outputs(args.dump_outputs, *sctx[last].fetch(st_))
+    if not args.full:
+        finish()
+        return
+
     # sets in one launch of the dominant kernel (layer k, sets without variable 0)
     per_launch = sum(math.comb(msz[v] - (1 if (v != 0 and cands_all[v] & 1) else 0), kk) for v in variables)
     if ex is not None and slots > 1:
@@ -757,31 +841,8 @@ def main():
         search = search_metrics(ctx, cfg, variables, cands, rank, ws, edges=rows, skel_note=skel_note)
 
     if rank == 0:
-        res = {
-            "metric": METRIC,
-            "value": scored_all / elapsed,
-            "unit": "parent-set scores/s",
-            "n_gpus": ws,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak" if args.mode == "weak" else "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": f"synthetic: seeded linear-Gaussian SEM (synth.gaussian_sem, seed "
-                    f"{'9200+rank' if args.mode == 'weak' else '9200, one dataset'}), {skel_note}",
-            "config": {"workload": f"{args.config.upper()} cBIC scoring: n={n}, N={N}, max-parents k={k}, "
-                                   f"lambda={lam}, {skel_note}, "
-                                   + (f"all {n} variables per GPU" if args.mode == "weak" else
-                                      f"{n} variables balanced over {ws} GPU(s), one all-gather of the lists"),
-                       "config_id": args.config, "mode": args.mode,
-                       "parallelism": f"variable shard x{ws}" if args.mode == "shard" else f"replicas x{ws}",
-                       "steps_in_flight": slots,
-                       "parent_sets_per_step_per_rank": units_rank},
-            "roofline": roof,
-            "kernel_ms_one_step": {kk2: round(vv["total_ms"], 4) for kk2, vv in kernels.items()},
-        }
+        res["roofline"] = roof
+        res["kernel_ms_one_step"] = {kk2: round(vv["total_ms"], 4) for kk2, vv in kernels.items()}
         res["single_call_ms"] = single_call_ms
         res["single_call_note"] = ("one synchronised ulg_cbic_score call at a time with the library's default "
                                    "options (what bin/score makes), median of 10 on a fresh context")
@@ -795,12 +856,7 @@ def main():
             res["cpu_baseline"] = cpu_baseline(cfg, X)
         if ws == 1 and args.config != "c4" and not args.no_c4:
             res["c4"] = c4_leg(local)
-        print(json.dumps(res), flush=True)
-    for c2 in sctx[1:]:
-        c2.close()
-    ctx.close()
-    if dist:
-        dist.destroy_process_group()
+    finish()
 
 
 def sharded_search(ctx, cfg, ex, variables, cands, rows, skel_note, rank, ws, dist, cdev, torch):

@@ -36,8 +36,8 @@ mkdir -p "$OUT"
 LIBS=${LIBS:-urlearning-cpp_amd/libulg.so}
 CASES=${CASES:-c3 c5}
 OPTS=${OPTS:-}
-FULL="python3 bench.py ${BENCH_ARGS:-}"
-SHORT="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-search --no-c4 ${BENCH_ARGS:-}"
+FULL="python3 bench.py --full ${BENCH_ARGS:-}"
+SHORT="python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-search --no-c4 ${BENCH_ARGS:-}"
 summ() {  # one line per score_probe.py case: case digest ms_median
   grep -h '"case"' "$1" | sed -E 's/.*"case": "([a-z0-9]+)".*"digest": "([0-9a-f]+)".*"ms_median": ([0-9.]+).*/\1 \2 \3/' | tr '\n' ' '
 }
@@ -75,7 +75,7 @@ for step in ${STEPS:-suite smoke bench}; do
       for ctrs in FETCH_SIZE WRITE_SIZE; do
         i=$((i+1))
         timeout -s KILL 300 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d "$OUT/s$i" -o run -- \
-          python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-c4 > "$OUT/s$i.log" 2>&1
+          python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-c4 > "$OUT/s$i.log" 2>&1
         echo "search pmc pass $i ok"
       done
       F=$(find "$OUT/s1" -name "*counter_collection.csv" | head -1)

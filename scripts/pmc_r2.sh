@@ -23,7 +23,7 @@ PROBE=./scripts/bin/gather_probe
 run g_fetch 90 FETCH_SIZE -- ${PROBE}
 run g_req 90 TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum -- ${PROBE}
 run g_dram 90 TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_DRAM_32B_sum -- ${PROBE}
-BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH="python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline"
 run b_fetch 240 FETCH_SIZE -- ${BENCH}
 run b_write 240 WRITE_SIZE -- ${BENCH}
 run b_req 240 TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum -- ${BENCH}

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${TAG:-pmc}
 mkdir -p gpurun_out/${TAG}
-CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-search ${BENCH_ARGS:-}"
+CMD="python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-search ${BENCH_ARGS:-}"
 timeout -k 10 120 rocprofv3 -L > gpurun_out/${TAG}/counters.txt 2>&1 || true
 i=0
 for ctrs in "${@}"; do

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${TAG:-pmcs}
 mkdir -p gpurun_out/${TAG}
-CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline"
 i=0
 for ctrs in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))

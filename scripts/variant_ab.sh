@@ -13,7 +13,7 @@ if [ "${TESTS:-1}" = "1" ]; then
 fi
 for v in ${VARIANTS:-49 113}; do
   timeout -k 10 200 python -u scripts/score_probe.py --cases c3 c5 small --reps 10 --options score_variant=$v > ${OUT}/probe_$v.log 2>&1
-  timeout -k 10 150 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-search --no-c4 --option score_variant=$v > ${OUT}/bench_$v.json 2> ${OUT}/bench_$v.err
+  timeout -k 10 150 python -u bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-search --no-c4 --option score_variant=$v > ${OUT}/bench_$v.json 2> ${OUT}/bench_$v.err
   if [ -f ab/libulg_LAYER_STATS.so ]; then
     timeout -k 10 150 python -u scripts/score_probe.py --cases c5 --reps 1 --options score_variant=$v,score_streams=1 --lib ab/libulg_LAYER_STATS.so > ${OUT}/stats_$v.log 2>&1
   fi

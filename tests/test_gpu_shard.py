@@ -113,7 +113,7 @@ def _bench(args):
 def test_bench_two_ranks_on_one_gpu_matches_one_rank():
     """bench.py --gpus 2 starts its own two ranks (gloo, both on GPU 0),
     reports n_gpus 2, and its gathered lists and goal cost equal N=1's."""
-    common = ["--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--config", "c2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     one = _bench(["--gpus", "1"] + common)
     two = _bench(["--gpus", "2", "--dist-backend", "gloo", "--device", "0"] + common)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2

@@ -16,6 +16,12 @@
  *                        BIC_OLS.cpp:174-389) for a batch of variables; the
  *                        stored-set rule and the find_best_subset_score
  *                        dominance recursion are reproduced exactly.
+ *   ulg_cbic_set_constraints  replaces the scoring::Constraints* argument
+ *                        of the scoring function's constructor
+ *                        (scoring_function/constraints.h:36-139, wired in at
+ *                        score/score_main.cpp:314-317,351): a violating parent
+ *                        set takes the raw score variableCount before any
+ *                        regression (BIC_OLS.cpp:279-283).
  *   ulg_cbic_fetch       hands the stored FloatMap contents back (what
  *                        scoringThread prints, score/score_main.cpp:173-203).
  *   ulg_bestscore_*      replaces bestscorecalculators::BestScoreCalculator
@@ -62,6 +68,8 @@ typedef struct ulg_ctx ulg_ctx;
  * find_best_subset_score walk keeps a 2^(k+1)-bit checked set per set. */
 #define ULG_MAX_PARENTS_GPU 31
 #define ULG_UNROLLED_PARENTS_GPU 8
+/* Most alternatives ulg_cbic_set_constraints takes for one variable. */
+#define ULG_MAX_CONSTRAINT_ALTERNATIVES 64
 
 /* ---- context --------------------------------------------------------- */
 /* One device per context: ndev must be 1 (multi-GPU = one process per GPU). */
@@ -132,6 +140,22 @@ int ulg_cbic_score_vars(ulg_ctx *ctx, const int *vars, int nv,
                         const uint64_t *candidates, int max_parents,
                         uint64_t *sets, float *scores, int64_t *offsets,
                         int64_t cap);
+
+/* scoring::Constraints (scoring_function/constraints.h:36-139) for the loaded data:
+ * alternative i says variable vars[i] may take a parent set P with required[i] ⊆ P and
+ * P ∩ forbidden[i] = ∅; a variable with at least one alternative must satisfy one of them.
+ * count = 0 clears.  Valid after ulg_cbic_load, cleared by the next ulg_cbic_load;
+ * applies to ulg_cbic_score*, ulg_cbic_score_sets and everything that reads their lists.
+ * A violating set scores variableCount (BIC_OLS.cpp:279-283), so it is stored
+ * at -float(n) -- the empty set too, when every alternative of its variable
+ * requires a parent -- and the dominance walks of larger sets see it as a
+ * present key.  The reference's uninitialised Constraints::empty
+ * (constraints.h:59) is taken as 0.  Masks with a bit >= n, a variable out
+ * of range or a call before ulg_cbic_load return ULG_ERR_ARG; more than
+ * ULG_MAX_CONSTRAINT_ALTERNATIVES alternatives for one variable return
+ * ULG_ERR_UNSUPPORTED.  ulg_get_info("constraints") is the number held. */
+int ulg_cbic_set_constraints(ulg_ctx *ctx, int count, const int *vars,
+                             const uint64_t *required, const uint64_t *forbidden);
 
 /* Per-call counterpart of ScoringFunction::calculateScore(variable, parents,
  * cache) (scoring_function.h:16-23, BIC_OLS.cpp:174-276): for each pair

@@ -169,6 +169,39 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb, int on) {
     return x * q + (x < r ? x : r) + k;
 }
 
+// Parent-set constraints (scoring::Constraints, constraints.h:123-139) as the
+// kernels read them: words [0, nv] are the prefix of the variables'
+// alternatives, then one (required, forbidden) pair of masks per alternative.
+// A scoring call's table is indexed by the call's variable index and holds
+// compact candidate masks (the lanes' cm); ulg_cbic_score_sets' table is
+// indexed by variable and holds variable masks.  A set satisfies a variable
+// without alternatives, or one alternative with required within the set and
+// forbidden disjoint from it; a variable whose alternatives all require a
+// non-candidate carries one alternative requiring bit 63, which no set holds.
+// Only the constrained kernels read it (*_cons_kernel: the texts of
+// cbic_score_{layer,small,wide,sets}.inc included a second time with
+// ULG_CONS 1, so the unconstrained kernels stay the code they were); tables
+// of at most kConsLdsWords words are copied into LDS behind the block's
+// layout.
+constexpr int kConsLdsWords = 256;
+__host__ __device__ inline bool cons_violates(const uint64_t *ct, int nv, int vi, uint64_t set) {
+    const uint64_t b = ct[vi], e = ct[vi + 1];
+    if (b == e) return false;
+    const uint64_t *p = ct + nv + 1 + 2 * b;
+    for (uint64_t i = 0; i < e - b; ++i)
+        if ((p[2 * i] & ~set) == 0 && (p[2 * i + 1] & set) == 0) return false;
+    return true;
+}
+// the block's copy of the call's table (CONS kernels; before the first barrier)
+template <int THREADS>
+__device__ __forceinline__ const uint64_t *cons_stage(unsigned char *smem, int lds_end, const uint64_t *cons,
+                                                      int cons_words) {
+    if (cons_words > kConsLdsWords) return cons;
+    uint64_t *sc = reinterpret_cast<uint64_t *>(smem + ((lds_end + 15) & ~15));
+    for (int i = threadIdx.x; i < cons_words; i += THREADS) sc[i] = cons[i];
+    return sc;
+}
+
 
 // LDS carve: gram | binom | work | tbl_off | meta | candidate lists |
 // recursion stack (variant bit 1)
@@ -611,255 +644,12 @@ constexpr int score_min_waves() {
 // PHASE 0: sets containing variable 0; 1: the rest.  V = variant bits (see
 // ulg_set_option "score_variant"), compile-time so each form gets its own
 // register allocation.
-template <int L, int PHASE, int V>
-__global__ void __launch_bounds__(kBlock, (score_min_waves<L, PHASE, V>())) score_layer_kernel(ScoreArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsLayout lay = lds_layout(a.n, a.nv, a.S, L, V);
-    double *g = reinterpret_cast<double *>(smem + lay.gram);
-    uint32_t *binom = reinterpret_cast<uint32_t *>(smem + lay.binom);
-    uint64_t *work = reinterpret_cast<uint64_t *>(smem + lay.work);
-    uint64_t *toff = reinterpret_cast<uint64_t *>(smem + lay.toff);
-    // the per-variable metadata and candidate lists too: every lane reads
-    // them right after its variable is known, and from global memory those
-    // would be two more dependent round trips per lane
-    int *smeta = reinterpret_cast<int *>(smem + lay.meta);
-    uint8_t *scand = reinterpret_cast<uint8_t *>(smem + lay.cand);
-    for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
-    for (int i = threadIdx.x; i < 64 * kBinomK; i += kBlock) binom[i] = a.binom[i];
-    for (int i = threadIdx.x; i <= a.nv; i += kBlock) work[i] = a.work[i];
-    for (int i = threadIdx.x; i <= a.nv * a.S; i += kBlock) toff[i] = a.tbl_off[i];
-    for (int i = threadIdx.x; i < a.nv * 4; i += kBlock) smeta[i] = a.meta[i];
-    for (int i = threadIdx.x; i < a.nv * 16; i += kBlock)
-        reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
-    __syncthreads();
-
-    constexpr bool HM = (V & 64) != 0;           // subset maxima kept up to date
-    constexpr bool CMP = HM && (V & 16) != 0;     // ... and the sets settled by them first
-    const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
-    const bool valid = gid0 < work[a.nv];
-    if (!CMP && !valid) return;
-    // CMP: every lane reaches the block's barrier; a lane past the launch's
-    // sets scores the last one again and writes nothing
-    const uint64_t gid = valid ? gid0 : work[a.nv] - 1;
-    int lo = 0, hi = a.nv;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (work[mid] <= gid) lo = mid; else hi = mid;
-    }
-    const int vi = lo;
-    const uint64_t r = gid - work[vi];
-    const SetHead<L> hd = set_head<L, PHASE>(smeta, scand, binom, vi, r);
-    const bool z = hd.z;
-    const uint64_t cm = hd.cm, rankP = hd.rankP;
-
-#ifndef ULG_PROBE_NOSCORE  // ULG_PROBE_*: timing-only builds, see the two-pass section below
-    const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
-#else
-    const float ts = (float)(-a.N * g[hd.gv[0] * a.n + hd.gv[L - 1]] - (double)(r & 1023));
-#endif
-
-    if constexpr (CMP) {
-        // 1. settle by the subset maxima: ts >= 0, no key >= -ts in U(P), or a
-        //    present direct child >= -ts (always visited at the top level)
-        const uint64_t vbase = (uint64_t)vi * a.S;
-        const uint64_t slot = toff[vbase + L] + rankP;
-        uint64_t rc[L], rz[L];
-        child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
-        // every load of the settle issued at once (the children's maxima and
-        // values, the var-0 toggles' maxima): one memory round trip instead
-        // of up to three dependent ones
-        float hch = absent_f();  // max over the proper nonempty subsets of P
-        float hz = absent_f();   // ... and over the toggles P\a + {0}
-        bool dh = false;         // a direct child >= -ts
-#ifdef ULG_GATHER_STATS
-        uint32_t hotA = 0u;      // children P\a_i holding a key >= -ts (hsub)
-        uint32_t hotZ = 0u;      // toggled children P\a_i + {0} holding one
-#endif
-        {
-            float ch[L], cv[L], zv[L];
-            const uint32_t o1 = (uint32_t)toff[vbase + L - 1], o0 = (uint32_t)toff[vbase + L];
-#pragma unroll
-            for (int i = 0; i < L; ++i) {
-                if constexpr (L > 1) {
-                    ch[i] = a.hsub[o1 + (uint32_t)rc[i]];
-                    cv[i] = a.table[o1 + (uint32_t)rc[i]];
-                }
-                if constexpr (PHASE == 1) zv[i] = a.hsub[(z ? o0 : 0u) + (z ? (uint32_t)rz[i] : 0u)];
-            }
-            const float thr = -ts;
-#pragma unroll
-            for (int i = 0; i < L; ++i) {
-                if constexpr (L > 1) {
-                    hch = fmaxf(hch, ch[i]);
-                    dh |= cv[i] >= thr;
-#ifdef ULG_GATHER_STATS
-                    hotA |= (ch[i] >= thr) ? 1u << i : 0u;
-#endif
-                }
-                if constexpr (PHASE == 1) {
-                    hz = fmaxf(hz, zv[i]);
-#ifdef ULG_GATHER_STATS
-                    hotZ |= (zv[i] >= thr) ? 1u << i : 0u;
-#endif
-                }
-            }
-            if (!z) hz = absent_f();
-#ifdef ULG_GATHER_STATS
-            if (!z) hotZ = 0u;
-#endif
-        }
-        bool need = false;
-        float out;
-        if (ts >= 0.0f) {
-            const float s = -ts;
-            out = (s < 0.0f) ? s : absent_f();
-        } else {
-            const float thr = -ts;
-            const float hu = fmaxf(hch, hz);
-            out = -ts;
-            if (hu >= thr) {
-                out = absent_f();
-                need = !dh;
-            }
-        }
-        if (valid && !need) {
-            a.table[slot] = out;
-            if (a.hsub_out) a.hsub[slot] = fmaxf(out, hch);
-        }
-// ULG_PROBE_*: timing-only builds (wrong lists, never shipped) that drop one
-// part of the two-pass kernel (scripts/r5_kernel_ab.sh)
-#ifdef ULG_PROBE_NOCMP  // the undecided sets are left undecided
-        return;
-#endif
-        // 2. the rest of the block's sets, compacted in LDS, so the presence
-        //    gathers (2^(L+1) reads each) run on dense waves
-        unsigned int *cnt = reinterpret_cast<unsigned int *>(smem + lay.cmp);
-        uint64_t *ecm = reinterpret_cast<uint64_t *>(smem + lay.cmp + 16);
-        uint32_t *eslot = reinterpret_cast<uint32_t *>(ecm + kBlock);
-        float *ets = reinterpret_cast<float *>(eslot + kBlock);
-        float *ehch = ets + kBlock;
-        int *evi = reinterpret_cast<int *>(ehch + kBlock);
-        if (threadIdx.x == 0) {
-            cnt[0] = 0u;
-            cnt[1] = 0u;  // the second compaction's count (variant bit 7)
-        }
-        __syncthreads();
-        if (valid && need) {
-            const unsigned int k = atomicAdd(cnt, 1u);
-            ecm[k] = cm;
-            eslot[k] = (uint32_t)slot;
-            ets[k] = ts;
-            ehch[k] = hch;
-#ifdef ULG_GATHER_STATS
-            evi[k] = vi | (int)(hotA << 8) | (int)(hotZ << 16);
-#else
-            evi[k] = vi;
-#endif
-        }
-        __syncthreads();
-        constexpr int W = bits_words(L);
-        using BS = std::conditional_t<(W >= 4), BitsLds<W>, Bits<W>>;
-        constexpr bool CMP2 = (V & 128) != 0 && W < 4;
-        if constexpr (!CMP2)
-            if (threadIdx.x >= *cnt) return;
-        const int k = threadIdx.x;
-        const bool a1 = threadIdx.x < cnt[0];
-        const uint64_t seg = walk_segment();
-        // this lane's compacted set (the lanes past the count, variant bit 7
-        // only, carry a dummy and gather nothing)
-        const int vk = a1 ? evi[k] & 0xff : 0;
-#ifdef ULG_GATHER_STATS
-        const uint32_t hk = a1 ? (uint32_t)evi[k] >> 8 : 0u;  // hotA | hotZ << 8
-#endif
-        const bool zk = smeta[vk * 4 + 2] != 0;
-        const float tk = a1 ? ets[k] : -1.0f;
-        const uint64_t sk = a1 ? eslot[k] : 0u;
-        const uint64_t cmk = a1 ? ecm[k] : 1ull;
-        const float hk1 = a1 ? ehch[k] : absent_f();
-        uint64_t *lds_bits = reinterpret_cast<uint64_t *>(smem + lay.bits) + threadIdx.x;
-        const LocalSet<L> ls = local_set<L, PHASE>(cmk, zk);
-        BS present = make_bits<BS>(lds_bits);
-        BS hib = make_bits<BS>(lds_bits + (size_t)W * kBlock);
-        present.clear();
-        hib.clear();
-        bool q = false;
-        if (a1) {
-            // the keys the two-level rules read first; the rest only for the
-            // sets the rules leave to the walk (the subset maxima already
-            // showed a key >= -ts is present, so the rules need no "any key"
-            // test)
-#ifndef ULG_PROBE_NOPART1
-            gather_keys<L, PHASE, V, BS, LdPlain, 1>(present, hib, ls, -tk, binom, zk, a.table,
-                                                    toff + (uint64_t)vk * a.S);
-#endif
-#ifndef ULG_PROBE_NORULES
-            const bool dom = settle_rules<L, PHASE, BS, true>(present, hib, ls, q);
-#else
-            const bool dom = false;
-            q = false;
-#endif
-#ifdef ULG_GATHER_STATS
-            if constexpr (W < 4) {
-                BS p2 = make_bits<BS>(lds_bits), h2 = make_bits<BS>(lds_bits);
-                p2.clear();
-                h2.clear();
-                gather_keys<L, PHASE, V, BS, LdPlain, 0>(p2, h2, ls, -tk, binom, zk, a.table,
-                                                        toff + (uint64_t)vk * a.S);
-                gather_stats<L, PHASE>(p2, h2, hk & 0xffu, hk >> 8, zk, q);
-            }
-#endif
-            if (!q) {
-                const float o = dom ? absent_f() : -tk;
-                a.table[sk] = o;
-                if (a.hsub_out) a.hsub[sk] = fmaxf(o, hk1);
-            }
-        }
-        if constexpr (CMP2) {
-            // 3. the sets the rules leave to the walk (about a third of the
-            //    compacted ones) compacted once more, with their gathered
-            //    words, so the rest of the gathers, the walk closure and the
-            //    queue run on dense waves: at ~30 % of the lanes every wave
-            //    would still issue them
-            uint64_t *c2w = reinterpret_cast<uint64_t *>(smem + lay.cmp2);  // [2W][kBlock]
-            __syncthreads();  // every lane has read its first entry
-            if (q) {
-                const unsigned int k2 = atomicAdd(cnt + 1, 1u);
-                ecm[k2] = cmk;
-                eslot[k2] = (uint32_t)sk;
-                ets[k2] = tk;
-                ehch[k2] = hk1;
-                evi[k2] = vk;
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    c2w[j * kBlock + k2] = present.word(j);
-                    c2w[(W + j) * kBlock + k2] = hib.word(j);
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x >= cnt[1]) return;
-            const int vq = evi[k];
-            const bool zq = smeta[vq * 4 + 2] != 0;
-            const float tq = ets[k];
-            const uint64_t sq = eslot[k];
-            const float hq = ehch[k];
-            const LocalSet<L> lq = local_set<L, PHASE>(ecm[k], zq);
-            BS pq = make_bits<BS>(lds_bits), hq_bits = make_bits<BS>(lds_bits);
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                pq.w[j] = c2w[j * kBlock + k];
-                hq_bits.w[j] = c2w[(W + j) * kBlock + k];
-            }
-            walk_or_store<L, PHASE, V, BS>(a, pq, hq_bits, lq, tq, binom, zq, toff + (uint64_t)vq * a.S, seg, sq, hq);
-        } else {
-            if (q)
-                walk_or_store<L, PHASE, V, BS>(a, present, hib, ls, tk, binom, zk, toff + (uint64_t)vk * a.S, seg, sk,
-                                               hk1);
-        }
-        return;
-    }
-
-    one_pass_set<L, PHASE, V>(a, smem, lay, binom, toff, vi, z, cm, rankP, ts);
-}
+#define ULG_CONS 0
+#include "cbic_score_layer.inc"
+#undef ULG_CONS
+#define ULG_CONS 1
+#include "cbic_score_layer.inc"
+#undef ULG_CONS
 
 // Layers 1..LF of every variable in ONE launch (option score_fused; the
 // small layers' one-pass form, V = variant & 65).  Workgroup b takes variable
@@ -871,43 +661,12 @@ __global__ void __launch_bounds__(kBlock, (score_min_waves<L, PHASE, V>())) scor
 // order the stores before the loads).  Replaces 2 LF dependent launches of
 // a few waves each (layers 1-4 at C3: ~117 us whatever the variable count).
 constexpr int kFusedThreads = 1024;
-template <int L, int PHASE, int LF, int V>
-__device__ __forceinline__ void fused_phase(const ScoreArgs &a, const uint64_t *work_all, unsigned char *smem,
-                                            const LdsLayout &lay, const double *g, const uint32_t *binom,
-                                            const uint64_t *toff, const int *smeta, const uint8_t *scand, int vi) {
-    const uint64_t *w = work_all + ((uint64_t)L * 2 + PHASE) * (uint64_t)(a.nv + 1);
-    const uint64_t cnt = w[vi + 1] - w[vi];
-    ScoreArgs as = a;
-    as.hsub_out = a.hsub_out || !(L == LF && PHASE == 1);
-    for (uint64_t r = threadIdx.x; r < cnt; r += kFusedThreads) {
-        const SetHead<L> hd = set_head<L, PHASE>(smeta, scand, binom, vi, r);
-        const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
-        one_pass_set<L, PHASE, V>(as, smem, lay, binom, toff, vi, hd.z, hd.cm, hd.rankP, ts);
-    }
-    __syncthreads();
-    if constexpr (PHASE == 0) fused_phase<L, 1, LF, V>(a, work_all, smem, lay, g, binom, toff, smeta, scand, vi);
-    else if constexpr (L < LF) fused_phase<L + 1, 0, LF, V>(a, work_all, smem, lay, g, binom, toff, smeta, scand, vi);
-}
-// a.hsub_out: whether layer LF's phase 1 writes the subset maxima (read by a
-// layer above LF); a.work unused (work_all: every (layer, phase) prefix)
-template <int LF, int V>
-__global__ void __launch_bounds__(kFusedThreads) score_small_kernel(ScoreArgs a, const uint64_t *work_all) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsLayout lay = lds_layout(a.n, a.nv, a.S, LF, V);
-    double *g = reinterpret_cast<double *>(smem + lay.gram);
-    uint32_t *binom = reinterpret_cast<uint32_t *>(smem + lay.binom);
-    uint64_t *toff = reinterpret_cast<uint64_t *>(smem + lay.toff);
-    int *smeta = reinterpret_cast<int *>(smem + lay.meta);
-    uint8_t *scand = reinterpret_cast<uint8_t *>(smem + lay.cand);
-    for (int i = threadIdx.x; i < a.n * a.n; i += kFusedThreads) g[i] = a.gram[i];
-    for (int i = threadIdx.x; i < 64 * kBinomK; i += kFusedThreads) binom[i] = a.binom[i];
-    for (int i = threadIdx.x; i <= a.nv * a.S; i += kFusedThreads) toff[i] = a.tbl_off[i];
-    for (int i = threadIdx.x; i < a.nv * 4; i += kFusedThreads) smeta[i] = a.meta[i];
-    for (int i = threadIdx.x; i < a.nv * 16; i += kFusedThreads)
-        reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
-    __syncthreads();
-    fused_phase<1, 0, LF, V>(a, work_all, smem, lay, g, binom, toff, smeta, scand, (int)blockIdx.x);
-}
+#define ULG_CONS 0
+#include "cbic_score_small.inc"
+#undef ULG_CONS
+#define ULG_CONS 1
+#include "cbic_score_small.inc"
+#undef ULG_CONS
 
 // Second half of a queued layer (variant bit 4): one wave (64 threads) per
 // 64*K queued sets.  Entry: table slot (low 32 bits) | ts bits (high 32), W
@@ -1361,108 +1120,14 @@ struct WideArgs {
     int n, nv, S, L;
 };
 
-template <int LMAX, int PHASE>
-__global__ void __launch_bounds__(kBlock) score_wide_kernel(WideArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *g = reinterpret_cast<double *>(smem);
-    for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
-    __syncthreads();
-    const uint64_t gid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (gid >= a.work[a.nv]) return;
-    int lo = 0, hi = a.nv;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.work[mid] <= gid) lo = mid; else hi = mid;
-    }
-    const int vi = lo;
-    const int v = a.meta[vi * 4 + 0];
-    const int m = a.meta[vi * 4 + 1];
-    const bool z = a.meta[vi * 4 + 2] != 0;
-    const int L = a.L;
-    const uint64_t r = gid - a.work[vi];
-    uint64_t cm;
-    if (PHASE == 0) cm = (unrank_colex64(r, L - 1, m - 1, a.binom) << 1) | 1ull;
-    else if (z) cm = unrank_colex64(r, L, m - 1, a.binom) << 1;
-    else cm = unrank_colex64(r, L, m, a.binom);
-    const uint64_t slot = a.tbl_off[(uint64_t)vi * a.S + L] + rank_colex64(cm, a.binom);
-
-    int gv[LMAX];
-    {
-        uint64_t rem = cm;
-        for (int i = 0; i < L; ++i) {
-            gv[i] = a.cand[vi * 64 + __builtin_ctzll(rem)];
-            rem &= rem - 1;
-        }
-    }
-    // Cholesky of G[P,P] (packed rows, row i at i(i+1)/2), y = L^-1 G[P,v]:
-    // the unrolled kernels' operation order
-    double Lm[LMAX * (LMAX + 1) / 2];
-    double y[LMAX];
-    const int n = a.n;
-    for (int i = 0; i < L; ++i) {
-        for (int j = 0; j <= i; ++j) Lm[i * (i + 1) / 2 + j] = g[gv[i] * n + gv[j]];
-        y[i] = g[gv[i] * n + v];
-    }
-    const double cvv = g[v * n + v];
-    for (int j = 0; j < L; ++j) {
-        const int rj = j * (j + 1) / 2;
-        double s = Lm[rj + j];
-        for (int k = 0; k < j; ++k) s -= Lm[rj + k] * Lm[rj + k];
-        const double d = sqrt(s);
-        Lm[rj + j] = d;
-        const double inv = 1.0 / d;
-        for (int i = j + 1; i < L; ++i) {
-            const int ri = i * (i + 1) / 2;
-            double t = Lm[ri + j];
-            for (int k = 0; k < j; ++k) t -= Lm[ri + k] * Lm[rj + k];
-            Lm[ri + j] = t * inv;
-        }
-    }
-    double yy = 0.0;
-    for (int i = 0; i < L; ++i) {
-        const int ri = i * (i + 1) / 2;
-        double t = y[i];
-        for (int k = 0; k < i; ++k) t -= Lm[ri + k] * y[k];
-        t = t / Lm[ri + i];
-        y[i] = t;
-        yy += t * t;
-    }
-    const double rss = cvv - yy;
-    // BIC_OLS.cpp:366
-    const double the_score = a.N * log(rss / a.N) + a.lambda * log(a.N) * (double)L - 0.0;
-    const float ts = (float)the_score;
-    if (ts >= 0.0f) {
-        const float s = -ts;  // stored by the caller iff < 0 (score_calculator.cpp:111)
-        a.table[slot] = (s < 0.0f) ? s : absent_f();
-        return;
-    }
-    const float thr = -ts;
-    const uint64_t coff = a.tbl_off[(uint64_t)vi * a.S + L - 1];
-    bool dom = false;
-    {
-        uint64_t rem = cm;
-        while (rem) {
-            const uint64_t bit = rem & (0 - rem);
-            rem ^= bit;
-            dom |= a.table[coff + rank_colex64(cm ^ bit, a.binom)] >= thr;  // absent (NaN) never >= thr
-        }
-    }
-    if (dom) {
-        a.table[slot] = absent_f();
-        return;
-    }
-    const unsigned long long act = __ballot(1);
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)act) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(a.qcount, (unsigned long long)__popcll(act));
-    base = __shfl(base, leader);
-    const uint64_t pos = base + (uint64_t)__popcll(act & ((1ull << lane) - 1ull));
-    uint64_t *e = a.queue + 3 * pos;
-    e[0] = slot;
-    e[1] = cm;
-    e[2] = (uint64_t)(uint32_t)vi | ((uint64_t)fbits(ts) << 32);
-}
+// A wide layer's scoring launch: the regression, the ts >= 0 exit, the direct
+// children's test; the undecided sets go to the walk queue.
+#define ULG_CONS 0
+#include "cbic_score_wide.inc"
+#undef ULG_CONS
+#define ULG_CONS 1
+#include "cbic_score_wide.inc"
+#undef ULG_CONS
 
 // One lane per queued set: find_best_subset_score replayed step by step.  A
 // frame at depth d holds T, the parent vector (L - d entries; entries past the
@@ -1663,6 +1328,11 @@ using WideWalkFn = void (*)(WideArgs, uint64_t, uint64_t, uint64_t *, uint64_t, 
 WideFn wide_fn(int L, int phase) {
     if (L <= 16) return phase == 0 ? score_wide_kernel<16, 0> : score_wide_kernel<16, 1>;
     return phase == 0 ? score_wide_kernel<kWideMax, 0> : score_wide_kernel<kWideMax, 1>;
+}
+using WideConsFn = void (*)(WideArgs, const uint64_t *, int);
+WideConsFn wide_cons_fn(int L, int phase) {
+    if (L <= 16) return phase == 0 ? score_wide_cons_kernel<16, 0> : score_wide_cons_kernel<16, 1>;
+    return phase == 0 ? score_wide_cons_kernel<kWideMax, 0> : score_wide_cons_kernel<kWideMax, 1>;
 }
 WideWalkFn wide_walk_fn(int L, int phase) {
     if (L <= 16) return phase == 0 ? walk_wide_kernel<16, 0> : walk_wide_kernel<16, 1>;
@@ -2088,6 +1758,17 @@ __global__ void call_prologue_kernel(const uint64_t *tbl_off, int nv, int S, flo
     if (qcount && i < nqc) qcount[i] = 0ull;
     if (qseg && i < nseg) qseg[i] = 0ull;
 }
+// ... under constraints: a variable whose every alternative requires a parent
+// has cache[empty] = -float(n) (the violator's value falls through to
+// BIC_OLS.cpp:249 and score_calculator.cpp:59 keeps it)
+__global__ void call_prologue_cons_kernel(const uint64_t *tbl_off, int nv, int S, float *table,
+                                          unsigned long long *qcount, uint64_t nqc, unsigned long long *qseg,
+                                          uint64_t nseg, const uint64_t *cons, int n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (uint64_t)nv) table[tbl_off[i * (uint64_t)S]] = cons_violates(cons, nv, (int)i, 0ull) ? -(float)n : -0.0f;
+    if (qcount && i < nqc) qcount[i] = 0ull;
+    if (qseg && i < nseg) qseg[i] = 0ull;
+}
 
 // ---- compaction of the slabs into (set, score) lists ------------------------
 constexpr int kSlotsPerThread = 16;  // contiguous slots per thread (four 16-B loads)
@@ -2290,68 +1971,23 @@ __global__ void quantize_kernel(const float *in, float *out, int64_t count) {
 // 300-303).  One lane per pair, parents in ascending order (parent_vec), the
 // Cholesky in the layer kernels' operation order, so a stored set's value is
 // the one ulg_cbic_score stored for it.
-__global__ void __launch_bounds__(kBlock) score_sets_kernel(const double *gram, const uint64_t *pairs, int64_t count,
-                                                            int n, double N, double lambda, float *out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *g = reinterpret_cast<double *>(smem);
-    for (int i = threadIdx.x; i < n * n; i += kBlock) g[i] = gram[i];
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= count) return;
-    const int v = (int)pairs[2 * i];
-    const uint64_t P = pairs[2 * i + 1] & ~(1ull << v);
-    const int L = __builtin_popcountll(P);
-    if (L == 0) {
-        out[i] = -0.0f;
-        return;
-    }
-    int gv[kWideMax];
-    {
-        uint64_t rem = P;
-        for (int j = 0; j < L; ++j) {
-            gv[j] = __builtin_ctzll(rem);
-            rem &= rem - 1;
-        }
-    }
-    double Lm[kWideMax * (kWideMax + 1) / 2];
-    double y[kWideMax];
-    for (int r = 0; r < L; ++r) {
-        for (int j = 0; j <= r; ++j) Lm[r * (r + 1) / 2 + j] = g[gv[r] * n + gv[j]];
-        y[r] = g[gv[r] * n + v];
-    }
-    const double cvv = g[v * n + v];
-    for (int j = 0; j < L; ++j) {
-        const int rj = j * (j + 1) / 2;
-        double s = Lm[rj + j];
-        for (int k = 0; k < j; ++k) s -= Lm[rj + k] * Lm[rj + k];
-        const double d = sqrt(s);
-        Lm[rj + j] = d;
-        const double inv = 1.0 / d;
-        for (int r = j + 1; r < L; ++r) {
-            const int rr = r * (r + 1) / 2;
-            double t = Lm[rr + j];
-            for (int k = 0; k < j; ++k) t -= Lm[rr + k] * Lm[rj + k];
-            Lm[rr + j] = t * inv;
-        }
-    }
-    double yy = 0.0;
-    for (int r = 0; r < L; ++r) {
-        const int rr = r * (r + 1) / 2;
-        double t = y[r];
-        for (int k = 0; k < r; ++k) t -= Lm[rr + k] * y[k];
-        t = t / Lm[rr + r];
-        y[r] = t;
-        yy += t * t;
-    }
-    const double rss = cvv - yy;
-    const double the_score = N * log(rss / N) + lambda * log(N) * (double)L - 0.0;  // BIC_OLS.cpp:366
-    out[i] = -(float)the_score;
-}
+#define ULG_CONS 0
+#include "cbic_score_sets.inc"
+#undef ULG_CONS
+#define ULG_CONS 1
+#include "cbic_score_sets.inc"
+#undef ULG_CONS
 
 using KernelFn = void (*)(ScoreArgs);
 template <int L, int V>
 KernelFn pick_phase(int phase) {
     return phase == 0 ? score_layer_kernel<L, 0, V> : score_layer_kernel<L, 1, V>;
+}
+// the constrained twins (score_layer_cons_kernel), the same (layer, phase, variant) dispatch
+using ConsKernelFn = void (*)(ScoreArgs, const uint64_t *, int);
+template <int L, int V>
+ConsKernelFn pick_phase_cons(int phase) {
+    return phase == 0 ? score_layer_cons_kernel<L, 0, V> : score_layer_cons_kernel<L, 1, V>;
 }
 // variants (ulg_set_option "score_variant"): bit 0 unrolled presence gathers
 // (layers <= 6), bit 4 two-pass (settle, queue the rest for a walk launch),
@@ -2372,6 +2008,17 @@ KernelFn pick(int phase, int variant) {
         case 65: return pick_phase<L, 65>(phase);
         case 113: return pick_phase<L, 81>(phase);
         case 241: return pick_phase<L, 209>(phase);
+        default: return nullptr;
+    }
+}
+template <int L>
+ConsKernelFn pick_cons(int phase, int variant) {
+    switch (variant) {
+        case 1: return pick_phase_cons<L, 1>(phase);
+        case 49: return pick_phase_cons<L, 17>(phase);
+        case 65: return pick_phase_cons<L, 65>(phase);
+        case 113: return pick_phase_cons<L, 81>(phase);
+        case 241: return pick_phase_cons<L, 209>(phase);
         default: return nullptr;
     }
 }
@@ -2467,6 +2114,15 @@ SmallFn small_kernel(int Lf) {
         default: return score_small_kernel<4, 65>;
     }
 }
+using SmallConsFn = void (*)(ScoreArgs, const uint64_t *, const uint64_t *, int);
+SmallConsFn small_cons_kernel(int Lf) {
+    switch (Lf) {
+        case 1: return score_small_cons_kernel<1, 65>;
+        case 2: return score_small_cons_kernel<2, 65>;
+        case 3: return score_small_cons_kernel<3, 65>;
+        default: return score_small_cons_kernel<4, 65>;
+    }
+}
 
 KernelFn layer_kernel(int L, int phase, int variant) {
     switch (L) {
@@ -2478,6 +2134,19 @@ KernelFn layer_kernel(int L, int phase, int variant) {
         case 6: return pick<6>(phase, variant);
         case 7: return pick<7>(phase, variant);
         case 8: return pick<8>(phase, variant);
+        default: return nullptr;
+    }
+}
+ConsKernelFn layer_cons_kernel(int L, int phase, int variant) {
+    switch (L) {
+        case 1: return pick_cons<1>(phase, variant);
+        case 2: return pick_cons<2>(phase, variant);
+        case 3: return pick_cons<3>(phase, variant);
+        case 4: return pick_cons<4>(phase, variant);
+        case 5: return pick_cons<5>(phase, variant);
+        case 6: return pick_cons<6>(phase, variant);
+        case 7: return pick_cons<7>(phase, variant);
+        case 8: return pick_cons<8>(phase, variant);
         default: return nullptr;
     }
 }
@@ -2657,6 +2326,17 @@ int score_wide_groups(ulg_ctx *c, int L, int ph, std::vector<WideGroup> &gs, int
         wa.S = S;
         wa.L = L;
         const uint64_t blocks = (G.cnt + kBlock - 1) / kBlock;
+        if (c->cons_call_words) {  // the call's constraint table (cbic_score)
+            const WideConsFn cf = wide_cons_fn(L, ph);
+            const int cw = c->cons_call_words;
+            const int lds = align16(c->n * c->n * 8) + (cw <= kConsLdsWords ? cw * 8 : 0);
+            if (lds > 64 * 1024)
+                ULG_HIP(c, hipFuncSetAttribute((const void *)cf, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            prof_begin_s(c, ph == 0 ? "score_wide_var0" : "score_wide_rest", G.st);
+            hipLaunchKernelGGL(cf, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, G.st, wa,
+                               (const uint64_t *)c->d_cons.p, cw);
+            prof_end_s(c, G.st);
+        } else {
         const WideFn sf = wide_fn(L, ph);
         const int lds = c->n * c->n * 8;
         if (lds > 64 * 1024)
@@ -2664,6 +2344,7 @@ int score_wide_groups(ulg_ctx *c, int L, int ph, std::vector<WideGroup> &gs, int
         prof_begin_s(c, ph == 0 ? "score_wide_var0" : "score_wide_rest", G.st);
         hipLaunchKernelGGL(sf, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, G.st, wa);
         prof_end_s(c, G.st);
+        }
         ULG_HIP(c, hipGetLastError());
         ULG_HIP(c, hipMemcpyAsync(pin + gi, G.qc, 8, hipMemcpyDeviceToHost, G.st));
     }
@@ -2949,6 +2630,12 @@ int ulg_cbic_load(ulg_ctx *c, const double *data, int64_t N, int n, double lambd
     ULG_HIP(c, hipSetDevice(c->device));
     c->loaded = false;
     c->scored = false;
+    if (!c->cons_var.empty()) {  // constraints belong to the data they were set for
+        graph_reset(c);
+        c->cons_var.clear();
+        c->cons_req.clear();
+        c->cons_forb.clear();
+    }
     c->n = n;
     c->N = N;
     c->lambda = lambda;
@@ -3172,6 +2859,45 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
         (rc = upload(c, c->d_meta, c->mir_meta, meta)) || (rc = ensure(c, c->out_sets, total_slots)) ||
         (rc = ensure(c, c->out_scores, total_slots)) || (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
         return rc;
+
+    // the call's constraint table: the alternatives of the scored variables in
+    // their compact candidate numbering (cons_violates); none -> the
+    // unconstrained kernels
+    int cons_words = 0;
+    if (!c->cons_var.empty()) {
+        std::vector<uint64_t> ct((size_t)nv + 1, 0);
+        for (int i = 0; i < nv; ++i) {
+            ct[i] = (ct.size() - (size_t)(nv + 1)) / 2;
+            const uint64_t C = candidates[i] & allmask & ~(1ull << vars[i]);
+            auto compact = [&](uint64_t mask) {
+                uint64_t out = 0;
+                for (int k = 0; k < mv[i]; ++k)
+                    if ((mask >> cand[(size_t)i * 64 + k]) & 1ull) out |= 1ull << k;
+                return out;
+            };
+            bool any = false, kept = false;
+            for (size_t j = 0; j < c->cons_var.size(); ++j) {
+                if (c->cons_var[j] != vars[i]) continue;
+                any = true;
+                if (c->cons_req[j] & ~C) continue;  // requires a non-candidate (or the variable itself)
+                kept = true;
+                ct.push_back(compact(c->cons_req[j]));
+                ct.push_back(compact(c->cons_forb[j]));
+            }
+            if (any && !kept) {  // every set of this variable violates
+                ct.push_back(1ull << 63);
+                ct.push_back(0);
+            }
+        }
+        ct[nv] = (ct.size() - (size_t)(nv + 1)) / 2;
+        if (ct[nv] > 0) {
+            if ((rc = upload(c, c->d_cons, c->mir_cons, ct))) return rc;
+            cons_words = (int)ct.size();
+        }
+    }
+    c->cons_call_words = cons_words;
+    const uint64_t *d_cons = cons_words ? c->d_cons.p : nullptr;
+    const int cons_lds = cons_words && cons_words <= kConsLdsWords ? cons_words * 8 : 0;
 
     ScoreArgs sa;
     sa.hsub_out = 1;
@@ -3400,7 +3126,8 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
                      (uint64_t)(uintptr_t)c->out_offsets.p, (uint64_t)(uintptr_t)c->d_blk.p,
                      (uint64_t)(uintptr_t)c->gram.p, (uint64_t)(uintptr_t)c->d_binom.p,
                      (uint64_t)(uintptr_t)c->d_binom64.p, (uint64_t)(uintptr_t)c->d_hsub.p, (uint64_t)total_slots,
-                     (uint64_t)c->score_small_layers, (uint64_t)c->score_fused});
+                     (uint64_t)c->score_small_layers, (uint64_t)c->score_fused, (uint64_t)cons_words,
+                     (uint64_t)(uintptr_t)d_cons});
         for (int i = 0; i < nv; ++i) gkey.push_back((uint64_t)vars[i]);
         for (int i = 0; i < nv; ++i) gkey.push_back(candidates[i]);
         for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
@@ -3419,6 +3146,11 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
     {
         const uint64_t nz = std::max<uint64_t>((uint64_t)nv, std::max<uint64_t>(zero_q ? nqc : 0, nqseg));
         prof_begin(c, "call_prologue");
+        if (d_cons)
+            call_prologue_cons_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, c->stream>>>(
+                c->d_tbl_off.p, nv, S, c->table.p, zero_q ? c->d_qcount.p : nullptr, zero_q ? nqc : 0,
+                zero_q ? c->d_qseg.p : nullptr, nqseg, d_cons, n);
+        else
         call_prologue_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, c->stream>>>(
             c->d_tbl_off.p, nv, S, c->table.p, zero_q ? c->d_qcount.p : nullptr, zero_q ? nqc : 0,
             zero_q ? c->d_qseg.p : nullptr, nqseg);
@@ -3434,6 +3166,18 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
                     ss.qcount = nullptr;
                     ss.hsub_out = Lf < kmax;  // layer Lf's phase 1 maxima: read only by a layer above
                     const LdsLayout lay = lds_layout(n, nv, S, Lf, 65);
+                    if (d_cons) {
+                        const SmallConsFn cfn = small_cons_kernel(Lf);
+                        const int lds = align16(lay.total) + cons_lds;
+                        if (lds > 64 * 1024)
+                            ULG_HIP(c, hipFuncSetAttribute((const void *)cfn,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                        prof_begin_s(c, "score_small_fused", c->stream);
+                        hipLaunchKernelGGL(cfn, dim3((unsigned)nv), dim3(kFusedThreads), (size_t)lds, c->stream, ss,
+                                           (const uint64_t *)c->d_work.p, d_cons, cons_words);
+                        prof_end_s(c, c->stream);
+                        continue;
+                    }
                     const SmallFn kfn = small_kernel(Lf);
                     if (lay.total > 64 * 1024)
                         ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3455,6 +3199,17 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
                 ss.qcount = nullptr;
                 ss.hsub_out = !(L == kmax && ph == 1);
                 const LdsLayout lay = lds_layout(n, nv, S, L, vsmall);
+                if (d_cons) {
+                    const ConsKernelFn cfn = layer_cons_kernel(L, ph, vsmall);
+                    const int lds = align16(lay.total) + cons_lds;
+                    if (lds > 64 * 1024)
+                        ULG_HIP(c, hipFuncSetAttribute((const void *)cfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                    prof_begin_s(c, kLayerNames[ph][L], c->stream);
+                    hipLaunchKernelGGL(cfn, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock), (size_t)lds,
+                                       c->stream, ss, d_cons, cons_words);
+                    prof_end_s(c, c->stream);
+                    continue;
+                }
                 const KernelFn kfn = layer_kernel(L, ph, vsmall);
                 if (lay.total > 64 * 1024)
                     ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
@@ -3517,12 +3272,22 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
                     continue;
                 }
                 const LdsLayout lay = lds_layout(n, nv, S, L, variant);
+                if (d_cons) {
+                    const ConsKernelFn cfn = layer_cons_kernel(L, ph, variant);
+                    const int lds = align16(lay.total) + cons_lds;
+                    if (lds > 64 * 1024)
+                        ULG_HIP(c, hipFuncSetAttribute((const void *)cfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+                    prof_begin_s(c, kLayerNames[ph][L], st);
+                    hipLaunchKernelGGL(cfn, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, st, sa, d_cons, cons_words);
+                    prof_end_s(c, st);
+                } else {
                 const KernelFn kfn = layer_kernel(L, ph, variant);
                 if (lay.total > 64 * 1024)
                     ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
                 prof_begin_s(c, kLayerNames[ph][L], st);
                 hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(kBlock), (size_t)lay.total, st, sa);
                 prof_end_s(c, st);
+                }
                 if (variant & 16) {
                     // the undecided lanes of this launch, densely packed
                     const int wk = sliced_k(L, cnt, (uint64_t)c->walk_small_sets, c->walk_k6);
@@ -3702,6 +3467,55 @@ int ulg_cbic_fetch(ulg_ctx *c, uint64_t *sets, float *scores, int64_t *offsets, 
     return ULG_OK;
 }
 
+int ulg_cbic_set_constraints(ulg_ctx *c, int count, const int *vars, const uint64_t *required,
+                             const uint64_t *forbidden) {
+    if (!c) return ULG_ERR_ARG;
+    if (!c->loaded) return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: call ulg_cbic_load first");
+    if (count < 0 || (count > 0 && (!vars || !required || !forbidden)))
+        return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: bad arguments");
+    const int n = c->n;
+    const uint64_t allmask = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
+    std::vector<int> per(n, 0);
+    for (int i = 0; i < count; ++i) {
+        if (vars[i] < 0 || vars[i] >= n)
+            return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: variable out of range");
+        if ((required[i] | forbidden[i]) & ~allmask)
+            return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: mask bit >= n");
+        if (++per[vars[i]] > ULG_MAX_CONSTRAINT_ALTERNATIVES)
+            return set_err(c, ULG_ERR_UNSUPPORTED,
+                           "ulg_cbic_set_constraints: more than ULG_MAX_CONSTRAINT_ALTERNATIVES (64) alternatives "
+                           "for variable " + std::to_string(vars[i]));
+    }
+    if (c->async_pending) {  // the launches in flight read the tables
+        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
+        if (rc0) return rc0;
+    }
+    ULG_HIP(c, hipSetDevice(c->device));
+    // the captured scoring graph holds the kernels and the table pointer of
+    // the constraints it was captured under
+    graph_reset(c);
+    c->cons_var.assign(vars, vars + count);
+    c->cons_req.assign(required, required + count);
+    c->cons_forb.assign(forbidden, forbidden + count);
+    c->cons_call_words = 0;
+    if (count == 0) return ULG_OK;
+    // ulg_cbic_score_sets' table: by variable, in variable masks
+    std::vector<uint64_t> ct((size_t)n + 1, 0);
+    for (int v = 0; v < n; ++v) {
+        ct[v] = (ct.size() - (size_t)(n + 1)) / 2;
+        for (int i = 0; i < count; ++i)
+            if (vars[i] == v) {
+                ct.push_back(required[i]);
+                ct.push_back(forbidden[i]);
+            }
+    }
+    ct[n] = (ct.size() - (size_t)(n + 1)) / 2;
+    int rc;
+    if ((rc = ensure(c, c->d_cons_var, ct.size()))) return rc;
+    ULG_HIP(c, hipMemcpy(c->d_cons_var.p, ct.data(), ct.size() * 8, hipMemcpyHostToDevice));
+    return ULG_OK;
+}
+
 int ulg_cbic_score_vars(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
                         uint64_t *sets, float *scores, int64_t *offsets, int64_t cap) {
     int64_t stored = 0;
@@ -3731,6 +3545,10 @@ int ulg_cbic_score_sets(ulg_ctx *c, int64_t count, const int *vars, const uint64
     if ((rc = ensure(c, c->d_sets_in, (size_t)count * 2)) || (rc = ensure(c, c->qbuf_out, (size_t)count))) return rc;
     ULG_HIP(c, hipMemcpyAsync(c->d_sets_in.p, pairs.data(), (size_t)count * 16, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, "score_sets");
+    if (!c->cons_var.empty())
+        score_sets_cons_kernel<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, (size_t)n * n * 8, c->stream>>>(
+            c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p, c->d_cons_var.p);
+    else
     score_sets_kernel<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, (size_t)n * n * 8, c->stream>>>(
         c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p);
     prof_end(c);

@@ -1,0 +1,270 @@
+// cbic_score_layer.inc -- the body of score_layer_kernel, included by cbic.hip
+// once per form: ULG_CONS 0 is score_layer_kernel, 1 its constrained
+// twin score_layer_cons_kernel (launched while the context holds
+// constraints): a set that violates its variable's constraints takes
+// ts = float(n) (BIC_OLS.cpp:279-283) without a regression, and everything
+// after ts is the same text.  Two kernels from one text, not one template
+// with a flag: the unconstrained kernels keep the code, and so the register
+// allocation, they had before constraints existed (DESIGN.md 3.1h).
+template <int L, int PHASE, int V>
+__global__ void __launch_bounds__(kBlock, (score_min_waves<L, PHASE, V>()))
+#if ULG_CONS
+score_layer_cons_kernel(ScoreArgs a, const uint64_t *cons, int cons_words) {
+#else
+score_layer_kernel(ScoreArgs a) {
+#endif
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const LdsLayout lay = lds_layout(a.n, a.nv, a.S, L, V);
+#if ULG_CONS
+    const uint64_t *ct = cons_stage<kBlock>(smem, lay.total, cons, cons_words);
+#endif
+    double *g = reinterpret_cast<double *>(smem + lay.gram);
+    uint32_t *binom = reinterpret_cast<uint32_t *>(smem + lay.binom);
+    uint64_t *work = reinterpret_cast<uint64_t *>(smem + lay.work);
+    uint64_t *toff = reinterpret_cast<uint64_t *>(smem + lay.toff);
+    // the per-variable metadata and candidate lists too: every lane reads
+    // them right after its variable is known, and from global memory those
+    // would be two more dependent round trips per lane
+    int *smeta = reinterpret_cast<int *>(smem + lay.meta);
+    uint8_t *scand = reinterpret_cast<uint8_t *>(smem + lay.cand);
+    for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
+    for (int i = threadIdx.x; i < 64 * kBinomK; i += kBlock) binom[i] = a.binom[i];
+    for (int i = threadIdx.x; i <= a.nv; i += kBlock) work[i] = a.work[i];
+    for (int i = threadIdx.x; i <= a.nv * a.S; i += kBlock) toff[i] = a.tbl_off[i];
+    for (int i = threadIdx.x; i < a.nv * 4; i += kBlock) smeta[i] = a.meta[i];
+    for (int i = threadIdx.x; i < a.nv * 16; i += kBlock)
+        reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
+    __syncthreads();
+
+    constexpr bool HM = (V & 64) != 0;           // subset maxima kept up to date
+    constexpr bool CMP = HM && (V & 16) != 0;     // ... and the sets settled by them first
+    const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
+    const bool valid = gid0 < work[a.nv];
+    if (!CMP && !valid) return;
+    // CMP: every lane reaches the block's barrier; a lane past the launch's
+    // sets scores the last one again and writes nothing
+    const uint64_t gid = valid ? gid0 : work[a.nv] - 1;
+    int lo = 0, hi = a.nv;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (work[mid] <= gid) lo = mid; else hi = mid;
+    }
+    const int vi = lo;
+    const uint64_t r = gid - work[vi];
+    const SetHead<L> hd = set_head<L, PHASE>(smeta, scand, binom, vi, r);
+    const bool z = hd.z;
+    const uint64_t cm = hd.cm, rankP = hd.rankP;
+
+#ifndef ULG_PROBE_NOSCORE  // ULG_PROBE_*: timing-only builds, see the two-pass section below
+#if ULG_CONS
+    float ts = (float)a.n;
+    if (!cons_violates(ct, a.nv, vi, cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+#else
+    const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+#endif
+#else
+    const float ts = (float)(-a.N * g[hd.gv[0] * a.n + hd.gv[L - 1]] - (double)(r & 1023));
+#endif
+
+    if constexpr (CMP) {
+        // 1. settle by the subset maxima: ts >= 0, no key >= -ts in U(P), or a
+        //    present direct child >= -ts (always visited at the top level)
+        const uint64_t vbase = (uint64_t)vi * a.S;
+        const uint64_t slot = toff[vbase + L] + rankP;
+        uint64_t rc[L], rz[L];
+        child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
+        // every load of the settle issued at once (the children's maxima and
+        // values, the var-0 toggles' maxima): one memory round trip instead
+        // of up to three dependent ones
+        float hch = absent_f();  // max over the proper nonempty subsets of P
+        float hz = absent_f();   // ... and over the toggles P\a + {0}
+        bool dh = false;         // a direct child >= -ts
+#ifdef ULG_GATHER_STATS
+        uint32_t hotA = 0u;      // children P\a_i holding a key >= -ts (hsub)
+        uint32_t hotZ = 0u;      // toggled children P\a_i + {0} holding one
+#endif
+        {
+            float ch[L], cv[L], zv[L];
+            const uint32_t o1 = (uint32_t)toff[vbase + L - 1], o0 = (uint32_t)toff[vbase + L];
+#pragma unroll
+            for (int i = 0; i < L; ++i) {
+                if constexpr (L > 1) {
+                    ch[i] = a.hsub[o1 + (uint32_t)rc[i]];
+                    cv[i] = a.table[o1 + (uint32_t)rc[i]];
+                }
+                if constexpr (PHASE == 1) zv[i] = a.hsub[(z ? o0 : 0u) + (z ? (uint32_t)rz[i] : 0u)];
+            }
+            const float thr = -ts;
+#pragma unroll
+            for (int i = 0; i < L; ++i) {
+                if constexpr (L > 1) {
+                    hch = fmaxf(hch, ch[i]);
+                    dh |= cv[i] >= thr;
+#ifdef ULG_GATHER_STATS
+                    hotA |= (ch[i] >= thr) ? 1u << i : 0u;
+#endif
+                }
+                if constexpr (PHASE == 1) {
+                    hz = fmaxf(hz, zv[i]);
+#ifdef ULG_GATHER_STATS
+                    hotZ |= (zv[i] >= thr) ? 1u << i : 0u;
+#endif
+                }
+            }
+            if (!z) hz = absent_f();
+#ifdef ULG_GATHER_STATS
+            if (!z) hotZ = 0u;
+#endif
+        }
+        bool need = false;
+        float out;
+        if (ts >= 0.0f) {
+            const float s = -ts;
+            out = (s < 0.0f) ? s : absent_f();
+        } else {
+            const float thr = -ts;
+            const float hu = fmaxf(hch, hz);
+            out = -ts;
+            if (hu >= thr) {
+                out = absent_f();
+                need = !dh;
+            }
+        }
+        if (valid && !need) {
+            a.table[slot] = out;
+            if (a.hsub_out) a.hsub[slot] = fmaxf(out, hch);
+        }
+// ULG_PROBE_*: timing-only builds (wrong lists, never shipped) that drop one
+// part of the two-pass kernel (scripts/r5_kernel_ab.sh, DESIGN.md §3.1d)
+#ifdef ULG_PROBE_NOCMP  // the undecided sets are left undecided
+        return;
+#endif
+        // 2. the rest of the block's sets, compacted in LDS, so the presence
+        //    gathers (2^(L+1) reads each) run on dense waves
+        unsigned int *cnt = reinterpret_cast<unsigned int *>(smem + lay.cmp);
+        uint64_t *ecm = reinterpret_cast<uint64_t *>(smem + lay.cmp + 16);
+        uint32_t *eslot = reinterpret_cast<uint32_t *>(ecm + kBlock);
+        float *ets = reinterpret_cast<float *>(eslot + kBlock);
+        float *ehch = ets + kBlock;
+        int *evi = reinterpret_cast<int *>(ehch + kBlock);
+        if (threadIdx.x == 0) {
+            cnt[0] = 0u;
+            cnt[1] = 0u;  // the second compaction's count (variant bit 7)
+        }
+        __syncthreads();
+        if (valid && need) {
+            const unsigned int k = atomicAdd(cnt, 1u);
+            ecm[k] = cm;
+            eslot[k] = (uint32_t)slot;
+            ets[k] = ts;
+            ehch[k] = hch;
+#ifdef ULG_GATHER_STATS
+            evi[k] = vi | (int)(hotA << 8) | (int)(hotZ << 16);
+#else
+            evi[k] = vi;
+#endif
+        }
+        __syncthreads();
+        constexpr int W = bits_words(L);
+        using BS = std::conditional_t<(W >= 4), BitsLds<W>, Bits<W>>;
+        constexpr bool CMP2 = (V & 128) != 0 && W < 4;
+        if constexpr (!CMP2)
+            if (threadIdx.x >= *cnt) return;
+        const int k = threadIdx.x;
+        const bool a1 = threadIdx.x < cnt[0];
+        const uint64_t seg = walk_segment();
+        // this lane's compacted set (the lanes past the count, variant bit 7
+        // only, carry a dummy and gather nothing)
+        const int vk = a1 ? evi[k] & 0xff : 0;
+#ifdef ULG_GATHER_STATS
+        const uint32_t hk = a1 ? (uint32_t)evi[k] >> 8 : 0u;  // hotA | hotZ << 8
+#endif
+        const bool zk = smeta[vk * 4 + 2] != 0;
+        const float tk = a1 ? ets[k] : -1.0f;
+        const uint64_t sk = a1 ? eslot[k] : 0u;
+        const uint64_t cmk = a1 ? ecm[k] : 1ull;
+        const float hk1 = a1 ? ehch[k] : absent_f();
+        uint64_t *lds_bits = reinterpret_cast<uint64_t *>(smem + lay.bits) + threadIdx.x;
+        const LocalSet<L> ls = local_set<L, PHASE>(cmk, zk);
+        BS present = make_bits<BS>(lds_bits);
+        BS hib = make_bits<BS>(lds_bits + (size_t)W * kBlock);
+        present.clear();
+        hib.clear();
+        bool q = false;
+        if (a1) {
+            // the keys the two-level rules read first; the rest only for the
+            // sets the rules leave to the walk (the subset maxima already
+            // showed a key >= -ts is present, so the rules need no "any key"
+            // test)
+#ifndef ULG_PROBE_NOPART1
+            gather_keys<L, PHASE, V, BS, LdPlain, 1>(present, hib, ls, -tk, binom, zk, a.table,
+                                                    toff + (uint64_t)vk * a.S);
+#endif
+#ifndef ULG_PROBE_NORULES
+            const bool dom = settle_rules<L, PHASE, BS, true>(present, hib, ls, q);
+#else
+            const bool dom = false;
+            q = false;
+#endif
+#ifdef ULG_GATHER_STATS
+            if constexpr (W < 4) {
+                BS p2 = make_bits<BS>(lds_bits), h2 = make_bits<BS>(lds_bits);
+                p2.clear();
+                h2.clear();
+                gather_keys<L, PHASE, V, BS, LdPlain, 0>(p2, h2, ls, -tk, binom, zk, a.table,
+                                                        toff + (uint64_t)vk * a.S);
+                gather_stats<L, PHASE>(p2, h2, hk & 0xffu, hk >> 8, zk, q);
+            }
+#endif
+            if (!q) {
+                const float o = dom ? absent_f() : -tk;
+                a.table[sk] = o;
+                if (a.hsub_out) a.hsub[sk] = fmaxf(o, hk1);
+            }
+        }
+        if constexpr (CMP2) {
+            // 3. the sets the rules leave to the walk (about a third of the
+            //    compacted ones) compacted once more, with their gathered
+            //    words, so the rest of the gathers, the walk closure and the
+            //    queue run on dense waves: at ~30 % of the lanes every wave
+            //    would still issue them
+            uint64_t *c2w = reinterpret_cast<uint64_t *>(smem + lay.cmp2);  // [2W][kBlock]
+            __syncthreads();  // every lane has read its first entry
+            if (q) {
+                const unsigned int k2 = atomicAdd(cnt + 1, 1u);
+                ecm[k2] = cmk;
+                eslot[k2] = (uint32_t)sk;
+                ets[k2] = tk;
+                ehch[k2] = hk1;
+                evi[k2] = vk;
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    c2w[j * kBlock + k2] = present.word(j);
+                    c2w[(W + j) * kBlock + k2] = hib.word(j);
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x >= cnt[1]) return;
+            const int vq = evi[k];
+            const bool zq = smeta[vq * 4 + 2] != 0;
+            const float tq = ets[k];
+            const uint64_t sq = eslot[k];
+            const float hq = ehch[k];
+            const LocalSet<L> lq = local_set<L, PHASE>(ecm[k], zq);
+            BS pq = make_bits<BS>(lds_bits), hq_bits = make_bits<BS>(lds_bits);
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                pq.w[j] = c2w[j * kBlock + k];
+                hq_bits.w[j] = c2w[(W + j) * kBlock + k];
+            }
+            walk_or_store<L, PHASE, V, BS>(a, pq, hq_bits, lq, tq, binom, zq, toff + (uint64_t)vq * a.S, seg, sq, hq);
+        } else {
+            if (q)
+                walk_or_store<L, PHASE, V, BS>(a, present, hib, ls, tk, binom, zk, toff + (uint64_t)vk * a.S, seg, sk,
+                                               hk1);
+        }
+        return;
+    }
+
+    one_pass_set<L, PHASE, V>(a, smem, lay, binom, toff, vi, z, cm, rankP, ts);
+}

@@ -168,6 +168,7 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->d_qaux); release(c->d_qsidx); release(c->d_qoffs); release(c->d_qkey);
     release(c->out_sets); release(c->out_scores); release(c->out_offsets);
     release(c->qbuf_in); release(c->qbuf_out);
+    release(c->d_cons); release(c->d_cons_var);
     pss_release(c);
     if (c->search) {
         c->search->release_all();
@@ -313,6 +314,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // (1), a walk-queue segment overflow (2) or a walk entry past the table (4)
     if (std::strcmp(name, "score_error_word") == 0) {
         *value = (int64_t)c->last_err_word;
+        return ULG_OK;
+    }
+    // alternatives held by ulg_cbic_set_constraints
+    if (std::strcmp(name, "constraints") == 0) {
+        *value = (int64_t)c->cons_var.size();
         return ULG_OK;
     }
     // the last exact A*'s host counters (user space, the calling thread; -1: not granted)

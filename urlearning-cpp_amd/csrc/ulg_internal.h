@@ -122,6 +122,13 @@ struct ulg_ctx {
     ulg::DevBuf<float> out_scores;
     ulg::DevBuf<int64_t> out_offsets;
 
+    // ---- parent-set constraints (ulg_cbic_set_constraints) ----
+    std::vector<int> cons_var;                    // one entry per alternative: its variable,
+    std::vector<uint64_t> cons_req, cons_forb;    // required and forbidden parents (variable masks)
+    ulg::DevBuf<uint64_t> d_cons_var;             // by variable, variable masks (ulg_cbic_score_sets)
+    ulg::DevBuf<uint64_t> d_cons;                 // the scoring call's table: by call index, compact masks
+    int cons_call_words = 0;                      // its words (0: the call runs the unconstrained kernels)
+
     ulg::DevBuf<float> qbuf_in, qbuf_out;
     ulg::DevBuf<uint64_t> d_sets_in;              // ulg_cbic_score_sets: (variable, parent mask) pairs
 
@@ -137,7 +144,7 @@ struct ulg_ctx {
     std::set<std::string> prof_only;  // ulg_profile_select: time only these kernels
     std::mutex mu;  // err / pending: the wide scoring layers use one host thread per stream group
     std::vector<hipEvent_t> event_pool;
-    ulg::Mirror mir_tbl_off, mir_work, mir_cand, mir_meta, mir_workg, mir_hoff, mir_vwork;
+    ulg::Mirror mir_tbl_off, mir_work, mir_cand, mir_meta, mir_workg, mir_hoff, mir_vwork, mir_cons;
     ulg::DevBuf<float> d_hmax;      // wide walks: hi-cover tables (subset max of the present keys), then the present keys
     uint64_t hmax_half = 0;         // entries of each half of d_hmax
     ulg::DevBuf<uint64_t> d_hoff;   // [nv] table offsets, ~0 = no table

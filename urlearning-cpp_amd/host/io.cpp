@@ -434,6 +434,75 @@ bool read_pss(const std::string &path, PssData &out, std::string &err) {
     return true;
 }
 
+bool read_constraints(const std::string &path, const std::vector<std::string> &names, Constraints &out,
+                      std::string &err) {
+    out = Constraints();
+    if (names.size() > 64) {
+        err = "constraints need at most 64 variables (varsets are 64-bit masks)";
+        return false;
+    }
+    std::ifstream f(path);
+    if (!f) {
+        err = "cannot open constraints file '" + path + "'";
+        return false;
+    }
+    std::unordered_map<std::string, int> index;  // nameToIndex: a repeated name keeps its last index
+    for (size_t i = 0; i < names.size(); ++i) index[names[i]] = (int)i;
+    auto lookup = [&](const std::string &name, const std::string &token, int lineno, int &idx) {
+        auto it = index.find(name);
+        if (it == index.end()) {
+            err = "constraints file '" + path + "' line " + std::to_string(lineno) +
+                  ": expecting a variable name, but found '" + token + "'";
+            return false;
+        }
+        idx = it->second;
+        return true;
+    };
+    std::string line;
+    int lineno = 0;
+    while (std::getline(f, line)) {
+        ++lineno;
+        const std::string stripped = trim(line.substr(0, line.find('#')));
+        if (stripped.empty()) continue;
+        // boost::char_separator(", "): space and comma, empty tokens dropped
+        std::vector<std::string> tok;
+        std::string cur;
+        for (char ch : stripped) {
+            if (ch == ',' || ch == ' ') {
+                if (!cur.empty()) tok.push_back(cur);
+                cur.clear();
+            } else {
+                cur.push_back(ch);
+            }
+        }
+        if (!cur.empty()) tok.push_back(cur);
+        if (tok.empty()) continue;  // only separators
+        int variable = 0;
+        if (!lookup(tok[0], tok[0], lineno, variable)) return false;
+        uint64_t required = 0, forbidden = 0;
+        for (size_t i = 1; i < tok.size(); ++i) {
+            const std::string &t = tok[i];
+            int p = 0;
+            if (t == ")") {
+                out.vars.push_back(variable);
+                out.required.push_back(required);
+                out.forbidden.push_back(forbidden);
+                required = forbidden = 0;
+            } else if (t[0] == '!') {
+                if (!lookup(t.substr(1), t, lineno, p)) return false;
+                forbidden |= 1ull << p;
+            } else if (t == "(") {
+                // skipped, nested or not
+            } else {
+                if (!lookup(t, t, lineno, p)) return false;
+                required |= 1ull << p;
+            }
+        }
+        // what follows the last ")" never reaches addConstraint
+    }
+    return true;
+}
+
 bool write_net_csv(const std::string &path, const std::vector<uint64_t> &vpar, int n) {
     std::ofstream f(path, std::ios::trunc);
     if (!f) return false;

@@ -55,6 +55,23 @@ struct PssData {
 };
 bool read_pss(const std::string &path, PssData &out, std::string &err);
 
+// scoring::parseConstraints (scoring_function/constraints.h:161-236): one line
+// per variable entry, "#" starts a comment, the line is trimmed, tokens split
+// on space and comma (a tab separates nothing); the first token names the
+// variable, "(" is skipped, ")" closes one alternative (required, forbidden)
+// and clears both masks, "!name" forbids, any other token requires; tokens
+// after the last ")" are dropped and further lines of a variable append.
+// names: the .pss names (record_stats).  Unlike the reference, whose
+// nameToIndex[] lookup inserts a missing key (a misspelt name silently means
+// variable 0, base/bayesian_network.cpp:48-53), an unknown name is an error
+// naming the token and the line; so is a file that cannot be opened.
+struct Constraints {
+    std::vector<int> vars;  // one entry per alternative
+    std::vector<uint64_t> required, forbidden;
+};
+bool read_constraints(const std::string &path, const std::vector<std::string> &names, Constraints &out,
+                      std::string &err);
+
 // netFile text and netFile.csv (astar/astar_main.cpp:192-212, 518-533)
 bool write_net_csv(const std::string &path, const std::vector<uint64_t> &vpar, int n);
 bool write_text(const std::string &path, const std::string &text);

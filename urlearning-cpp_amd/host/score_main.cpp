@@ -3,7 +3,7 @@
 // scored by libulg.so on one GPU, and the .pss score cache is written in the
 // reference's exact text format.
 //
-//   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-p k] [-s] [-d ,]
+//   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //
 // Options that only matter for other scoring functions or for the reference's
 // AD-tree (-m, -e, -w, -a, -o, --enableDeCamposPruning) are accepted; -e
@@ -25,7 +25,7 @@ int main(int argc, char **argv) {
             {"l", "lambda", true, "0.5", "The lambda (BIC penalty weight)."},
             {"a", "adaptive", false, "", "Use adaptive Lasso (not on this path)."},
             {"w", "scoreType", true, "1", "which score (not on this path)"},
-            {"c", "constraints", true, "", "The file specifying constraints on the scores (unsupported)."},
+            {"c", "constraints", true, "", "The file specifying constraints on the scores."},
             {"k", "skeleton", true, "", "The file specifying the skeleton superstructure"},
             {"m", "rMin", true, "5", "The minimum number of records in the AD-tree nodes (unused by cBIC)."},
             {"f", "function", true, "BIC", "The scoring function to use (cBIC)."},
@@ -55,10 +55,6 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "score: scoring function '%s' is not on this path; use -f cBIC\n", args.get("function").c_str());
         return 2;
     }
-    if (!args.get("constraints").empty()) {
-        std::fprintf(stderr, "score: constraint files (-c) are not supported on this path\n");
-        return 2;
-    }
     const std::string input = args.get("input"), output = args.get("output");
     const char delim = args.get("delimiter").empty() ? ',' : args.get("delimiter")[0];
     const bool has_header = args.has("hasHeader");
@@ -83,6 +79,17 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (maxp > n || maxp < 1) maxp = n - 1;  // score_main.cpp:296-298
+    // -c: scoring::parseConstraints over the .pss names (score_main.cpp:314-317)
+    const std::string cons_file = args.get("constraints");
+    ulgio::Constraints cons;
+    if (!cons_file.empty()) {
+        std::printf("Constraints file: '%s'\n", cons_file.c_str());  // score_main.cpp:270
+        std::string cerr_;
+        if (!ulgio::read_constraints(cons_file, rs.names, cons, cerr_)) {
+            std::fprintf(stderr, "score: %s\n", cerr_.c_str());
+            return 1;
+        }
+    }
     // candidates: 2-hop skeleton neighbourhood; no -k = every variable
     std::vector<uint64_t> cands(n, n >= 64 ? ~0ull : ((1ull << n) - 1ull));
     const std::string skel = args.get("skeleton");
@@ -112,6 +119,9 @@ int main(int argc, char **argv) {
         std::printf("I am using a timer in the calculation function.\n");  // score_calculator.cpp:40
         if (rc == ULG_OK) rc = ulg_set_option(ctx, "time_limit_ms", (int64_t)running_time * 1000);
     }
+    if (rc == ULG_OK && !cons.vars.empty())
+        rc = ulg_cbic_set_constraints(ctx, (int)cons.vars.size(), cons.vars.data(), cons.required.data(),
+                                      cons.forbidden.data());
     if (rc == ULG_OK) rc = ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
     int64_t oot = 0, done_layer = 0;
     if (rc == ULG_OK && running_time > 0) {

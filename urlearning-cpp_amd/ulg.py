@@ -44,6 +44,7 @@ def lib():
         L.ulg_cbic_fetch.argtypes = [P, P, P, P, I]
         L.ulg_cbic_score_vars.argtypes = [P, P, I, P, I, P, P, P, I64]
         L.ulg_cbic_score_sets.argtypes = [P, I64, P, P, P]
+        L.ulg_cbic_set_constraints.argtypes = [P, I, P, P, P]
         L.ulg_quantize_costs.argtypes = [P, P, P, I64]
         L.ulg_search_load.argtypes = [P, I, P, P, P]
         L.ulg_search_from_scores.argtypes = [P]
@@ -194,6 +195,22 @@ class Context:
         out = np.empty(max(len(v), 1), dtype=np.float32)
         self._check(lib().ulg_cbic_score_sets(self._h, len(v), _ptr(v), _ptr(p), _ptr(out)), "ulg_cbic_score_sets")
         return out[:len(v)]
+
+    def set_constraints(self, alternatives):
+        """ulg_cbic_set_constraints: alternatives = [(v, required, forbidden), ...] with
+        required / forbidden as parent masks (bit i = variable i).  A variable with at
+        least one alternative takes only parent sets P with required <= P and
+        P & forbidden == 0 for one of them; every other set scores -float(n).  Holds
+        until the next load(); an empty list clears."""
+        alts = list(alternatives)
+        v = np.ascontiguousarray([a[0] for a in alts], dtype=np.int32)
+        r = np.ascontiguousarray([a[1] for a in alts], dtype=np.uint64)
+        f = np.ascontiguousarray([a[2] for a in alts], dtype=np.uint64)
+        self._check(lib().ulg_cbic_set_constraints(self._h, len(alts), _ptr(v), _ptr(r), _ptr(f)),
+                    "ulg_cbic_set_constraints")
+
+    def clear_constraints(self):
+        self._check(lib().ulg_cbic_set_constraints(self._h, 0, None, None, None), "ulg_cbic_set_constraints")
 
     def quantize(self, scores: np.ndarray) -> np.ndarray:
         s = np.ascontiguousarray(scores, dtype=np.float32)

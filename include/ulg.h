@@ -24,6 +24,19 @@
  *                        regression (BIC_OLS.cpp:279-283).
  *   ulg_cbic_fetch       hands the stored FloatMap contents back (what
  *                        scoringThread prints, score/score_main.cpp:173-203).
+ *   ulg_disc_load        replaces the RecordFile / BayesianNetwork / ADTree
+ *                        state score_main builds for the discrete scores
+ *                        (score/score_main.cpp:283-292): the value codes of
+ *                        every record and each variable's cardinality.
+ *   ulg_disc_score       replaces ScoreCalculator::calculateScores
+ *                        (score_calculator.cpp:33-135) driving
+ *                        BICScoringFunction::calculateScore
+ *                        (scoring_function/bic_scoring_function.cpp:20-76) and
+ *                        LogLikelihoodCalculator::calculate
+ *                        (log_likelihood_calculator.cpp:17-77): the AD-tree's
+ *                        count queries (ad_tree/ad_tree.cpp:95-164) become one
+ *                        contingency-count pass over the records per set.
+ *   ulg_disc_score_sets  the per-call BICScoringFunction::calculateScore value.
  *   ulg_bestscore_*      replaces bestscorecalculators::BestScoreCalculator
  *                        (score_cache/best_score_calculator.h:16-26) with the
  *                        list calculator's semantics
@@ -144,14 +157,15 @@ int ulg_cbic_score_vars(ulg_ctx *ctx, const int *vars, int nv,
 /* scoring::Constraints (scoring_function/constraints.h:36-139) for the loaded data:
  * alternative i says variable vars[i] may take a parent set P with required[i] ⊆ P and
  * P ∩ forbidden[i] = ∅; a variable with at least one alternative must satisfy one of them.
- * count = 0 clears.  Valid after ulg_cbic_load, cleared by the next ulg_cbic_load;
- * applies to ulg_cbic_score*, ulg_cbic_score_sets and everything that reads their lists.
+ * count = 0 clears.  Valid after ulg_cbic_load or ulg_disc_load, cleared by the next load
+ * of either kind; applies to ulg_cbic_score*, ulg_cbic_score_sets, ulg_disc_score* and
+ * everything that reads their lists (for the discrete scores see ulg_disc_score).
  * A violating set scores variableCount (BIC_OLS.cpp:279-283), so it is stored
  * at -float(n) -- the empty set too, when every alternative of its variable
  * requires a parent -- and the dominance walks of larger sets see it as a
  * present key.  The reference's uninitialised Constraints::empty
  * (constraints.h:59) is taken as 0.  Masks with a bit >= n, a variable out
- * of range or a call before ulg_cbic_load return ULG_ERR_ARG; more than
+ * of range or a call before any load return ULG_ERR_ARG; more than
  * ULG_MAX_CONSTRAINT_ALTERNATIVES alternatives for one variable return
  * ULG_ERR_UNSUPPORTED.  ulg_get_info("constraints") is the number held. */
 int ulg_cbic_set_constraints(ulg_ctx *ctx, int count, const int *vars,
@@ -169,6 +183,46 @@ int ulg_cbic_set_constraints(ulg_ctx *ctx, int count, const int *vars,
  * applies it layer by layer.  At most 31 parents per set. */
 int ulg_cbic_score_sets(ulg_ctx *ctx, int64_t count, const int *vars,
                         const uint64_t *parents, float *neg_scores);
+
+/* ---- discrete BIC scoring (bic_scoring_function.cpp, log_likelihood_calculator.cpp) ---- */
+#define ULG_SCORE_BIC 1
+/* codes_colmajor: N x n value codes, column-major (column j = variable j);
+ * arity[j] = cardinality of variable j.  n <= 63, 1 <= arity <= 255,
+ * 2 <= N < 2^31.  Every code must be below its column's arity; the upload
+ * pass checks that on the device and the call returns ULG_ERR_ARG otherwise.
+ * A context holds continuous or discrete data, whichever was loaded last:
+ * ulg_cbic_score*, ulg_cbic_score_sets, ulg_cbic_gram and ulg_mmpc after
+ * ulg_disc_load return ULG_ERR_STATE, and ulg_disc_* after ulg_cbic_load
+ * likewise.  Either load clears ulg_cbic_set_constraints. */
+int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n, const int *arity);
+/* ulg_cbic_score's arguments and counts for a discrete score (kind =
+ * ULG_SCORE_BIC; anything else is ULG_ERR_ARG).  max_parents is taken as
+ * given (< 1 or > n - 1 means n - 1): the BIC limit log(2N / log N) is the
+ * command line's job (score_main.cpp:300-304).  The value of (v, P) is
+ *   sum_cells n_jk ln n_jk - sum_j n_j ln n_j - (r_v - 1) prod_{p in P} r_p ln(N) / 2
+ * from the exact integer counts in FP64, rounded to float once; each
+ * n ln n term is accumulated as a fixed-point integer, so the value does not
+ * depend on scheduling or on the kernel path that counted.  The empty set is
+ * stored iff its value is < 1, every other set iff its value is < 0
+ * (score_calculator.cpp:62,116); there is no dominance test.  A variable of
+ * arity 1 scores 0 for every set.  A set that violates
+ * ulg_cbic_set_constraints scores 1 and is never stored
+ * (bic_scoring_function.cpp:34-37).  The lists replace the context's
+ * (ulg_cbic_fetch, ulg_pss_format, ulg_search_from_scores read them);
+ * time_limit_ms is checked after each complete layer.  q r_v >= 2^63 cells
+ * (q = prod r_p) returns ULG_ERR_UNSUPPORTED, as do sets of more than
+ * ULG_MAX_PARENTS_GPU parents.  A refused call leaves the previous lists. */
+int ulg_disc_score(ulg_ctx *ctx, int kind, const int *vars, int nv, const uint64_t *candidates,
+                   int max_parents, int64_t *total_stored, int64_t *total_scored);
+/* calculateScore(vars[i], parents[i]) for arbitrary pairs: the value above
+ * without the store rule (a violating set gives 1). */
+int ulg_disc_score_sets(ulg_ctx *ctx, int kind, int64_t count, const int *vars,
+                        const uint64_t *parents, float *scores);
+/* diagnostics: the dense contingency table of one (variable, parent set).
+ * Cell index = sum_p code_p base_p + code_v q, parents in ascending variable
+ * order, the first with base 1, q = prod r_p.  *ncells = q r_v;
+ * ULG_ERR_ARG if cap is smaller. */
+int ulg_disc_counts(ulg_ctx *ctx, int var, uint64_t parents, int32_t *counts, int64_t cap, int64_t *ncells);
 
 /* The .pss "%f" + atof round trip the A* input goes through
  * (score_main.cpp:191, score_cache.cpp:151), computed exactly on the
@@ -356,6 +410,11 @@ int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_co
  * and 241 only, and not under time_limit_ms, whose budget is checked after every
  * layer; lists identical either way; C3 layers 1-3: 40 us against 54 us
  * for six launches, layer 4 in it 340 us: too many sets for one workgroup).
+ * "disc_dense_cells" (1..32768, default 16384): a discrete set whose
+ * contingency table has at most this many cells is counted in an int32 LDS
+ * histogram; larger tables are counted in a hash table of their non-empty
+ * cells (in LDS when 4N slots fit, else in a per-workgroup HBM slab).  Both
+ * give bit-identical values.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -400,7 +459,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * score_calculator.h:45), "exact_cycles" / "exact_instructions" /
  * "exact_cache_misses" (the last exact-order A*'s user-space host counters on
  * the calling thread, perf_event_open; -1 where the host does not grant
- * them), "score_error_word" (the last scoring call's device error word: 0,
+ * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
+ * counted on each path), "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero
  * word also made that call return a nonzero status). */

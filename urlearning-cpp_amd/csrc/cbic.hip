@@ -3470,7 +3470,8 @@ int ulg_cbic_fetch(ulg_ctx *c, uint64_t *sets, float *scores, int64_t *offsets, 
 int ulg_cbic_set_constraints(ulg_ctx *c, int count, const int *vars, const uint64_t *required,
                              const uint64_t *forbidden) {
     if (!c) return ULG_ERR_ARG;
-    if (!c->loaded) return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: call ulg_cbic_load first");
+    if (!c->loaded && !c->disc_loaded)
+        return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: call ulg_cbic_load or ulg_disc_load first");
     if (count < 0 || (count > 0 && (!vars || !required || !forbidden)))
         return set_err(c, ULG_ERR_ARG, "ulg_cbic_set_constraints: bad arguments");
     const int n = c->n;

@@ -1,0 +1,735 @@
+// disc.hip -- discrete BIC scoring (ulg_disc_*): contingency counts of the
+// records per (variable, parent set), then the n ln n reduction.
+//
+// Replaces, for `score -f BIC`, the reference's RecordFile / ADTree state
+// (score/score_main.cpp:283-292), the AD-tree count queries
+// (ad_tree/ad_tree.cpp:95-164), LogLikelihoodCalculator::calculate
+// (scoring_function/log_likelihood_calculator.cpp:17-77) and
+// BICScoringFunction::calculateScore (bic_scoring_function.cpp:20-76).
+//
+// One workgroup per (variable, parent set) work item, a grid-stride loop over
+// the layer's items; an item is unranked from its colex rank within its
+// variable's layer.  Two counting paths:
+//   dense   q r_v <= disc_dense_cells: an int32 LDS histogram, one LDS atomic
+//           per record, then one thread per parent configuration;
+//   sparse  above: a hash table of the non-empty cells and parent
+//           configurations (at most 2N keys in >= 4N slots), in LDS when it
+//           fits, else in the workgroup's HBM slab.
+// Either way the value is the sum of the terms +fix(n_jk ln n_jk) and
+// -fix(n_j ln n_j) over the non-empty cells and parent configurations, where
+// fix() rounds one FP64 term to a 2^-shift fixed-point integer: the terms are
+// a function of the counts alone and integer adds commute, so the sum -- and
+// the float it is rounded to once -- does not depend on the path, the hash
+// placement or the scheduling.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#include "ulg_internal.h"
+
+using namespace ulg;
+
+namespace {
+
+constexpr int kDiscBlock = 256;
+constexpr unsigned long long kEmptyKey = ~0ull;
+constexpr unsigned long long kCfgTag = 1ull << 63;  // hash keys of parent configurations
+constexpr int kHashLdsSlots = 8192;                 // 8192 x 12 B = 96 KB of the 160 KB LDS
+constexpr int kScanPerThread = 8;
+constexpr int kScanPerBlock = kDiscBlock * kScanPerThread;
+constexpr unsigned long long kErrCode = 1ull;       // a value code >= its column's arity
+
+struct DiscData {
+    const uint8_t *codes;  // [n][N]
+    int64_t N;
+    int n;
+    int shift;             // fixed point: 2^-shift
+    double half_ln_N;
+    uint8_t arity[64];
+};
+
+struct DiscWork {
+    unsigned long long *slab;  // sparse path in HBM: hslots keys, then hslots uint32 counts, per workgroup
+    uint64_t hslots;           // power of two >= 4N
+    int hash_lds;              // the hash table fits LDS
+    int64_t dense_cells;
+    unsigned long long *word;  // [error word, dense sets, sparse sets, stored]
+};
+
+// One work item, decoded by thread 0.
+struct Item {
+    int v, k, rv, skip;        // skip: 1 = value known without counting
+    float value;
+    uint64_t q, cells, mask;
+    int col[ULG_MAX_PARENTS_GPU];
+    uint64_t base[ULG_MAX_PARENTS_GPU];
+};
+
+__device__ __forceinline__ bool disc_violates(const uint64_t *ct, int n, int v, uint64_t set) {
+    const uint64_t b = ct[v], e = ct[v + 1];
+    if (b == e) return false;
+    const uint64_t *p = ct + n + 1 + 2 * b;
+    for (uint64_t i = 0; i < e - b; ++i)
+        if ((p[2 * i] & ~set) == 0 && (p[2 * i + 1] & set) == 0) return false;
+    return true;
+}
+
+// fix(n ln n): zero cells contribute nothing (ilogi[0] = 0), and 1 ln 1 = 0
+__device__ __forceinline__ long long fix_nlogn(unsigned int n, int shift) {
+    if (n <= 1u) return 0;
+    return __double2ll_rn(ldexp((double)n * log((double)n), shift));
+}
+
+// Thread 0: the item's parents (ascending variable order), bases and table
+// size; R5 (arity 1) and R6 (constraints) settle the value without counting.
+// The host has checked that q r_v < 2^63 for every set of the call.
+__device__ void decode_item(const DiscData &D, int v, uint64_t pmask, const uint64_t *cons, Item &it) {
+    it.v = v;
+    it.mask = pmask;
+    it.rv = D.arity[v];
+    int k = 0;
+    uint64_t q = 1;
+    for (uint64_t m = pmask; m; m &= m - 1) {
+        const int p = __builtin_ctzll(m);
+        it.col[k] = p;
+        it.base[k] = q;
+        q *= (uint64_t)D.arity[p];
+        ++k;
+    }
+    it.k = k;
+    it.q = q;
+    it.cells = q * (uint64_t)it.rv;
+    it.skip = 0;
+    if (cons && disc_violates(cons, D.n, v, pmask)) {
+        it.skip = 1;
+        it.value = 1.0f;  // bic_scoring_function.cpp:34-37
+    } else if (it.rv == 1) {
+        it.skip = 1;
+        it.value = 0.0f;  // penalty 0, log-likelihood 0
+    }
+}
+
+__device__ __forceinline__ uint64_t cell_of(const DiscData &D, const Item &it, int64_t r, uint64_t &cfg) {
+    uint64_t j = 0;
+    for (int a = 0; a < it.k; ++a) j += (uint64_t)D.codes[(int64_t)it.col[a] * D.N + r] * it.base[a];
+    cfg = j;
+    return j + (uint64_t)D.codes[(int64_t)it.v * D.N + r] * it.q;
+}
+
+// Counts the item's records in the hash table (keys / cnt, hslots entries) and
+// adds the fixed-point terms to *acc; counts_out (optional) receives the
+// non-empty cells of the dense table.
+template <class KP, class CP>
+__device__ __forceinline__ void sparse_count(const DiscData &D, const Item &it, KP keys, CP cnt, uint64_t hslots,
+                                             unsigned long long *acc, int32_t *counts_out) {
+    const int tid = threadIdx.x;
+    for (uint64_t h = tid; h < hslots; h += kDiscBlock) {
+        keys[h] = kEmptyKey;
+        cnt[h] = 0u;
+    }
+    __syncthreads();
+    const uint64_t hm = hslots - 1;
+    for (int64_t r = tid; r < D.N; r += kDiscBlock) {
+        uint64_t cfg;
+        const uint64_t cell = cell_of(D, it, r, cfg);
+        const unsigned long long two[2] = {cell, cfg | kCfgTag};
+        for (int t = 0; t < 2; ++t) {
+            const unsigned long long key = two[t];
+            uint64_t h = (key * 0x9E3779B97F4A7C15ull >> 20) & hm;
+            // at most 2N distinct keys in >= 4N slots: a free slot is always reached
+            for (;;) {
+                const unsigned long long prev = atomicCAS(&keys[h], kEmptyKey, key);
+                if (prev == kEmptyKey || prev == key) break;
+                h = (h + 1) & hm;
+            }
+            atomicAdd(&cnt[h], 1u);
+        }
+    }
+    __syncthreads();
+    long long a = 0;
+    for (uint64_t h = tid; h < hslots; h += kDiscBlock) {
+        const unsigned long long key = keys[h];
+        if (key == kEmptyKey) continue;
+        const unsigned int c = cnt[h];
+        const long long f = fix_nlogn(c, D.shift);
+        if (key & kCfgTag) {
+            a -= f;
+        } else {
+            a += f;
+            if (counts_out) counts_out[key] = (int32_t)c;
+        }
+    }
+    if (a) atomicAdd(acc, (unsigned long long)a);
+    __syncthreads();
+}
+
+// The whole workgroup: the value of the decoded item `it` (in LDS).  smem:
+// the dynamic LDS behind the item (histogram or hash table).  counts_out
+// (optional, zeroed by the caller, it.cells entries): the dense table.
+__device__ float item_value(const DiscData &D, const DiscWork &W, const Item &it, unsigned long long *acc,
+                            unsigned char *smem, int32_t *counts_out, bool count_path) {
+    const int tid = threadIdx.x;
+    if (it.skip && !counts_out) return it.value;
+    if (tid == 0) *acc = 0ull;
+    __syncthreads();
+    if (it.cells <= (uint64_t)W.dense_cells) {
+        int *hist = reinterpret_cast<int *>(smem);
+        const int cells = (int)it.cells;
+        for (int i = tid; i < cells; i += kDiscBlock) hist[i] = 0;
+        __syncthreads();
+        for (int64_t r = tid; r < D.N; r += kDiscBlock) {
+            uint64_t cfg;
+            const uint64_t cell = cell_of(D, it, r, cfg);
+            atomicAdd(&hist[(int)cell], 1);  // cell < cells: every code is below its arity (checked at load)
+        }
+        __syncthreads();
+        long long a = 0;
+        const int q = (int)it.q;
+        for (int j = tid; j < q; j += kDiscBlock) {
+            unsigned int nj = 0;
+            for (int kk = 0; kk < it.rv; ++kk) {
+                const unsigned int c = (unsigned int)hist[j + kk * q];
+                nj += c;
+                a += fix_nlogn(c, D.shift);
+            }
+            a -= fix_nlogn(nj, D.shift);
+        }
+        if (a) atomicAdd(acc, (unsigned long long)a);
+        if (counts_out)
+            for (int i = tid; i < cells; i += kDiscBlock) counts_out[i] = hist[i];
+        if (count_path && tid == 0) atomicAdd(&W.word[1], 1ull);
+        __syncthreads();
+    } else {
+        if (W.hash_lds) {
+            unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
+            unsigned int *cnt = reinterpret_cast<unsigned int *>(keys + W.hslots);
+            sparse_count(D, it, keys, cnt, W.hslots, acc, counts_out);
+        } else {
+            unsigned long long *keys = W.slab + (uint64_t)blockIdx.x * (W.hslots + W.hslots / 2);
+            unsigned int *cnt = reinterpret_cast<unsigned int *>(keys + W.hslots);
+            sparse_count(D, it, keys, cnt, W.hslots, acc, counts_out);
+        }
+        if (count_path && tid == 0) atomicAdd(&W.word[2], 1ull);
+    }
+    if (it.skip) return it.value;
+    // R4: the log-likelihood from the exact counts, the penalty, one rounding
+    const double ll = ldexp((double)(long long)*acc, -D.shift);
+    const double pen = (double)(it.rv - 1) * (double)it.q * D.half_ln_N;
+    return (float)(ll - pen);
+}
+
+// ---- upload check ------------------------------------------------------------
+__global__ void __launch_bounds__(kDiscBlock) disc_check_kernel(DiscData D, unsigned long long *word) {
+    const int64_t total = D.N * (int64_t)D.n;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * kDiscBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kDiscBlock)
+        bad |= D.codes[i] >= D.arity[(int)(i / D.N)];
+    if (bad) atomicOr(word, kErrCode);
+}
+
+// ---- one layer ---------------------------------------------------------------
+struct LayerArgs {
+    const uint8_t *cand;     // [nv][64] compact index -> variable
+    const int *vm;           // [nv][2]: variable, candidate count
+    const uint64_t *toff;    // [nv * S + 1] slot prefixes
+    const uint64_t *work;    // [nv + 1] this layer's item prefixes
+    const uint64_t *binom64; // [64][64]
+    const uint64_t *cons;    // by variable, or null
+    float *table;            // per slot: the stored value, or absent
+    uint64_t *sets;          // per slot: the set's variable mask
+    int nv, S, L;
+};
+
+__global__ void __launch_bounds__(kDiscBlock) disc_layer_kernel(DiscData D, DiscWork W, LayerArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ Item it;
+    __shared__ unsigned long long acc;
+    __shared__ uint64_t slot;
+    const uint64_t total = A.work[A.nv];
+    for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
+        __syncthreads();  // the previous item's LDS is done with
+        if (threadIdx.x == 0) {
+            int i = 0;
+            while (i + 1 < A.nv && A.work[i + 1] <= w) ++i;
+            uint64_t r = w - A.work[i];
+            // colex unrank over the variable's compact candidate indices
+            const int m = A.vm[2 * i + 1];
+            uint64_t pmask = 0;
+            int c = m - 1;
+            for (int e = A.L; e >= 1; --e) {
+                while (c > e - 1 && A.binom64[c * 64 + e] > r) --c;
+                r -= A.binom64[c * 64 + e];
+                pmask |= 1ull << A.cand[i * 64 + c];
+                --c;
+            }
+            slot = A.toff[(uint64_t)i * A.S + A.L] + (w - A.work[i]);
+            decode_item(D, A.vm[2 * i], pmask, A.cons, it);
+        }
+        __syncthreads();
+        const float val = item_value(D, W, it, &acc, smem, nullptr, true);
+        if (threadIdx.x == 0) {
+            // R3: the empty set is stored iff < 1, every other set iff < 0
+            const bool keep = A.L == 0 ? val < 1.0f : val < 0.0f;
+            A.table[slot] = keep ? val : __uint_as_float(kAbsentBits);
+            A.sets[slot] = it.mask;
+        }
+    }
+}
+
+// ---- arbitrary pairs / one table ---------------------------------------------
+__global__ void __launch_bounds__(kDiscBlock)
+disc_sets_kernel(DiscData D, DiscWork W, const uint64_t *pairs, int64_t count, const uint64_t *cons, float *out,
+                 int32_t *counts_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ Item it;
+    __shared__ unsigned long long acc;
+    for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
+        __syncthreads();
+        if (threadIdx.x == 0) decode_item(D, (int)pairs[2 * w], pairs[2 * w + 1], cons, it);
+        __syncthreads();
+        const float val = item_value(D, W, it, &acc, smem, counts_out, false);
+        if (threadIdx.x == 0 && out) out[w] = val;
+    }
+}
+
+// ---- compaction in slot (= rank) order -----------------------------------------
+__global__ void __launch_bounds__(kDiscBlock)
+disc_count_kernel(const float *table, uint64_t total, unsigned long long *blk) {
+    __shared__ unsigned int s;
+    if (threadIdx.x == 0) s = 0;
+    __syncthreads();
+    const uint64_t b0 = (uint64_t)blockIdx.x * kScanPerBlock + (uint64_t)threadIdx.x * kScanPerThread;
+    unsigned int cnt = 0;
+    for (int j = 0; j < kScanPerThread; ++j)
+        if (b0 + j < total && __float_as_uint(table[b0 + j]) != kAbsentBits) ++cnt;
+    if (cnt) atomicAdd(&s, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s;
+}
+
+// one workgroup: exclusive scan of the block counts, total into blk[nb] and word[3]
+__global__ void __launch_bounds__(kDiscBlock)
+disc_scan_kernel(unsigned long long *blk, int64_t nb, unsigned long long *word) {
+    __shared__ unsigned long long part[kDiscBlock];
+    const int tid = threadIdx.x;
+    const int64_t per = (nb + kDiscBlock - 1) / kDiscBlock;
+    const int64_t b = std::min<int64_t>(nb, (int64_t)tid * per), e = std::min<int64_t>(nb, b + per);
+    unsigned long long s = 0;
+    for (int64_t i = b; i < e; ++i) s += blk[i];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long run = 0;
+        for (int i = 0; i < kDiscBlock; ++i) {
+            const unsigned long long t = part[i];
+            part[i] = run;
+            run += t;
+        }
+        blk[nb] = run;
+        word[3] = run;
+    }
+    __syncthreads();
+    unsigned long long run = part[tid];
+    for (int64_t i = b; i < e; ++i) {
+        const unsigned long long t = blk[i];
+        blk[i] = run;
+        run += t;
+    }
+}
+
+__global__ void __launch_bounds__(kDiscBlock)
+disc_write_kernel(const float *table, const uint64_t *sets, uint64_t total, const unsigned long long *blk,
+                  uint64_t *out_sets, float *out_scores) {
+    __shared__ unsigned int pre[kDiscBlock];
+    const int tid = threadIdx.x;
+    const uint64_t b0 = (uint64_t)blockIdx.x * kScanPerBlock + (uint64_t)tid * kScanPerThread;
+    unsigned int cnt = 0;
+    for (int j = 0; j < kScanPerThread; ++j)
+        if (b0 + j < total && __float_as_uint(table[b0 + j]) != kAbsentBits) ++cnt;
+    pre[tid] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned int run = 0;
+        for (int i = 0; i < kDiscBlock; ++i) {
+            const unsigned int t = pre[i];
+            pre[i] = run;
+            run += t;
+        }
+    }
+    __syncthreads();
+    unsigned long long o = blk[blockIdx.x] + pre[tid];
+    for (int j = 0; j < kScanPerThread; ++j)
+        if (b0 + j < total && __float_as_uint(table[b0 + j]) != kAbsentBits) {
+            out_sets[o] = sets[b0 + j];
+            out_scores[o] = table[b0 + j];
+            ++o;
+        }
+}
+
+// offsets[i] = stored sets below slot toff[i * S] (i = nv: all of them)
+__global__ void disc_offsets_kernel(const float *table, const uint64_t *toff, int nv, int S,
+                                    const unsigned long long *blk, int64_t *offsets) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nv) return;
+    const uint64_t s = toff[(uint64_t)i * S];
+    const uint64_t b = s / kScanPerBlock;
+    unsigned long long o = blk[b];  // slot == total: b may be nb, the total
+    for (uint64_t j = b * kScanPerBlock; j < s; ++j)
+        if (__float_as_uint(table[j]) != kAbsentBits) ++o;
+    offsets[i] = (int64_t)o;
+}
+
+// ---- host ----------------------------------------------------------------------
+bool disc_ready(const ulg_ctx *c) { return c->disc_loaded && !c->loaded; }
+
+DiscData disc_data(const ulg_ctx *c) {
+    DiscData D{};
+    D.codes = c->d_codes.p;
+    D.N = c->N;
+    D.n = c->n;
+    // the largest power-of-two scale at which N ln N stays below 2^62, at most 2^32
+    int ex = 0;
+    (void)std::frexp((double)c->N * std::log((double)c->N), &ex);  // N ln N < 2^ex
+    D.shift = std::min(32, 62 - ex);
+    D.half_ln_N = std::log((double)c->N) / 2.0;
+    for (int j = 0; j < c->n; ++j) D.arity[j] = (uint8_t)c->disc_arity[j];
+    return D;
+}
+
+// q r_v of (v, parents), or 2^63 where it does not fit
+uint64_t table_cells(const ulg_ctx *c, int v, uint64_t parents) {
+    unsigned __int128 cells = (unsigned)c->disc_arity[v];
+    for (uint64_t m = parents; m; m &= m - 1) {
+        cells *= (unsigned)c->disc_arity[__builtin_ctzll(m)];
+        if (cells >> 63) return 1ull << 63;
+    }
+    return (uint64_t)cells;
+}
+
+// The counting resources of a launch whose largest table has max_cells cells:
+// the dynamic LDS, and the HBM slabs when the hash table does not fit LDS
+// (which bounds the grid).
+int disc_work(ulg_ctx *c, uint64_t max_cells, uint64_t items, DiscWork &W, size_t &lds, unsigned &grid) {
+    W = DiscWork{};
+    W.dense_cells = c->disc_dense_cells;
+    W.word = c->d_disc_word.p;
+    uint64_t hs = 64;
+    while (hs < 4ull * (uint64_t)c->N) hs <<= 1;
+    W.hslots = hs;
+    W.hash_lds = hs <= (uint64_t)kHashLdsSlots;
+    const bool sparse = max_cells > (uint64_t)W.dense_cells;
+    lds = (size_t)std::min<uint64_t>(max_cells, (uint64_t)W.dense_cells) * 4;
+    if (sparse && W.hash_lds) lds = std::max(lds, (size_t)hs * 12);
+    lds = std::max<size_t>(lds, 16);
+    uint64_t g = std::min<uint64_t>(std::max<uint64_t>(items, 1), 2048);
+    if (sparse && !W.hash_lds) {
+        const uint64_t per = hs + hs / 2;  // words per workgroup
+        g = std::min<uint64_t>(g, std::max<uint64_t>(1, (1ull << 28) / per));  // at most 2 GiB of slabs
+        if (int rc = ensure(c, c->d_disc_slab, (size_t)(g * per))) return rc;
+        W.slab = c->d_disc_slab.p;
+    }
+    grid = (unsigned)g;
+    return ULG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int *arity) {
+    if (!c) return ULG_ERR_ARG;
+    if (!codes || !arity || N < 2 || N >= (1ll << 31) || n < 1 || n > kMaxVars)
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_load: bad arguments");
+    for (int j = 0; j < n; ++j)
+        if (arity[j] < 1 || arity[j] > 255) return set_err(c, ULG_ERR_ARG, "ulg_disc_load: arity must be 1..255");
+    if (c->async_pending) {
+        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
+        if (rc0) return rc0;
+    }
+    ULG_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->d_codes, (size_t)(N * n))) || (rc = ensure(c, c->d_disc_word, 4))) return rc;
+    c->disc_loaded = false;  // the previous codes are gone
+    ULG_HIP(c, hipMemcpyAsync(c->d_codes.p, codes, (size_t)(N * n), hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    DiscData D{};
+    D.codes = c->d_codes.p;
+    D.N = N;
+    D.n = n;
+    for (int j = 0; j < n; ++j) D.arity[j] = (uint8_t)arity[j];
+    const int64_t total = N * n;
+    prof_begin(c, "disc_check");
+    disc_check_kernel<<<(unsigned)std::min<int64_t>((total + kDiscBlock - 1) / kDiscBlock, 4096), kDiscBlock, 0,
+                        c->stream>>>(D, c->d_disc_word.p);
+    prof_end(c);
+    ULG_HIP(c, hipGetLastError());
+    unsigned long long word = 0;
+    ULG_HIP(c, hipMemcpyAsync(&word, c->d_disc_word.p, sizeof word, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (word & kErrCode) return set_err(c, ULG_ERR_ARG, "ulg_disc_load: a value code is not below its column's arity");
+    // the context now holds these records: the continuous data, the lists
+    // scored from the previous data and its constraints are gone
+    c->loaded = false;
+    c->scored = false;
+    if (!c->cons_var.empty()) {
+        graph_reset(c);
+        c->cons_var.clear();
+        c->cons_req.clear();
+        c->cons_forb.clear();
+    }
+    c->n = n;
+    c->N = N;
+    c->disc_arity.assign(arity, arity + n);
+    c->disc_loaded = true;
+    return ULG_OK;
+}
+
+int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t *candidates, int max_parents,
+                   int64_t *total_stored, int64_t *total_scored) {
+    if (!c) return ULG_ERR_ARG;
+    if (c->async_pending) {
+        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
+        if (rc0) return rc0;
+    }
+    if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score: call ulg_disc_load first");
+    if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC");
+    if (!vars || !candidates || nv < 1 || nv > c->n) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: bad variable list");
+    const int n = c->n;
+    uint64_t seen = 0;
+    for (int i = 0; i < nv; ++i) {
+        if (vars[i] < 0 || vars[i] >= n || ((seen >> vars[i]) & 1ull))
+            return set_err(c, ULG_ERR_ARG, "ulg_disc_score: variables must be distinct and < n");
+        seen |= 1ull << vars[i];
+    }
+    const uint64_t allmask = (1ull << n) - 1ull;
+    if (max_parents < 1 || max_parents > n - 1) max_parents = n - 1;
+    std::vector<uint8_t> cand((size_t)nv * 64, 0);
+    std::vector<int> vm((size_t)nv * 2, 0), mv(nv);
+    int kmax = 0;
+    uint64_t max_cells = 0;
+    for (int i = 0; i < nv; ++i) {
+        const uint64_t C = candidates[i] & allmask & ~(1ull << vars[i]);
+        int m = 0;
+        std::vector<int> ar;
+        for (int b = 0; b < n; ++b)
+            if ((C >> b) & 1ull) {
+                cand[(size_t)i * 64 + m++] = (uint8_t)b;
+                ar.push_back(c->disc_arity[b]);
+            }
+        mv[i] = m;
+        vm[2 * i] = vars[i];
+        vm[2 * i + 1] = m;
+        const int k = std::min(m, max_parents);
+        kmax = std::max(kmax, k);
+        // the variable's largest table: its k candidates of largest arity
+        std::sort(ar.begin(), ar.end(), std::greater<int>());
+        unsigned __int128 cells = (unsigned)c->disc_arity[vars[i]];
+        for (int j = 0; j < k && !(cells >> 63); ++j) cells *= (unsigned)ar[j];
+        if ((cells >> 63) && c->disc_arity[vars[i]] > 1)
+            return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_disc_score: a contingency table of 2^63 cells or more");
+        if (c->disc_arity[vars[i]] > 1) max_cells = std::max(max_cells, (uint64_t)cells);
+    }
+    if (kmax > kWideMax)
+        return set_err(c, ULG_ERR_UNSUPPORTED,
+                       "ulg_disc_score: parent sets larger than ULG_MAX_PARENTS_GPU (31) are not supported");
+    const int S = kmax + 1;
+    // [toff: nv * S + 1][work: S x (nv + 1)]
+    std::vector<uint64_t> meta((size_t)nv * S + 1 + (size_t)S * (nv + 1), 0);
+    uint64_t *toff = meta.data(), *work = meta.data() + (size_t)nv * S + 1;
+    uint64_t acc = 0;
+    for (int i = 0; i < nv; ++i)
+        for (int L = 0; L < S; ++L) {
+            toff[(size_t)i * S + L] = acc;
+            acc += L <= std::min(mv[i], max_parents) ? binom64(mv[i], L) : 0;
+        }
+    toff[(size_t)nv * S] = acc;
+    const uint64_t total_slots = acc;
+    for (int L = 0; L < S; ++L) {
+        uint64_t s = 0;
+        for (int i = 0; i < nv; ++i) {
+            work[(size_t)L * (nv + 1) + i] = s;
+            s += toff[(size_t)i * S + L + 1] - toff[(size_t)i * S + L];
+        }
+        work[(size_t)L * (nv + 1) + nv] = s;
+    }
+    ULG_HIP(c, hipSetDevice(c->device));
+    const int64_t nb = (int64_t)((total_slots + kScanPerBlock - 1) / kScanPerBlock);
+    int rc;
+    // the slot table and the block counts live in buffers of this scorer; the
+    // context's lists are replaced only once every layer has been launched
+    if ((rc = ensure(c, c->d_disc_meta, meta.size())) || (rc = ensure(c, c->d_disc_cand, cand.size())) ||
+        (rc = ensure(c, c->d_disc_vm, vm.size())) || (rc = ensure(c, c->d_disc_table, total_slots)) ||
+        (rc = ensure(c, c->d_disc_sets, total_slots)) || (rc = ensure(c, c->d_disc_blk, (size_t)nb + 1)) ||
+        (rc = ensure(c, c->d_disc_word, 4)))
+        return rc;
+    DiscWork W;
+    size_t lds = 0;
+    unsigned grid_cap = 1;
+    if ((rc = disc_work(c, max_cells, total_slots, W, lds, grid_cap))) return rc;
+    ULG_HIP(c, hipFuncSetAttribute((const void *)disc_layer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_vm.p, vm.data(), vm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_table.p, 0xFF, total_slots * sizeof(float), c->stream));  // absent
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    // pageable sources: the copies above must be done before `meta` goes away
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+
+    const DiscData D = disc_data(c);
+    LayerArgs A{};
+    A.cand = c->d_disc_cand.p;
+    A.vm = c->d_disc_vm.p;
+    A.toff = c->d_disc_meta.p;
+    A.binom64 = c->d_binom64.p;
+    A.cons = c->cons_var.empty() ? nullptr : c->d_cons_var.p;
+    A.table = c->d_disc_table.p;
+    A.sets = c->d_disc_sets.p;
+    A.nv = nv;
+    A.S = S;
+    // -r (score_calculator.cpp:33-52,78): checked after every complete layer
+    const auto t_call = std::chrono::steady_clock::now();
+    c->out_of_time = 0;
+    int done_L = kmax;
+    for (int L = 0; L <= kmax; ++L) {
+        const uint64_t items = work[(size_t)L * (nv + 1) + nv];
+        if (items) {
+            A.L = L;
+            A.work = c->d_disc_meta.p + (size_t)nv * S + 1 + (size_t)L * (nv + 1);
+            prof_begin(c, "disc_layer");
+            disc_layer_kernel<<<(unsigned)std::min<uint64_t>(items, grid_cap), kDiscBlock, lds, c->stream>>>(D, W, A);
+            prof_end(c);
+            ULG_HIP(c, hipGetLastError());
+        }
+        if (c->time_limit_ms > 0 && L < kmax) {
+            ULG_HIP(c, hipStreamSynchronize(c->stream));
+            const double ms =
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+            if (ms > (double)c->time_limit_ms) {
+                done_L = L;
+                c->out_of_time = 1;
+                break;
+            }
+        }
+    }
+    int64_t scored = 0;
+    for (int i = 0; i < nv; ++i)
+        for (int L = 0; L <= done_L; ++L) scored += (int64_t)(toff[(size_t)i * S + L + 1] - toff[(size_t)i * S + L]);
+    c->completed_layer = done_L;
+    if ((rc = ensure(c, c->out_sets, total_slots)) || (rc = ensure(c, c->out_scores, total_slots)) ||
+        (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
+        return rc;
+    prof_begin(c, "disc_compact");
+    disc_count_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, total_slots, c->d_disc_blk.p);
+    disc_scan_kernel<<<1, kDiscBlock, 0, c->stream>>>(c->d_disc_blk.p, nb, c->d_disc_word.p);
+    disc_write_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_sets.p, total_slots,
+                                                                 c->d_disc_blk.p, c->out_sets.p, c->out_scores.p);
+    disc_offsets_kernel<<<(nv + 1 + 63) / 64, 64, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_meta.p, nv, S,
+                                                                 c->d_disc_blk.p, c->out_offsets.p);
+    prof_end(c);
+    ULG_HIP(c, hipGetLastError());
+    unsigned long long word[4] = {0, 0, 0, 0};
+    ULG_HIP(c, hipMemcpyAsync(word, c->d_disc_word.p, sizeof word, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    c->last_err_word = 0;
+    c->disc_path_sets[0] = (int64_t)word[1];
+    c->disc_path_sets[1] = (int64_t)word[2];
+    c->nv = nv;
+    c->kmax = kmax;
+    c->vars.assign(vars, vars + nv);
+    c->m = mv;
+    c->tbl_off.assign(toff, toff + (size_t)nv * S + 1);
+    c->total_slots = (int64_t)total_slots;
+    c->total_stored = (int64_t)word[3];
+    c->total_scored = scored;
+    c->scored = true;
+    if (total_stored) *total_stored = c->total_stored;
+    if (total_scored) *total_scored = scored;
+    return ULG_OK;
+}
+
+// the pairs on the device, the counting resources and one launch of disc_sets_kernel
+static int disc_sets_launch(ulg_ctx *c, const char *what, int64_t count, const int *vars, const uint64_t *parents,
+                            float *out_dev, int32_t *counts_dev) {
+    const int n = c->n;
+    const uint64_t allmask = (1ull << n) - 1ull;
+    std::vector<uint64_t> pairs((size_t)count * 2);
+    uint64_t max_cells = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (vars[i] < 0 || vars[i] >= n) return set_err(c, ULG_ERR_ARG, std::string(what) + ": variable out of range");
+        if (parents[i] & ~allmask) return set_err(c, ULG_ERR_ARG, std::string(what) + ": parent bit >= n");
+        const uint64_t P = parents[i] & ~(1ull << vars[i]);
+        if (__builtin_popcountll(P) > kWideMax)
+            return set_err(c, ULG_ERR_UNSUPPORTED, std::string(what) + ": more than ULG_MAX_PARENTS_GPU (31) parents");
+        const uint64_t cells = table_cells(c, vars[i], P);
+        if (cells >> 63) {
+            if (c->disc_arity[vars[i]] > 1 || counts_dev)
+                return set_err(c, ULG_ERR_UNSUPPORTED, std::string(what) + ": a contingency table of 2^63 cells or more");
+        } else if (c->disc_arity[vars[i]] > 1 || counts_dev) {
+            max_cells = std::max(max_cells, cells);
+        }
+        pairs[2 * i] = (uint64_t)vars[i];
+        pairs[2 * i + 1] = P;
+    }
+    ULG_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->d_sets_in, (size_t)count * 2)) || (rc = ensure(c, c->d_disc_word, 4))) return rc;
+    DiscWork W;
+    size_t lds = 0;
+    unsigned grid = 1;
+    if ((rc = disc_work(c, max_cells, (uint64_t)count, W, lds, grid))) return rc;
+    ULG_HIP(c, hipFuncSetAttribute((const void *)disc_sets_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ULG_HIP(c, hipMemcpyAsync(c->d_sets_in.p, pairs.data(), (size_t)count * 16, hipMemcpyHostToDevice, c->stream));
+    prof_begin(c, "disc_sets");
+    disc_sets_kernel<<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count,
+                                                           c->cons_var.empty() || counts_dev ? nullptr : c->d_cons_var.p,
+                                                           out_dev, counts_dev);
+    prof_end(c);
+    ULG_HIP(c, hipGetLastError());
+    ULG_HIP(c, hipStreamSynchronize(c->stream));  // `pairs` is a pageable source
+    prof_collect(c);
+    return ULG_OK;
+}
+
+int ulg_disc_score_sets(ulg_ctx *c, int kind, int64_t count, const int *vars, const uint64_t *parents,
+                        float *scores) {
+    if (!c || count < 0 || (count > 0 && (!vars || !parents || !scores))) return ULG_ERR_ARG;
+    if (c->async_pending) {
+        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
+        if (rc0) return rc0;
+    }
+    if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score_sets: call ulg_disc_load first");
+    if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC");
+    if (count == 0) return ULG_OK;
+    int rc;
+    if ((rc = ensure(c, c->qbuf_out, (size_t)count))) return rc;
+    if ((rc = disc_sets_launch(c, "ulg_disc_score_sets", count, vars, parents, c->qbuf_out.p, nullptr))) return rc;
+    ULG_HIP(c, hipMemcpy(scores, c->qbuf_out.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return ULG_OK;
+}
+
+int ulg_disc_counts(ulg_ctx *c, int var, uint64_t parents, int32_t *counts, int64_t cap, int64_t *ncells) {
+    if (!c || !counts || !ncells) return ULG_ERR_ARG;
+    if (c->async_pending) {
+        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
+        if (rc0) return rc0;
+    }
+    if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_counts: call ulg_disc_load first");
+    if (var < 0 || var >= c->n || (parents >> c->n)) return set_err(c, ULG_ERR_ARG, "ulg_disc_counts: bad variable or parents");
+    const uint64_t P = parents & ~(1ull << var);
+    const uint64_t cells = table_cells(c, var, P);
+    if (cells >> 63) return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_disc_counts: a contingency table of 2^63 cells or more");
+    *ncells = (int64_t)cells;
+    if (cap < (int64_t)cells) return set_err(c, ULG_ERR_ARG, "ulg_disc_counts: cap is below q * r_v");
+    if (cells > (1ull << 28)) return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_disc_counts: more than 2^28 cells");
+    ULG_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->d_disc_counts, (size_t)cells))) return rc;
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_counts.p, 0, (size_t)cells * 4, c->stream));
+    if ((rc = disc_sets_launch(c, "ulg_disc_counts", 1, &var, &P, nullptr, c->d_disc_counts.p))) return rc;
+    ULG_HIP(c, hipMemcpy(counts, c->d_disc_counts.p, (size_t)cells * 4, hipMemcpyDeviceToHost));
+    return ULG_OK;
+}
+
+}  // extern "C"

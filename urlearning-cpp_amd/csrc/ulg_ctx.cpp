@@ -169,6 +169,9 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->out_sets); release(c->out_scores); release(c->out_offsets);
     release(c->qbuf_in); release(c->qbuf_out);
     release(c->d_cons); release(c->d_cons_var);
+    release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
+    release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
+    release(c->d_disc_table); release(c->d_disc_blk);
     pss_release(c);
     if (c->search) {
         c->search->release_all();
@@ -208,6 +211,11 @@ int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
     if (std::strcmp(name, "time_limit_ms") == 0) {
         if (value < 0) return set_err(c, ULG_ERR_ARG, "time_limit_ms must be >= 0");
         c->time_limit_ms = value;
+        return ULG_OK;
+    }
+    if (std::strcmp(name, "disc_dense_cells") == 0) {
+        if (value < 1 || value > 32768) return set_err(c, ULG_ERR_ARG, "disc_dense_cells must be 1..32768");
+        c->disc_dense_cells = value;
         return ULG_OK;
     }
     if (std::strcmp(name, "table_budget_kb") == 0) {
@@ -314,6 +322,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // (1), a walk-queue segment overflow (2) or a walk entry past the table (4)
     if (std::strcmp(name, "score_error_word") == 0) {
         *value = (int64_t)c->last_err_word;
+        return ULG_OK;
+    }
+    // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table
+    if (std::strcmp(name, "disc_dense_sets") == 0 || std::strcmp(name, "disc_sparse_sets") == 0) {
+        *value = c->disc_path_sets[name[5] == 's' ? 1 : 0];
         return ULG_OK;
     }
     // alternatives held by ulg_cbic_set_constraints

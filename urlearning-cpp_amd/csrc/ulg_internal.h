@@ -129,6 +129,24 @@ struct ulg_ctx {
     ulg::DevBuf<uint64_t> d_cons;                 // the scoring call's table: by call index, compact masks
     int cons_call_words = 0;                      // its words (0: the call runs the unconstrained kernels)
 
+    // ---- discrete data and scorer (disc.hip) ----
+    // The context holds discrete data iff disc_loaded && !loaded: ulg_cbic_load
+    // sets `loaded`, ulg_disc_load clears it.
+    bool disc_loaded = false;
+    std::vector<int> disc_arity;                  // [n]
+    int64_t disc_dense_cells = 16384;             // tables up to this many cells are counted in LDS
+    int64_t disc_path_sets[2] = {0, 0};           // last ulg_disc_score: sets on the dense / sparse path
+    ulg::DevBuf<uint8_t> d_codes;                 // [n][N] value codes, column-major
+    ulg::DevBuf<uint64_t> d_disc_meta;            // slot prefixes [nv * S + 1], then item prefixes [S][nv + 1]
+    ulg::DevBuf<uint8_t> d_disc_cand;             // [nv][64] compact index -> variable
+    ulg::DevBuf<int> d_disc_vm;                   // [nv][2]: variable, candidate count
+    ulg::DevBuf<float> d_disc_table;              // per table slot: the stored value, or absent
+    ulg::DevBuf<unsigned long long> d_disc_blk;   // compaction: stored sets per block, then their prefix
+    ulg::DevBuf<uint64_t> d_disc_sets;            // per table slot: the set's variable mask
+    ulg::DevBuf<unsigned long long> d_disc_slab;  // sparse path: per-workgroup hash tables
+    ulg::DevBuf<unsigned long long> d_disc_word;  // [error word, dense sets, sparse sets, stored]
+    ulg::DevBuf<int32_t> d_disc_counts;           // ulg_disc_counts' table
+
     ulg::DevBuf<float> qbuf_in, qbuf_out;
     ulg::DevBuf<uint64_t> d_sets_in;              // ulg_cbic_score_sets: (variable, parent mask) pairs
 

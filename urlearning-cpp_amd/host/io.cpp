@@ -121,6 +121,62 @@ bool record_stats(const std::string &path, char delim, bool has_header, RecordSt
     return true;
 }
 
+bool load_discrete_csv(const std::string &path, char delim, bool has_header, DiscreteData &out, std::string &err) {
+    std::ifstream in(path);
+    if (!in) {
+        err = "cannot read '" + path + "'";
+        return false;
+    }
+    out = DiscreteData();
+    std::vector<std::string> header;
+    std::vector<std::unordered_map<std::string, int>> code_of;
+    std::vector<std::vector<uint8_t>> cols;
+    const std::string d(1, delim);
+    std::string line;
+    size_t ncols = 0;
+    int64_t lineno = 0;
+    bool first = true;
+    while (std::getline(in, line)) {
+        ++lineno;
+        const std::vector<std::string> tok = split_compress(trim(line), d);
+        if (first && has_header) {
+            header = tok;
+            first = false;
+            continue;
+        }
+        if (ncols == 0) ncols = tok.size();  // as record_stats: the first record's token count
+        first = false;
+        if (code_of.empty()) {
+            code_of.resize(ncols);
+            cols.resize(ncols);
+        }
+        if (tok.size() < ncols) {
+            err = "line " + std::to_string(lineno) + " of '" + path + "' has " + std::to_string(tok.size()) +
+                  " values, fewer than the " + std::to_string(ncols) + " columns";
+            return false;
+        }
+        for (size_t c = 0; c < ncols; ++c) {
+            auto it = code_of[c].find(tok[c]);
+            if (it == code_of[c].end()) {
+                if (code_of[c].size() >= 255) {
+                    err = "line " + std::to_string(lineno) + " of '" + path + "': column " + std::to_string(c) +
+                          " has more than 255 values";
+                    return false;
+                }
+                it = code_of[c].emplace(tok[c], (int)code_of[c].size()).first;
+            }
+            cols[c].push_back((uint8_t)it->second);
+        }
+        ++out.num_records;
+    }
+    for (size_t c = 0; c < ncols; ++c) {
+        out.names.push_back(has_header && c < header.size() ? header[c] : "Variable_" + std::to_string(c));
+        out.arity.push_back(c < code_of.size() ? (int)code_of[c].size() : 0);
+        if (c < cols.size()) out.codes.insert(out.codes.end(), cols[c].begin(), cols[c].end());
+    }
+    return true;
+}
+
 bool read_skeleton(const std::string &path, int n_expected, std::vector<uint64_t> &rows, int &num_vertices) {
     std::ifstream in(path);
     if (!in) return false;

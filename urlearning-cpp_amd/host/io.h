@@ -24,6 +24,25 @@ struct RecordStats {
 };
 bool record_stats(const std::string &path, char delim, bool has_header, RecordStats &out);
 
+// The discrete records `score -f BIC` counts: RecordFile::read
+// (base/record_file.h:39-54) plus BayesianNetwork::initialize
+// (base/variable.h:43-64), in one pass with record_stats' tokenisation (the
+// line trimmed, then split on the delimiter).  With has_header the first line
+// gives the names; without it the first line is a record.  A variable's value
+// code is the order of first appearance of the token in its column; arity =
+// number of distinct tokens (what record_stats calls arity).  The column count
+// is the first record's token count, as in record_stats; further tokens of a longer line are
+// dropped.  A record with fewer tokens than columns (the reference indexes
+// past the end there), a column with more than 255 values and a file that
+// cannot be opened are errors; err names the line.
+struct DiscreteData {
+    int64_t num_records = 0;
+    std::vector<std::string> names;
+    std::vector<int> arity;
+    std::vector<uint8_t> codes;  // column-major: codes[c * num_records + r]
+};
+bool load_discrete_csv(const std::string &path, char delim, bool has_header, DiscreteData &out, std::string &err);
+
 // Skeleton::read_matrix_file / read_arc_list_file (base/skeleton.cpp:19-105).
 // Returns false if the file cannot be opened.  rows[i] bit j = edge i-j.
 bool read_skeleton(const std::string &path, int n_expected, std::vector<uint64_t> &rows, int &num_vertices);

@@ -1,13 +1,20 @@
 // score -- the reference's score command line (score/score_main.cpp) on the
-// MI355X path: the input CSV is read on the host, every cBIC parent set is
-// scored by libulg.so on one GPU, and the .pss score cache is written in the
+// MI355X path: the input CSV is read on the host, every parent set is scored
+// by libulg.so on one GPU, and the .pss score cache is written in the
 // reference's exact text format.
 //
+//   score <in.csv> <out.pss> [-f BIC] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //
-// Options that only matter for other scoring functions or for the reference's
-// AD-tree (-m, -e, -w, -a, -o, --enableDeCamposPruning) are accepted; -e
-// still feeds the "META ess" header line as in score_main.cpp:388.
+// -f BIC (the default, as in the reference) is the discrete score: the tokens
+// of each column are its values (load_discrete_csv), the parent limit is
+// min(-p, (int) log(2N / log N)) (score_main.cpp:300-304) and --lambda is
+// ignored.  -f cBIC reads the columns as numbers.  BDeu and fNML are not
+// built; nor is --enableDeCamposPruning with -f BIC (experimental in the
+// reference).  Options that only matter for those or for the reference's
+// AD-tree (-m, -e, -w, -a, -o) are accepted; -e still feeds the "META ess"
+// header line as in score_main.cpp:388.
+#include <cmath>
 #include <cctype>
 #include <cstdio>
 #include <string>
@@ -27,15 +34,15 @@ int main(int argc, char **argv) {
             {"w", "scoreType", true, "1", "which score (not on this path)"},
             {"c", "constraints", true, "", "The file specifying constraints on the scores."},
             {"k", "skeleton", true, "", "The file specifying the skeleton superstructure"},
-            {"m", "rMin", true, "5", "The minimum number of records in the AD-tree nodes (unused by cBIC)."},
-            {"f", "function", true, "BIC", "The scoring function to use (cBIC)."},
+            {"m", "rMin", true, "5", "The minimum number of records in the AD-tree nodes (no effect: the counts are exact)."},
+            {"f", "function", true, "BIC", "The scoring function to use (BIC or cBIC)."},
             {"e", "ess", true, "1", "The equivalent sample size (written to META ess)."},
             {"p", "maxParents", true, "0", "The maximum number of parents for any variable. A value less than 1 means no limit."},
             {"t", "threads", true, "1", "Host threads in the reference; the GPU scores every variable at once."},
             {"r", "time", true, "-1", "The maximum amount of time (s) to use for each variable (every variable is scored at once: the budget of the whole call, checked after each layer). A value less than 1 means no limit."},
             {"s", "hasHeader", false, "", "Add this flag if the first line of the input file gives the variable names."},
             {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171)."},
-            {"", "enableDeCamposPruning", false, "", "No effect for cBIC."},
+            {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC."},
             {"", "device", true, "0", "HIP device to use."},
             {"h", "help", false, "", "Show this help message."},
         },
@@ -46,13 +53,19 @@ int main(int argc, char **argv) {
         return 2;
     }
     if (args.has("help") || argc == 1 || !args.has("input") || !args.has("output")) {
-        args.usage(argv[0], "Compute the scores for a csv file on an MI355X.  Example usage: score iris.csv iris.pss -f cBIC --lambda 2");
+        args.usage(argv[0], "Compute the scores for a csv file on an MI355X.  Example usage: score iris.csv iris.pss  (discrete BIC), or: score iris.csv iris.pss -f cBIC --lambda 2");
         return args.has("help") || argc == 1 ? 0 : 2;
     }
     std::string sf = args.get("function");
     for (char &ch : sf) ch = (char)std::tolower((unsigned char)ch);
-    if (sf != "cbic") {
-        std::fprintf(stderr, "score: scoring function '%s' is not on this path; use -f cBIC\n", args.get("function").c_str());
+    if (sf != "cbic" && sf != "bic") {
+        std::fprintf(stderr, "score: scoring function '%s' is not on this path; use -f cBIC or -f BIC\n",
+                     args.get("function").c_str());
+        return 2;
+    }
+    const bool discrete = sf == "bic";
+    if (discrete && args.has("enableDeCamposPruning")) {
+        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC (it is a no-op for -f cBIC)\n");
         return 2;
     }
     const std::string input = args.get("input"), output = args.get("output");
@@ -62,16 +75,30 @@ int main(int argc, char **argv) {
     int maxp = std::atoi(args.get("maxParents").c_str());
 
     ulgio::RecordStats rs;
-    if (!ulgio::record_stats(input, delim, has_header, rs)) {
-        std::fprintf(stderr, "score: cannot read '%s'\n", input.c_str());
-        return 1;
-    }
+    ulgio::DiscreteData dd;
     std::vector<double> data;
     int64_t N = 0;
     int ncols = 0;
-    if (!ulgio::load_numeric_csv(input, data, N, ncols)) {
-        std::fprintf(stderr, "score: cannot load '%s'\n", input.c_str());
-        return 1;
+    if (discrete) {
+        std::string derr;
+        if (!ulgio::load_discrete_csv(input, delim, has_header, dd, derr)) {
+            std::fprintf(stderr, "score: %s\n", derr.c_str());
+            return 1;
+        }
+        rs.num_records = dd.num_records;
+        rs.names = dd.names;
+        rs.arity = dd.arity;
+        N = dd.num_records;
+        ncols = (int)dd.names.size();
+    } else {
+        if (!ulgio::record_stats(input, delim, has_header, rs)) {
+            std::fprintf(stderr, "score: cannot read '%s'\n", input.c_str());
+            return 1;
+        }
+        if (!ulgio::load_numeric_csv(input, data, N, ncols)) {
+            std::fprintf(stderr, "score: cannot load '%s'\n", input.c_str());
+            return 1;
+        }
     }
     const int n = (int)rs.names.size();
     if (n != ncols || n < 1 || n > 63) {
@@ -79,6 +106,15 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (maxp > n || maxp < 1) maxp = n - 1;  // score_main.cpp:296-298
+    if (discrete) {
+        // score_main.cpp:300-304; the reference divides by log 1 at N = 1
+        if (N < 2) {
+            std::fprintf(stderr, "score: -f BIC needs at least 2 records ('%s' has %lld)\n", input.c_str(), (long long)N);
+            return 2;
+        }
+        const int lim = (int)std::log(2 * (double)N / std::log((double)N));
+        if (lim < maxp) maxp = lim;
+    }
     // -c: scoring::parseConstraints over the .pss names (score_main.cpp:314-317)
     const std::string cons_file = args.get("constraints");
     ulgio::Constraints cons;
@@ -110,7 +146,8 @@ int main(int argc, char **argv) {
         return 1;
     }
     const double t0 = ulgcli::now_s();
-    int rc = ulg_cbic_load(ctx, data.data(), N, n, lambda);
+    int rc = discrete ? ulg_disc_load(ctx, dd.codes.data(), N, n, dd.arity.data())
+                      : ulg_cbic_load(ctx, data.data(), N, n, lambda);
     std::vector<int> vars(n);
     for (int v = 0; v < n; ++v) vars[v] = v;
     int64_t stored = 0, scored = 0;
@@ -122,7 +159,9 @@ int main(int argc, char **argv) {
     if (rc == ULG_OK && !cons.vars.empty())
         rc = ulg_cbic_set_constraints(ctx, (int)cons.vars.size(), cons.vars.data(), cons.required.data(),
                                       cons.forbidden.data());
-    if (rc == ULG_OK) rc = ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
+    if (rc == ULG_OK)
+        rc = discrete ? ulg_disc_score(ctx, ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
+                      : ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
     int64_t oot = 0, done_layer = 0;
     if (rc == ULG_OK && running_time > 0) {
         ulg_get_info(ctx, "out_of_time", &oot);
@@ -172,10 +211,10 @@ int main(int argc, char **argv) {
                 (long long)scored, (long long)stored, t1 - t0, (double)scored / (t1 - t0), t2 - t1, t3 - t2,
                 (long long)len);
     std::fprintf(stderr,
-                 "ulg_metrics {\"tool\": \"score\", \"n\": %d, \"N\": %lld, \"k\": %d, \"lambda\": %g, "
+                 "ulg_metrics {\"tool\": \"score\", \"function\": \"%s\", \"n\": %d, \"N\": %lld, \"k\": %d, \"lambda\": %g, "
                  "\"scored\": %lld, \"stored\": %lld, \"score_s\": %.6f, \"sets_per_s\": %.6g, \"format_s\": %.6f, "
                  "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d}\n",
-                 n, (long long)N, maxp, lambda, (long long)scored, (long long)stored, t1 - t0,
+                 sf.c_str(), n, (long long)N, maxp, lambda, (long long)scored, (long long)stored, t1 - t0,
                  (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot);
     return 0;
 }

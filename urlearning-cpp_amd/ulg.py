@@ -45,6 +45,10 @@ def lib():
         L.ulg_cbic_score_vars.argtypes = [P, P, I, P, I, P, P, P, I64]
         L.ulg_cbic_score_sets.argtypes = [P, I64, P, P, P]
         L.ulg_cbic_set_constraints.argtypes = [P, I, P, P, P]
+        L.ulg_disc_load.argtypes = [P, P, I64, I, P]
+        L.ulg_disc_score.argtypes = [P, I, P, I, P, I, C.POINTER(I64), C.POINTER(I64)]
+        L.ulg_disc_score_sets.argtypes = [P, I, I64, P, P, P]
+        L.ulg_disc_counts.argtypes = [P, I, C.c_uint64, P, I64, C.POINTER(I64)]
         L.ulg_quantize_costs.argtypes = [P, P, P, I64]
         L.ulg_search_load.argtypes = [P, I, P, P, P]
         L.ulg_search_from_scores.argtypes = [P]
@@ -211,6 +215,62 @@ class Context:
 
     def clear_constraints(self):
         self._check(lib().ulg_cbic_set_constraints(self._h, 0, None, None, None), "ulg_cbic_set_constraints")
+
+    # ---- discrete BIC -------------------------------------------------------
+    SCORE_BIC = 1
+
+    def load_discrete(self, codes: np.ndarray, arity):
+        """ulg_disc_load: codes = N x n array of value codes (rows = records),
+        arity[j] = cardinality of variable j.  Replaces the loaded data."""
+        x = np.asarray(codes)
+        if x.ndim != 2:
+            raise ValueError("load_discrete: codes must be N x n")
+        if x.size and (x.min() < 0 or x.max() > 255):
+            raise ValueError("load_discrete: codes must be 0..255")
+        N, n = x.shape
+        flat = np.ascontiguousarray(x.astype(np.uint8).T.reshape(-1))  # column-major flatten
+        ar = np.ascontiguousarray(arity, dtype=np.int32)
+        if len(ar) != n:
+            raise ValueError("load_discrete: one arity per column")
+        self._check(lib().ulg_disc_load(self._h, _ptr(flat), N, n, _ptr(ar)), "ulg_disc_load")
+        self.n = n
+        self.N = N
+
+    def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC):
+        """ulg_disc_score -> (total_stored, total_scored); fetch() reads the lists."""
+        v = np.ascontiguousarray(variables, dtype=np.int32)
+        c = np.ascontiguousarray(candidates, dtype=np.uint64)
+        st, sc = C.c_int64(), C.c_int64()
+        self._check(lib().ulg_disc_score(self._h, int(kind), _ptr(v), len(v), _ptr(c), int(max_parents),
+                                         C.byref(st), C.byref(sc)), "ulg_disc_score")
+        self._nv = len(v)
+        return st.value, sc.value
+
+    def score_sets_discrete(self, variables, parents, kind: int = SCORE_BIC) -> np.ndarray:
+        """BICScoringFunction::calculateScore's value per (variable, parent mask) pair (ulg_disc_score_sets)."""
+        v = np.ascontiguousarray(variables, dtype=np.int32)
+        p = np.ascontiguousarray(parents, dtype=np.uint64)
+        if v.shape != p.shape:
+            raise ValueError("score_sets_discrete: variables and parents differ in length")
+        out = np.empty(max(len(v), 1), dtype=np.float32)
+        self._check(lib().ulg_disc_score_sets(self._h, int(kind), len(v), _ptr(v), _ptr(p), _ptr(out)),
+                    "ulg_disc_score_sets")
+        return out[:len(v)]
+
+    def discrete_counts(self, variable: int, parents: int, cap=None) -> np.ndarray:
+        """ulg_disc_counts: the dense contingency table of (variable, parents),
+        cell = sum_p code_p base_p + code_v q (parents ascending, first base 1)."""
+        nc = C.c_int64()
+        if cap is None:
+            probe = np.zeros(1, dtype=np.int32)
+            rc = lib().ulg_disc_counts(self._h, int(variable), C.c_uint64(int(parents)), _ptr(probe), 0, C.byref(nc))
+            if rc != 0 and nc.value <= 0:
+                self._check(rc, "ulg_disc_counts")
+            cap = nc.value
+        out = np.zeros(max(int(cap), 1), dtype=np.int32)
+        self._check(lib().ulg_disc_counts(self._h, int(variable), C.c_uint64(int(parents)), _ptr(out), int(cap),
+                                          C.byref(nc)), "ulg_disc_counts")
+        return out[:nc.value]
 
     def quantize(self, scores: np.ndarray) -> np.ndarray:
         s = np.ascontiguousarray(scores, dtype=np.float32)

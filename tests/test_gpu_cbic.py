@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 REL_TOL = 1e-6
 DEFAULT_VARIANT = 241  # the library default (ulg_internal.h)
+DEFAULT_WALK_BUCKET = 1  # likewise; the ABI has no getter, and the context outlives the test
 
 
 def _compare_lists(o_offs, o_sets, o_scores, g_offs, g_sets, g_scores, variables, ctx=""):
@@ -315,7 +316,7 @@ def test_walk_forms_match_oracle(ulg_ctx, oracle_built, variant, option):
             o = _oracle_lists(oracle_built, X, 2.0, variables, cands, 6)
             _compare_lists(*o, *g, variables, ctx=f"{option} variant {variant}")
     finally:
-        ulg_ctx.set_option(option, 0)
+        ulg_ctx.set_option(option, DEFAULT_WALK_BUCKET)
         ulg_ctx.set_option("score_variant", DEFAULT_VARIANT)
 
 
@@ -340,7 +341,7 @@ def test_walk_forms_identical_c3_c5(ulg_ctx, option):
                 for a, b in zip(ref, got):
                     assert np.asarray(a).tobytes() == np.asarray(b).tobytes(), (n, streams, k6)
         finally:
-            ulg_ctx.set_option(option, 0)
+            ulg_ctx.set_option(option, DEFAULT_WALK_BUCKET)
             ulg_ctx.set_option("walk_k6", 4)
             ulg_ctx.set_option("score_streams", 3)
 

@@ -6,6 +6,8 @@
     decrease-key sequences, including sub-FLT_EPSILON near-ties that make the
     reference's __down_heap move and leave stale pqPos values; every pop,
     heap slot and position must agree;
+  * urlearning-cpp_amd/bin/san/plan_check: the scoring call's host arithmetic
+    (csrc/score_plan.h) against brute-force enumeration of parent sets;
   * urlearning-cpp_amd/bin/san/pss_dump: the parallel .pss reader (host/io.cpp);
   * oracle/build/san/ref_{score,astar,triplet}: the CPU oracle's command lines.
 Any sanitizer report aborts the program, so a zero exit status is the check."""
@@ -42,6 +44,11 @@ def _run(cmd, **extra_env):
 def test_heap_replays_agree_under_sanitizers(san_built, seed, ops, bits):
     r = _run([os.path.join(SAN, "heap_check"), str(seed), str(ops), str(bits)])
     assert "heap_check ok" in r.stdout
+
+
+def test_score_plan_matches_enumeration_under_sanitizers(san_built):
+    r = _run([os.path.join(SAN, "plan_check")])
+    assert "plan_check ok" in r.stdout
 
 
 def test_pss_reader_under_sanitizers(san_built, tmp_path):

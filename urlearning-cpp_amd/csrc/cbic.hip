@@ -181,9 +181,8 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb, int on) {
 // Only the constrained kernels read it (*_cons_kernel: the texts of
 // cbic_score_{layer,small,wide,sets}.inc included a second time with
 // ULG_CONS 1, so the unconstrained kernels stay the code they were); tables
-// of at most kConsLdsWords words are copied into LDS behind the block's
-// layout.
-constexpr int kConsLdsWords = 256;
+// of at most kConsLdsWords words (score_plan.h) are copied into LDS behind
+// the block's layout.
 __host__ __device__ inline bool cons_violates(const uint64_t *ct, int nv, int vi, uint64_t set) {
     const uint64_t b = ct[vi], e = ct[vi + 1];
     if (b == e) return false;
@@ -262,28 +261,13 @@ __host__ __device__ inline LdsLayout lds_layout(int n, int nv, int S, int L, int
 
 
 
-// The walk queue of a two-pass launch is cut into nseg = ceil(blocks /
-// kSegBlocks) segments, each with its own counter on its own 128-byte line:
-// one counter for the whole launch took ~23 K wave atomics in a row at C3's
-// layer 6 and cost a third of the scoring kernel (318 -> 204 us without it).
-// Block b queues into segment b mod nseg, so the blocks resident at any time
-// spread over all counters and every segment is a cross-section of the
-// launch (segments of neighbouring blocks cluster the long walks into the
-// same walk waves: the layer-6 walk launch took 2x longer).  Segment s holds
-// its queued sets at entries [s * kSegEntries, s * kSegEntries + count_s);
-// the walk kernel takes one (segment, chunk) per wave.
-constexpr int kSegBlocks = 32;
-constexpr uint64_t kSegEntries = (uint64_t)kSegBlocks * kBlock;
-constexpr int kSegStride = 16;  // counters 128 B apart
-// A bucketed launch's header after its segment counters (zeroed with them):
-// every key's set total (u32 64..191).
-constexpr int kBucketHdrWords = 128;
+// The walk queue's segments and their counters (kSegBlocks, kSegEntries,
+// kSegStride, kBucketHdrWords, seg_count): score_plan.h.
 // Bits of the call's error word (d_qcount[nqc - 1], zeroed by the prologue,
 // copied beside the stored count by scan_kernel): a wide walk over its cap;
 // a queue position past its segment (nothing is written there); a walk entry
 // whose table slot lies past the call's slots (its decision is not written).
 constexpr unsigned long long kErrWide = 1ull, kErrQueue = 2ull, kErrSlot = 4ull;
-__host__ __device__ inline uint64_t seg_count(uint64_t blocks) { return (blocks + kSegBlocks - 1) / kSegBlocks; }
 __device__ __forceinline__ uint64_t walk_segment() { return blockIdx.x % seg_count(gridDim.x); }
 
 // Append a set to the walk queue (wave-aggregated: one atomic per wave on the
@@ -806,8 +790,8 @@ __global__ void __launch_bounds__(64) walk_sliced_kernel(const uint64_t *queue, 
 // without variable 0 the longest wave's union walk drops from 811 to ~465
 // points and the launch's union points from 311 K to ~100 K
 // (scripts/walk_sched_study.cpp on the dumped queues).  Same walks, same
-// decisions: only which sets share a wave changes.
-constexpr int kBucketMax = 128;  // walk keys: 64 first-level patterns, the all-open one split 64 ways
+// decisions: only which sets share a wave changes.  kBucketMax keys
+// (score_plan.h): 64 first-level patterns, the all-open one split 64 ways.
 
 
 // One block per kBucketSegs segments: the segments' key histogram in LDS
@@ -1073,7 +1057,6 @@ __global__ void __launch_bounds__(64) walk_bucket_kernel(const uint64_t *queue, 
 // whose `checked` set is a 2^q-bit bitset per walking set in HBM (q local
 // bits: P, plus variable 0 when P lacks it).
 constexpr uint64_t kWideStepCap = 1ull << 30;  // per-set walk steps before the call fails loudly
-constexpr uint64_t kWideBitsWords = 1ull << 27;  // checked bitsets, all stream groups together (1 GiB)
 
 __device__ __forceinline__ uint64_t B64(const uint64_t *b, int a, int k) { return b[a * 64 + k]; }
 
@@ -1329,6 +1312,7 @@ WideFn wide_fn(int L, int phase) {
     if (L <= 16) return phase == 0 ? score_wide_kernel<16, 0> : score_wide_kernel<16, 1>;
     return phase == 0 ? score_wide_kernel<kWideMax, 0> : score_wide_kernel<kWideMax, 1>;
 }
+// the constrained twin (launch_twin)
 using WideConsFn = void (*)(WideArgs, const uint64_t *, int);
 WideConsFn wide_cons_fn(int L, int phase) {
     if (L <= 16) return phase == 0 ? score_wide_cons_kernel<16, 0> : score_wide_cons_kernel<16, 1>;
@@ -1668,8 +1652,7 @@ __global__ void __launch_bounds__(kStragThreads) walk_wide_lds_kernel(WideArgs a
 // SURVEY N4) of their stored value, over every subset of the compact mask X;
 // absent keys count as -inf.  A subset-max (zeta) transform: the low
 // kHiTileBits bits per LDS tile, the rest kHiGroup bits per strided pass.
-constexpr int kHiTileBits = 12;
-constexpr int kHiMaxBits = 24;  // 64 MB of floats per variable at most
+constexpr int kHiTileBits = 12;  // tables of up to kHiMaxBits bits (score_plan.h)
 constexpr int kHiGroup = 4;
 
 struct HiArgs {
@@ -1771,8 +1754,7 @@ __global__ void call_prologue_cons_kernel(const uint64_t *tbl_off, int nv, int S
 }
 
 // ---- compaction of the slabs into (set, score) lists ------------------------
-constexpr int kSlotsPerThread = 16;  // contiguous slots per thread (four 16-B loads)
-constexpr int kSlotsPerBlock = kBlock * kSlotsPerThread;
+// kSlotsPerThread contiguous slots per thread, kSlotsPerBlock per block (score_plan.h)
 
 // the thread's kSlotsPerThread slots from `base` (absent past the end)
 __device__ __forceinline__ void load_slots(const float *table, uint64_t total, uint64_t base,
@@ -1978,16 +1960,17 @@ __global__ void quantize_kernel(const float *in, float *out, int64_t count) {
 #include "cbic_score_sets.inc"
 #undef ULG_CONS
 
-using KernelFn = void (*)(ScoreArgs);
-template <int L, int V>
-KernelFn pick_phase(int phase) {
-    return phase == 0 ? score_layer_kernel<L, 0, V> : score_layer_kernel<L, 1, V>;
-}
-// the constrained twins (score_layer_cons_kernel), the same (layer, phase, variant) dispatch
-using ConsKernelFn = void (*)(ScoreArgs, const uint64_t *, int);
-template <int L, int V>
-ConsKernelFn pick_phase_cons(int phase) {
-    return phase == 0 ? score_layer_cons_kernel<L, 0, V> : score_layer_cons_kernel<L, 1, V>;
+// A scoring kernel's type, or with CONS its constrained twin's (*_cons_kernel:
+// the call's constraint table and its words after the common arguments); the
+// dispatch functions below pick either by the same (layer, phase, variant).
+template <bool CONS, class... A>
+using TwinFn = std::conditional_t<CONS, void (*)(A..., const uint64_t *, int), void (*)(A...)>;
+template <bool CONS>
+using LayerFn = TwinFn<CONS, ScoreArgs>;
+template <int L, int V, bool CONS>
+LayerFn<CONS> pick_phase(int phase) {
+    if constexpr (CONS) return phase == 0 ? score_layer_cons_kernel<L, 0, V> : score_layer_cons_kernel<L, 1, V>;
+    else return phase == 0 ? score_layer_kernel<L, 0, V> : score_layer_kernel<L, 1, V>;
 }
 // variants (ulg_set_option "score_variant"): bit 0 unrolled presence gathers
 // (layers <= 6), bit 4 two-pass (settle, queue the rest for a walk launch),
@@ -2000,25 +1983,14 @@ ConsKernelFn pick_phase_cons(int phase) {
 // against 3.59 ms: a 64-set union tree repeats work a 256-set one shares);
 // round 1's loop gathers at every layer, stack-machine recursion,
 // decision-only per-lane walk and statistics build.
-template <int L>
-KernelFn pick(int phase, int variant) {
+template <int L, bool CONS>
+LayerFn<CONS> pick(int phase, int variant) {
     switch (variant) {
-        case 1: return pick_phase<L, 1>(phase);
-        case 49: return pick_phase<L, 17>(phase);
-        case 65: return pick_phase<L, 65>(phase);
-        case 113: return pick_phase<L, 81>(phase);
-        case 241: return pick_phase<L, 209>(phase);
-        default: return nullptr;
-    }
-}
-template <int L>
-ConsKernelFn pick_cons(int phase, int variant) {
-    switch (variant) {
-        case 1: return pick_phase_cons<L, 1>(phase);
-        case 49: return pick_phase_cons<L, 17>(phase);
-        case 65: return pick_phase_cons<L, 65>(phase);
-        case 113: return pick_phase_cons<L, 81>(phase);
-        case 241: return pick_phase_cons<L, 209>(phase);
+        case 1: return pick_phase<L, 1, CONS>(phase);
+        case 49: return pick_phase<L, 17, CONS>(phase);
+        case 65: return pick_phase<L, 65, CONS>(phase);
+        case 113: return pick_phase<L, 81, CONS>(phase);
+        case 241: return pick_phase<L, 209, CONS>(phase);
         default: return nullptr;
     }
 }
@@ -2105,48 +2077,32 @@ const char *kWalkNames[2][kMaxL + 1] = {
     {"", "walk_1_rest", "walk_2_rest", "walk_3_rest", "walk_4_rest", "walk_5_rest", "walk_6_rest", "walk_7_rest",
      "walk_8_rest"}};
 
-using SmallFn = void (*)(ScoreArgs, const uint64_t *);
-SmallFn small_kernel(int Lf) {
-    switch (Lf) {
-        case 1: return score_small_kernel<1, 65>;
-        case 2: return score_small_kernel<2, 65>;
-        case 3: return score_small_kernel<3, 65>;
-        default: return score_small_kernel<4, 65>;
-    }
+template <int LF, bool CONS>
+TwinFn<CONS, ScoreArgs, const uint64_t *> small_pick() {
+    if constexpr (CONS) return score_small_cons_kernel<LF, 65>;
+    else return score_small_kernel<LF, 65>;
 }
-using SmallConsFn = void (*)(ScoreArgs, const uint64_t *, const uint64_t *, int);
-SmallConsFn small_cons_kernel(int Lf) {
+template <bool CONS>
+TwinFn<CONS, ScoreArgs, const uint64_t *> small_kernel(int Lf) {
     switch (Lf) {
-        case 1: return score_small_cons_kernel<1, 65>;
-        case 2: return score_small_cons_kernel<2, 65>;
-        case 3: return score_small_cons_kernel<3, 65>;
-        default: return score_small_cons_kernel<4, 65>;
+        case 1: return small_pick<1, CONS>();
+        case 2: return small_pick<2, CONS>();
+        case 3: return small_pick<3, CONS>();
+        default: return small_pick<4, CONS>();
     }
 }
 
-KernelFn layer_kernel(int L, int phase, int variant) {
+template <bool CONS>
+LayerFn<CONS> layer_kernel(int L, int phase, int variant) {
     switch (L) {
-        case 1: return pick<1>(phase, variant);
-        case 2: return pick<2>(phase, variant);
-        case 3: return pick<3>(phase, variant);
-        case 4: return pick<4>(phase, variant);
-        case 5: return pick<5>(phase, variant);
-        case 6: return pick<6>(phase, variant);
-        case 7: return pick<7>(phase, variant);
-        case 8: return pick<8>(phase, variant);
-        default: return nullptr;
-    }
-}
-ConsKernelFn layer_cons_kernel(int L, int phase, int variant) {
-    switch (L) {
-        case 1: return pick_cons<1>(phase, variant);
-        case 2: return pick_cons<2>(phase, variant);
-        case 3: return pick_cons<3>(phase, variant);
-        case 4: return pick_cons<4>(phase, variant);
-        case 5: return pick_cons<5>(phase, variant);
-        case 6: return pick_cons<6>(phase, variant);
-        case 7: return pick_cons<7>(phase, variant);
-        case 8: return pick_cons<8>(phase, variant);
+        case 1: return pick<1, CONS>(phase, variant);
+        case 2: return pick<2, CONS>(phase, variant);
+        case 3: return pick<3, CONS>(phase, variant);
+        case 4: return pick<4, CONS>(phase, variant);
+        case 5: return pick<5, CONS>(phase, variant);
+        case 6: return pick<6, CONS>(phase, variant);
+        case 7: return pick<7, CONS>(phase, variant);
+        case 8: return pick<8, CONS>(phase, variant);
         default: return nullptr;
     }
 }
@@ -2158,15 +2114,49 @@ const char *kLayerNames[2][kMaxL + 1] = {
     {"", "score_layer_1_rest", "score_layer_2_rest", "score_layer_3_rest", "score_layer_4_rest",
      "score_layer_5_rest", "score_layer_6_rest", "score_layer_7_rest", "score_layer_8_rest"}};
 
-// One wide layer phase on stream st: the scoring launch, then (one sync for
-// the queue length) the walks, in chunks whose checked bitsets fit the budget.
-// `bits` is this stream group's own slice of c->d_wbits (`slice` words): the
-// groups' walks run concurrently on their own streams.
-// One wide layer phase for every stream group, in stages so the groups stay
-// concurrent: every group's scoring launch; the queue lengths (one D2H each
-// into pinned memory, then the syncs -- the launches already overlap); every
-// group's hi-cover tables and walks; the long-walk counts; the LDS replays.
-// `bits` is each group's own slice of c->d_wbits (`slice` words).
+// ---- the scoring call's launches (host) --------------------------------------
+// the call's constraint table on the device (words 0: the unconstrained kernels)
+struct ConsTable {
+    const uint64_t *dev;
+    int words, lds;
+};
+
+// What the launch steps of one scoring call share.
+struct ScoreCall {
+    ulg_ctx *c;
+    const ScoreLists &ls;
+    const CbicPlan &p;
+    ConsTable cons;
+    ScoreArgs sa;                  // the fields every layer launch shares
+    const uint64_t *d_wk;          // the stream groups' work prefixes (p.group_work()) on the device
+    std::vector<hipStream_t> gst;  // each group's stream; group 0 is the context's
+    const char *wck;               // ULG_WALK_CLOCK: walk diagnostics (synchronising)
+    unsigned long long *errf() const { return p.zero_q ? c->d_qcount.p + p.nqc - 1 : nullptr; }
+};
+
+// One launch on stream st under its profiling name; LDS above 64 KiB is asked for first.
+template <class Fn, class... A>
+int launch_kernel(ulg_ctx *c, Fn fn, dim3 grid, dim3 block, int lds, hipStream_t st, const char *name, A... args) {
+    if (lds > 64 * 1024)
+        ULG_HIP(c, hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    prof_begin_s(c, name, st);
+    hipLaunchKernelGGL(fn, grid, block, (size_t)lds, st, args...);
+    prof_end_s(c, st);
+    return ULG_OK;
+}
+// A scoring launch: kernel fn, or under constraints its twin cfn, which takes
+// the table and its words after the common arguments and stages the table in
+// LDS behind the kernel's own layout.
+template <class Fn, class ConsFn, class... A>
+int launch_twin(ulg_ctx *c, const ConsTable &ct, Fn fn, ConsFn cfn, dim3 grid, dim3 block, int lds, hipStream_t st,
+                const char *name, A... args) {
+    if (!ct.words) return launch_kernel(c, fn, grid, block, lds, st, name, args...);
+    return launch_kernel(c, cfn, grid, block, align16(lds) + ct.lds, st, name, args..., ct.dev, ct.words);
+}
+
+// One stream group's part of a wide layer phase; `bits` is the group's own
+// slice of c->d_wbits (p.wslice words), so the groups' walks run concurrently
+// on their own streams.
 struct WideGroup {
     hipStream_t st;
     const uint64_t *d_work, *h_work;
@@ -2181,6 +2171,28 @@ struct WideGroup {
     uint32_t *hq = nullptr;      // replays handed to the host (indices into the straggler queue)
     unsigned int *hqc = nullptr;
 };
+
+// Launch (L, ph) of `cnt` sets with the prefixes d_work / h_work, on stream
+// group g's stream with the group's queue, counter, bitset, hi-cover-metadata
+// and host-replay slices.
+WideGroup wide_group(const ScoreCall &k, int g, int L, int ph, const uint64_t *d_work, const uint64_t *h_work,
+                     uint64_t cnt) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    WideGroup wg;
+    wg.st = k.gst[g];
+    wg.d_work = d_work;
+    wg.h_work = h_work;
+    wg.cnt = cnt;
+    wg.queue = c->d_wqueue.p + g * p.wqwords;
+    wg.qc = c->d_qcount.p + p.seg_slot(g, L, ph);
+    wg.scnt = c->d_scount.p + g;
+    wg.bits = c->d_wbits.p + (size_t)g * p.wslice;
+    wg.d_hmeta = p.hoff.empty() ? nullptr : c->d_hmeta.p + (size_t)g * p.hmeta_stride();
+    wg.hq = c->d_hq.p + (size_t)g * std::max<uint64_t>(p.wqwords / 6, 1);
+    wg.hqc = c->d_hqc.p + g;
+    return wg;
+}
 
 // table[pairs[2j]] = pairs[2j + 1] (the bits of a float): the host walks' decisions
 __global__ void scatter_decisions_kernel(const uint64_t *pairs, uint32_t cnt, float *table) {
@@ -2296,233 +2308,248 @@ int host_walks(ulg_ctx *c, WideGroup &G, int L, int ph, int q, uint64_t sn, uint
     return ULG_OK;
 }
 
-// pin: 2 * gs.size() pinned words of the caller's (queue lengths, long-walk counts)
-int score_wide_groups(ulg_ctx *c, int L, int ph, std::vector<WideGroup> &gs, int nv, int S, int kmax,
-                      unsigned long long *errf, uint64_t slice, const std::vector<uint64_t> &hoff,
-                      const std::vector<int> &meta, unsigned long long *pin) {
-    const int ng = (int)gs.size();
-    const int q = ph == 0 ? L : L + 1;
-    // 1. scoring launches
-    for (int gi = 0; gi < ng; ++gi) {
-        WideGroup &G = gs[gi];
-        WideArgs &wa = G.wa;
-        wa.gram = c->gram.p;
-        wa.binom = c->d_binom64.p;
-        wa.cand = c->d_cand.p;
-        wa.meta = c->d_meta.p;
-        wa.tbl_off = c->d_tbl_off.p;
-        wa.work = G.d_work;
-        wa.table = c->table.p;
-        wa.queue = G.queue;
-        wa.qcount = G.qc;
-        wa.hmax = nullptr;
-        wa.pval = nullptr;
-        wa.hoff = nullptr;
-        wa.reduced = c->wide_reduced;
-        wa.N = (double)c->N;
-        wa.lambda = c->lambda;
-        wa.n = c->n;
-        wa.nv = nv;
-        wa.S = S;
-        wa.L = L;
-        const uint64_t blocks = (G.cnt + kBlock - 1) / kBlock;
-        if (c->cons_call_words) {  // the call's constraint table (cbic_score)
-            const WideConsFn cf = wide_cons_fn(L, ph);
-            const int cw = c->cons_call_words;
-            const int lds = align16(c->n * c->n * 8) + (cw <= kConsLdsWords ? cw * 8 : 0);
-            if (lds > 64 * 1024)
-                ULG_HIP(c, hipFuncSetAttribute((const void *)cf, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            prof_begin_s(c, ph == 0 ? "score_wide_var0" : "score_wide_rest", G.st);
-            hipLaunchKernelGGL(cf, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, G.st, wa,
-                               (const uint64_t *)c->d_cons.p, cw);
-            prof_end_s(c, G.st);
-        } else {
-        const WideFn sf = wide_fn(L, ph);
-        const int lds = c->n * c->n * 8;
-        if (lds > 64 * 1024)
-            ULG_HIP(c, hipFuncSetAttribute((const void *)sf, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        prof_begin_s(c, ph == 0 ? "score_wide_var0" : "score_wide_rest", G.st);
-        hipLaunchKernelGGL(sf, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, G.st, wa);
-        prof_end_s(c, G.st);
-        }
-        ULG_HIP(c, hipGetLastError());
-        ULG_HIP(c, hipMemcpyAsync(pin + gi, G.qc, 8, hipMemcpyDeviceToHost, G.st));
+// A group's wide scoring launch; its queue length follows into *pin.
+int wide_score(const ScoreCall &k, int L, int ph, WideGroup &G, unsigned long long *pin) {
+    ulg_ctx *c = k.c;
+    WideArgs &wa = G.wa;
+    wa.gram = c->gram.p;
+    wa.binom = c->d_binom64.p;
+    wa.cand = c->d_cand.p;
+    wa.meta = c->d_meta.p;
+    wa.tbl_off = c->d_tbl_off.p;
+    wa.work = G.d_work;
+    wa.table = c->table.p;
+    wa.queue = G.queue;
+    wa.qcount = G.qc;
+    wa.hmax = nullptr;
+    wa.pval = nullptr;
+    wa.hoff = nullptr;
+    wa.reduced = c->wide_reduced;
+    wa.N = (double)c->N;
+    wa.lambda = c->lambda;
+    wa.n = c->n;
+    wa.nv = k.ls.nv;
+    wa.S = k.ls.S;
+    wa.L = L;
+    const uint64_t blocks = (G.cnt + kBlock - 1) / kBlock;
+    if (int rc = launch_twin(c, k.cons, wide_fn(L, ph), wide_cons_fn(L, ph), dim3((unsigned)blocks), dim3(kBlock),
+                             c->n * c->n * 8, G.st, ph == 0 ? "score_wide_var0" : "score_wide_rest", G.wa))
+        return rc;
+    ULG_HIP(c, hipGetLastError());
+    ULG_HIP(c, hipMemcpyAsync(pin, G.qc, 8, hipMemcpyDeviceToHost, G.st));
+    return ULG_OK;
+}
+
+// The hi-cover tables of this launch's variables, built on the group's
+// stream: [lvars][tile prefix][one block prefix per strided pass], one upload.
+int wide_hicover(const ScoreCall &k, int L, int ph, WideGroup &G) {
+    ulg_ctx *c = k.c;
+    const std::vector<int> &meta = k.p.meta;
+    const int nv = k.ls.nv;
+    hipStream_t st = G.st;
+    WideArgs &wa = G.wa;
+    const int S = k.ls.S, kmax = k.ls.kmax;
+    std::vector<int> lv;
+    for (int i = 0; i < nv; ++i)
+        if (G.h_work[i + 1] > G.h_work[i] && k.p.hoff[i] != ~0ull) lv.push_back(i);
+    const int nl = (int)lv.size();
+    if (nl == 0) return ULG_OK;
+    int maxm = 0;
+    for (int vi : lv) maxm = std::max(maxm, meta[vi * 4 + 1]);
+    const int passes = maxm > kHiTileBits ? (maxm - kHiTileBits + kHiGroup - 1) / kHiGroup : 0;
+    std::vector<int> &hm = G.hm;
+    hm.assign((size_t)nl + (size_t)(nl + 1) * (1 + passes), 0);
+    for (int i = 0; i < nl; ++i) hm[i] = lv[i];
+    int *tp = hm.data() + nl;
+    for (int i = 0; i < nl; ++i) {
+        const int m = meta[lv[i] * 4 + 1];
+        tp[i + 1] = tp[i] + (m <= kHiTileBits ? 1 : 1 << (m - kHiTileBits));
     }
+    for (int pp = 0; pp < passes; ++pp) {
+        int *bp = tp + (size_t)(nl + 1) * (1 + pp);
+        const int bit_lo = kHiTileBits + pp * kHiGroup;
+        for (int i = 0; i < nl; ++i) {
+            const int m = meta[lv[i] * 4 + 1];
+            const int Gb = std::min(kHiGroup, m - bit_lo);
+            bp[i + 1] = bp[i] + (Gb > 0 ? (int)(((1ull << (m - Gb)) + 255) / 256) : 0);
+        }
+    }
+    ULG_HIP(c, hipMemcpyAsync(G.d_hmeta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
+    HiArgs ha{G.d_hmeta, G.d_hmeta + nl, nl, c->d_meta.p, c->d_tbl_off.p, c->table.p, c->d_binom64.p,
+              c->d_hmax.p, c->d_hmax.p + c->hmax_half, c->d_hoff.p, S, L, kmax, 0};
+    prof_begin_s(c, "wide_hicover", st);
+    if (ph == 0) hikey_tile_kernel<0><<<tp[nl], 1024, 0, st>>>(ha);
+    else hikey_tile_kernel<1><<<tp[nl], 1024, 0, st>>>(ha);
+    for (int pp = 0; pp < passes; ++pp) {
+        ha.prefix = G.d_hmeta + nl + (size_t)(nl + 1) * (1 + pp);
+        ha.bit_lo = kHiTileBits + pp * kHiGroup;
+        const int nb = tp[(size_t)(nl + 1) * (1 + pp) + nl];
+        if (nb > 0) hikey_strided_kernel<<<nb, 256, 0, st>>>(ha);
+    }
+    prof_end_s(c, st);
+    ULG_HIP(c, hipGetLastError());
+    wa.hmax = c->d_hmax.p;
+    wa.pval = c->d_hmax.p + c->hmax_half;
+    wa.hoff = c->d_hoff.p;
+    return ULG_OK;
+}
+
+// The walks of the sets a group's scoring launch queued, in chunks whose
+// checked bitsets (2^q bits per walking set, q = L when P holds variable 0,
+// else L + 1) fit the group's slice.  budget: the steps after which a walk
+// moves to the LDS replays (0: never); their count follows into *pin_long.
+int wide_walks(const ScoreCall &k, int L, int ph, WideGroup &G, uint64_t &budget, unsigned long long *pin_long) {
+    ulg_ctx *c = k.c;
+    static const bool wstat = std::getenv("ULG_WALK_STATS") != nullptr;  // diagnostics: synchronises
+    const int q = ph == 0 ? L : L + 1;
+    const WideWalkFn wf = wide_walk_fn(L, ph);
+    const uint64_t wpl = q <= 6 ? 1ull : (1ull << (q - 6));
+    hipStream_t st = G.st;
+    WideArgs &wa = G.wa;
+    const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(G.qn, k.p.wslice / wpl));  // the slice holds >= wpl
+    unsigned long long *ws = nullptr;
+    if (wstat) {
+        int rc2;
+        if ((rc2 = ensure(c, c->d_stats, 16))) return rc2;
+        ws = c->d_stats.p;
+        ULG_HIP(c, hipStreamSynchronize(st));
+        ULG_HIP(c, hipMemsetAsync(ws, 0, 64, st));
+    }
+    // long walks move to the LDS kernel (reduced walks with hi-cover tables only)
+    budget = (wa.hoff && wa.reduced && q <= kStragQMax && c->wide_lds)
+                     ? (c->wide_lds == 2 ? 1 : strag_budget())
+                     : 0;
+    uint64_t *sq = G.queue + 3 * G.qn;  // straggler queue after this launch's entries (the queue has room)
+    if (budget) ULG_HIP(c, hipMemsetAsync(G.scnt, 0, 8, st));
+    const auto tw0 = std::chrono::steady_clock::now();
+    for (uint64_t base = 0; base < G.qn; base += per) {
+        const uint64_t nk = std::min<uint64_t>(per, G.qn - base);
+        ULG_HIP(c, hipMemsetAsync(G.bits, 0, (size_t)(nk * wpl * 8), st));
+        prof_begin_s(c, ph == 0 ? "walk_wide_var0" : "walk_wide_rest", st);
+        hipLaunchKernelGGL(wf, dim3((unsigned)((nk + 63) / 64)), dim3(64), 0, st, wa, base, base + nk, G.bits, wpl,
+                           k.errf(), ws, budget, sq, G.scnt);
+        prof_end_s(c, st);
+        ULG_HIP(c, hipGetLastError());
+    }
+    if (budget) ULG_HIP(c, hipMemcpyAsync(pin_long, G.scnt, 8, hipMemcpyDeviceToHost, st));
+    if (wstat) {
+        unsigned long long h[4];
+        ULG_HIP(c, hipMemcpyAsync(h, ws, 32, hipMemcpyDeviceToHost, st));
+        ULG_HIP(c, hipStreamSynchronize(st));
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+        std::fprintf(stderr,
+                     "walk_stats L=%d phase=%d queued=%llu walks=%llu steps=%llu max=%llu over2^20=%llu "
+                     "launch_ms=%.1f\n",
+                     L, ph, (unsigned long long)G.qn, h[0], h[1], h[2], h[3], ms);
+    }
+    return ULG_OK;
+}
+
+// A group's sn long walks, replayed with their bitsets in LDS; the longest
+// of those finish on host threads (host_walks).
+int wide_lds_replays(const ScoreCall &k, int L, int ph, WideGroup &G, unsigned long long sn) {
+    ulg_ctx *c = k.c;
+    static const bool wstat = std::getenv("ULG_WALK_STATS") != nullptr;
+    const int q = ph == 0 ? L : L + 1;
+    const uint64_t slice = k.p.wslice;
+    unsigned long long *errf = k.errf();
+    // skip bitset in LDS; the hi bitset too up to q = kStragHiLdsQ, else in
+    // this group's checked-bitset slice (free once its walks are done)
+    const bool hl = q <= kStragHiLdsQ;
+    const uint64_t nw = ((uint64_t)1 << q) >> 6;
+    const size_t lds = (size_t)(hl ? 2 : 1) * nw * 8 + 64 * 8 + 64;  // bitsets, xlow, lc
+    using LdsFn = void (*)(WideArgs, const uint64_t *, uint64_t *, unsigned long long *, unsigned long long *,
+                           uint64_t, uint32_t *, unsigned int *, uint32_t);
+    const LdsFn kf = ph == 0 ? (hl ? walk_wide_lds_kernel<0, true> : walk_wide_lds_kernel<0, false>)
+                             : (hl ? walk_wide_lds_kernel<1, true> : walk_wide_lds_kernel<1, false>);
+    ULG_HIP(c, hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const uint64_t per = hl ? sn : std::max<uint64_t>(1, slice / nw);
+    unsigned long long *ws = wstat ? c->d_stats.p : nullptr;
+    if (wstat) ULG_HIP(c, hipMemsetAsync(ws, 0, 128, G.st));
+    const auto tl0 = std::chrono::steady_clock::now();
+    // walks past this many iterations finish on the host; with few
+    // replays in the launch the host takes them sooner (it runs them in
+    // parallel threads, while the GPU's launch time is its longest walk)
+    // Host threads take the long walks only of launches with few replays
+    // (wide_host_max): with thousands of long walks (C1 at lambda 0.5) a
+    // few host threads would queue them behind each other while the GPU
+    // runs them all at once (C1 10.7 s GPU-only against 32 s with every
+    // launch handing over).
+    const uint64_t hbud = sn > c->wide_host_max ? 0
+                          : sn <= kHostFewReplays ? std::min<uint64_t>(c->wide_host_iters, kHostFewBudget)
+                                                  : c->wide_host_iters;
+    // ... and so do launches of few replays over 2^q >= 2^wide_host_q
+    // local subsets: at the top layers of the largest candidate sets
+    // nearly every replay outlives the LDS budget anyway (C4 v = 23:
+    // L >= 15 hands over 13 of 14, 13 of 15, 1 of 1), so its LDS phase is
+    // pure latency
+    if (hbud && (sn <= c->wide_host_first || (c->wide_host_q > 0 && q >= c->wide_host_q && sn <= 128))) {
+        // so few replays that the host takes them all at once: no GPU
+        // replay phase (its length is its longest walk's), straight to
+        // the fills, the copy and the host threads
+        std::vector<uint32_t> all((size_t)sn);
+        for (uint32_t j = 0; j < (uint32_t)sn; ++j) all[j] = j;
+        const unsigned int n32 = (unsigned int)sn;
+        ULG_HIP(c, hipMemcpyAsync(G.hq, all.data(), all.size() * 4, hipMemcpyHostToDevice, G.st));
+        ULG_HIP(c, hipMemcpyAsync(G.hqc, &n32, 4, hipMemcpyHostToDevice, G.st));
+        int rc2;
+        if ((rc2 = host_walks(c, G, L, ph, q, sn, slice, errf))) return rc2;
+        return ULG_OK;
+    }
+    if (hbud) ULG_HIP(c, hipMemsetAsync(G.hqc, 0, 4, G.st));
+    for (uint64_t base = 0; base < sn; base += per) {
+        const uint64_t nk = std::min<uint64_t>(per, sn - base);
+        prof_begin_s(c, "walk_wide_lds", G.st);
+        // many short replays: one wave per block, so more walks run at once
+        // (the walk is one wave's; waves 1-3 only speed up the fill)
+        const unsigned th = sn >= kStragWide ? 64u : (unsigned)kStragThreads;
+        hipLaunchKernelGGL(kf, dim3((unsigned)nk), dim3(th), lds, G.st, G.wa,
+                           G.queue + 3 * (G.qn + base), G.bits, errf, ws, hbud, G.hq, G.hqc, (uint32_t)base);
+        prof_end_s(c, G.st);
+        ULG_HIP(c, hipGetLastError());
+    }
+    if (hbud) {
+        int rc2;
+        if ((rc2 = host_walks(c, G, L, ph, q, sn, slice, errf))) return rc2;
+    }
+    if (wstat) {
+        unsigned long long h[16];
+        ULG_HIP(c, hipMemcpyAsync(h, ws, 128, hipMemcpyDeviceToHost, G.st));
+        ULG_HIP(c, hipStreamSynchronize(G.st));
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count();
+        std::fprintf(stderr,
+                     "walk_lds_stats L=%d phase=%d q=%d replays=%llu iters=%llu max=%llu fill_max_us=%.1f "
+                     "walk_max_us=%.1f launch_ms=%.1f\n",
+                     L, ph, q, h[4], h[5], h[6], h[7] / 100.0, h[8] / 100.0, ms);
+    }
+    return ULG_OK;
+}
+
+// One wide layer phase for every stream group, in stages so the groups stay
+// concurrent: every group's scoring launch; the queue lengths (one D2H each
+// into pinned memory, then the syncs -- the launches already overlap); every
+// group's hi-cover tables and walks; the long-walk counts; the LDS replays.
+// pin: 2 * gs.size() pinned words of the caller's (queue lengths, long-walk counts)
+int score_wide_groups(const ScoreCall &k, int L, int ph, std::vector<WideGroup> &gs, unsigned long long *pin) {
+    ulg_ctx *c = k.c;
+    const int ng = (int)gs.size();
+    int rc;
+    for (int gi = 0; gi < ng; ++gi)
+        if ((rc = wide_score(k, L, ph, gs[gi], pin + gi))) return rc;
     for (int gi = 0; gi < ng; ++gi) {
         ULG_HIP(c, hipStreamSynchronize(gs[gi].st));
         gs[gi].qn = pin[gi];
     }
-    // 2. hi-cover tables and walks
-    static const bool wstat = std::getenv("ULG_WALK_STATS") != nullptr;  // diagnostics: synchronises
-    const WideWalkFn wf = wide_walk_fn(L, ph);
-    const uint64_t wpl = q <= 6 ? 1ull : (1ull << (q - 6));
     std::vector<uint64_t> budget(ng, 0);
     for (int gi = 0; gi < ng; ++gi) {
-        WideGroup &G = gs[gi];
-        if (G.qn == 0) continue;
-        hipStream_t st = G.st;
-        WideArgs &wa = G.wa;
-        if (G.d_hmeta) {
-            // hi-cover tables of this launch's variables: [lvars][tile prefix][one
-            // block prefix per strided pass], one upload
-            std::vector<int> lv;
-            for (int i = 0; i < nv; ++i)
-                if (G.h_work[i + 1] > G.h_work[i] && hoff[i] != ~0ull) lv.push_back(i);
-            const int nl = (int)lv.size();
-            if (nl > 0) {
-                int maxm = 0;
-                for (int vi : lv) maxm = std::max(maxm, meta[vi * 4 + 1]);
-                const int passes = maxm > kHiTileBits ? (maxm - kHiTileBits + kHiGroup - 1) / kHiGroup : 0;
-                std::vector<int> &hm = G.hm;
-                hm.assign((size_t)nl + (size_t)(nl + 1) * (1 + passes), 0);
-                for (int i = 0; i < nl; ++i) hm[i] = lv[i];
-                int *tp = hm.data() + nl;
-                for (int i = 0; i < nl; ++i) {
-                    const int m = meta[lv[i] * 4 + 1];
-                    tp[i + 1] = tp[i] + (m <= kHiTileBits ? 1 : 1 << (m - kHiTileBits));
-                }
-                for (int pp = 0; pp < passes; ++pp) {
-                    int *bp = tp + (size_t)(nl + 1) * (1 + pp);
-                    const int bit_lo = kHiTileBits + pp * kHiGroup;
-                    for (int i = 0; i < nl; ++i) {
-                        const int m = meta[lv[i] * 4 + 1];
-                        const int Gb = std::min(kHiGroup, m - bit_lo);
-                        bp[i + 1] = bp[i] + (Gb > 0 ? (int)(((1ull << (m - Gb)) + 255) / 256) : 0);
-                    }
-                }
-                ULG_HIP(c, hipMemcpyAsync(G.d_hmeta, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, st));
-                HiArgs ha{G.d_hmeta, G.d_hmeta + nl, nl, c->d_meta.p, c->d_tbl_off.p, c->table.p, c->d_binom64.p,
-                          c->d_hmax.p, c->d_hmax.p + c->hmax_half, c->d_hoff.p, S, L, kmax, 0};
-                prof_begin_s(c, "wide_hicover", st);
-                if (ph == 0) hikey_tile_kernel<0><<<tp[nl], 1024, 0, st>>>(ha);
-                else hikey_tile_kernel<1><<<tp[nl], 1024, 0, st>>>(ha);
-                for (int pp = 0; pp < passes; ++pp) {
-                    ha.prefix = G.d_hmeta + nl + (size_t)(nl + 1) * (1 + pp);
-                    ha.bit_lo = kHiTileBits + pp * kHiGroup;
-                    const int nb = tp[(size_t)(nl + 1) * (1 + pp) + nl];
-                    if (nb > 0) hikey_strided_kernel<<<nb, 256, 0, st>>>(ha);
-                }
-                prof_end_s(c, st);
-                ULG_HIP(c, hipGetLastError());
-                wa.hmax = c->d_hmax.p;
-                wa.pval = c->d_hmax.p + c->hmax_half;
-                wa.hoff = c->d_hoff.p;
-            }
-        }
-        // checked bitset: 2^q bits per walking set, q = L (P holds variable 0) or L + 1
-        const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(G.qn, slice / wpl));  // slice >= wpl
-        unsigned long long *ws = nullptr;
-        if (wstat) {
-            int rc2;
-            if ((rc2 = ensure(c, c->d_stats, 16))) return rc2;
-            ws = c->d_stats.p;
-            ULG_HIP(c, hipStreamSynchronize(st));
-            ULG_HIP(c, hipMemsetAsync(ws, 0, 64, st));
-        }
-        // long walks move to the LDS kernel (reduced walks with hi-cover tables only)
-        budget[gi] = (wa.hoff && wa.reduced && q <= kStragQMax && c->wide_lds)
-                         ? (c->wide_lds == 2 ? 1 : strag_budget())
-                         : 0;
-        uint64_t *sq = G.queue + 3 * G.qn;  // straggler queue after this launch's entries (the queue has room)
-        if (budget[gi]) ULG_HIP(c, hipMemsetAsync(G.scnt, 0, 8, st));
-        const auto tw0 = std::chrono::steady_clock::now();
-        for (uint64_t base = 0; base < G.qn; base += per) {
-            const uint64_t k = std::min<uint64_t>(per, G.qn - base);
-            ULG_HIP(c, hipMemsetAsync(G.bits, 0, (size_t)(k * wpl * 8), st));
-            prof_begin_s(c, ph == 0 ? "walk_wide_var0" : "walk_wide_rest", st);
-            hipLaunchKernelGGL(wf, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, wa, base, base + k, G.bits, wpl,
-                               errf, ws, budget[gi], sq, G.scnt);
-            prof_end_s(c, st);
-            ULG_HIP(c, hipGetLastError());
-        }
-        if (budget[gi]) ULG_HIP(c, hipMemcpyAsync(pin + ng + gi, G.scnt, 8, hipMemcpyDeviceToHost, st));
-        if (wstat) {
-            unsigned long long h[4];
-            ULG_HIP(c, hipMemcpyAsync(h, ws, 32, hipMemcpyDeviceToHost, st));
-            ULG_HIP(c, hipStreamSynchronize(st));
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-            std::fprintf(stderr,
-                         "walk_stats L=%d phase=%d queued=%llu walks=%llu steps=%llu max=%llu over2^20=%llu "
-                         "launch_ms=%.1f\n",
-                         L, ph, (unsigned long long)G.qn, h[0], h[1], h[2], h[3], ms);
-        }
+        if (gs[gi].qn == 0) continue;
+        if (gs[gi].d_hmeta && (rc = wide_hicover(k, L, ph, gs[gi]))) return rc;
+        if ((rc = wide_walks(k, L, ph, gs[gi], budget[gi], pin + ng + gi))) return rc;
     }
-    // 3. the long walks, replayed in LDS
     for (int gi = 0; gi < ng; ++gi) {
-        WideGroup &G = gs[gi];
-        if (G.qn == 0 || !budget[gi]) continue;
-        ULG_HIP(c, hipStreamSynchronize(G.st));
-        const unsigned long long sn = pin[ng + gi];
-        if (sn == 0) continue;
-        // skip bitset in LDS; the hi bitset too up to q = kStragHiLdsQ, else in
-        // this group's checked-bitset slice (free once its walks are done)
-        const bool hl = q <= kStragHiLdsQ;
-        const uint64_t nw = ((uint64_t)1 << q) >> 6;
-        const size_t lds = (size_t)(hl ? 2 : 1) * nw * 8 + 64 * 8 + 64;  // bitsets, xlow, lc
-        using LdsFn = void (*)(WideArgs, const uint64_t *, uint64_t *, unsigned long long *, unsigned long long *,
-                               uint64_t, uint32_t *, unsigned int *, uint32_t);
-        const LdsFn kf = ph == 0 ? (hl ? walk_wide_lds_kernel<0, true> : walk_wide_lds_kernel<0, false>)
-                                 : (hl ? walk_wide_lds_kernel<1, true> : walk_wide_lds_kernel<1, false>);
-        ULG_HIP(c, hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const uint64_t per = hl ? sn : std::max<uint64_t>(1, slice / nw);
-        unsigned long long *ws = wstat ? c->d_stats.p : nullptr;
-        if (wstat) ULG_HIP(c, hipMemsetAsync(ws, 0, 128, G.st));
-        const auto tl0 = std::chrono::steady_clock::now();
-        // walks past this many iterations finish on the host; with few
-        // replays in the launch the host takes them sooner (it runs them in
-        // parallel threads, while the GPU's launch time is its longest walk)
-        // Host threads take the long walks only of launches with few replays
-        // (wide_host_max): with thousands of long walks (C1 at lambda 0.5) a
-        // few host threads would queue them behind each other while the GPU
-        // runs them all at once (C1 10.7 s GPU-only against 32 s with every
-        // launch handing over).
-        const uint64_t hbud = sn > c->wide_host_max ? 0
-                              : sn <= kHostFewReplays ? std::min<uint64_t>(c->wide_host_iters, kHostFewBudget)
-                                                      : c->wide_host_iters;
-        // ... and so do launches of few replays over 2^q >= 2^wide_host_q
-        // local subsets: at the top layers of the largest candidate sets
-        // nearly every replay outlives the LDS budget anyway (C4 v = 23:
-        // L >= 15 hands over 13 of 14, 13 of 15, 1 of 1), so its LDS phase is
-        // pure latency
-        if (hbud && (sn <= c->wide_host_first || (c->wide_host_q > 0 && q >= c->wide_host_q && sn <= 128))) {
-            // so few replays that the host takes them all at once: no GPU
-            // replay phase (its length is its longest walk's), straight to
-            // the fills, the copy and the host threads
-            std::vector<uint32_t> all((size_t)sn);
-            for (uint32_t j = 0; j < (uint32_t)sn; ++j) all[j] = j;
-            const unsigned int n32 = (unsigned int)sn;
-            ULG_HIP(c, hipMemcpyAsync(G.hq, all.data(), all.size() * 4, hipMemcpyHostToDevice, G.st));
-            ULG_HIP(c, hipMemcpyAsync(G.hqc, &n32, 4, hipMemcpyHostToDevice, G.st));
-            int rc2;
-            if ((rc2 = host_walks(c, G, L, ph, q, sn, slice, errf))) return rc2;
-            continue;
-        }
-        if (hbud) ULG_HIP(c, hipMemsetAsync(G.hqc, 0, 4, G.st));
-        for (uint64_t base = 0; base < sn; base += per) {
-            const uint64_t k = std::min<uint64_t>(per, sn - base);
-            prof_begin_s(c, "walk_wide_lds", G.st);
-            // many short replays: one wave per block, so more walks run at once
-            // (the walk is one wave's; waves 1-3 only speed up the fill)
-            const unsigned th = sn >= kStragWide ? 64u : (unsigned)kStragThreads;
-            hipLaunchKernelGGL(kf, dim3((unsigned)k), dim3(th), lds, G.st, G.wa,
-                               G.queue + 3 * (G.qn + base), G.bits, errf, ws, hbud, G.hq, G.hqc, (uint32_t)base);
-            prof_end_s(c, G.st);
-            ULG_HIP(c, hipGetLastError());
-        }
-        if (hbud) {
-            int rc2;
-            if ((rc2 = host_walks(c, G, L, ph, q, sn, slice, errf))) return rc2;
-        }
-        if (wstat) {
-            unsigned long long h[16];
-            ULG_HIP(c, hipMemcpyAsync(h, ws, 128, hipMemcpyDeviceToHost, G.st));
-            ULG_HIP(c, hipStreamSynchronize(G.st));
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count();
-            std::fprintf(stderr,
-                         "walk_lds_stats L=%d phase=%d q=%d replays=%llu iters=%llu max=%llu fill_max_us=%.1f "
-                         "walk_max_us=%.1f launch_ms=%.1f\n",
-                         L, ph, q, h[4], h[5], h[6], h[7] / 100.0, h[8] / 100.0, ms);
-        }
+        if (gs[gi].qn == 0 || !budget[gi]) continue;
+        ULG_HIP(c, hipStreamSynchronize(gs[gi].st));
+        if (pin[ng + gi] && (rc = wide_lds_replays(k, L, ph, gs[gi], pin[ng + gi]))) return rc;
     }
     // the hi-cover metadata vectors must outlive their copies
     for (int gi = 0; gi < ng; ++gi)
@@ -2531,35 +2558,89 @@ int score_wide_groups(ulg_ctx *c, int L, int ph, std::vector<WideGroup> &gs, int
 }
 
 
-// The wide layers L0..kmax of every variable that reaches them, one variable
-// per task on G host threads; thread t drives stream gst[t] with stream group
-// t's queue, counter, bitset and hi-cover-metadata slices.  Results are the
-// grouped form's (a variable's decisions read only its own slabs).
-int wide_pool(ulg_ctx *c, int L0, int G, const std::vector<hipStream_t> &gst, int nv, int S, int kmax,
-              int max_parents, const std::vector<int> &mv, const std::vector<int> &meta,
-              const std::vector<uint64_t> &work, uint64_t wqwords, uint64_t wslice, const std::vector<uint64_t> &hoff,
-              size_t nqc) {
-    // every stream's earlier layers first (the slabs the wide layers read)
-    for (int g = 0; g < G; ++g) ULG_HIP(c, hipStreamSynchronize(gst[g]));
-    std::vector<int> order;
-    for (int i = 0; i < nv; ++i)
-        if (std::min(mv[i], max_parents) >= L0) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return mv[a] > mv[b]; });
-    // per-variable launch prefixes: [task][L][phase][nv + 1], only variable i counts
-    const size_t stride = (size_t)(kmax + 1) * 2 * (nv + 1);
-    std::vector<uint64_t> vw(order.size() * stride, 0);
-    for (size_t k = 0; k < order.size(); ++k) {
-        const int i = order[k];
-        for (int L = L0; L <= kmax; ++L)
-            for (int ph = 0; ph < 2; ++ph) {
-                const uint64_t *w = &work[((size_t)L * 2 + ph) * (nv + 1)];
-                uint64_t *o = &vw[k * stride + ((size_t)L * 2 + ph) * (nv + 1)];
-                const uint64_t cnt = w[i + 1] - w[i];
-                for (int j = 0; j <= nv; ++j) o[j] = j > i ? cnt : 0;
-            }
+// ULG_WALK_CLOCK diagnostics: every walk wave's start / end clock and its
+// union points (steps) into <dir>/sliced_L<L>_p<phase>.bin (synchronising)
+int dump_walk_clock(ulg_ctx *c, hipStream_t st, uint64_t sb, const char *dir, int L, int ph) {
+    std::vector<uint64_t> hw((size_t)3 * sb);
+    ULG_HIP(c, hipMemcpyAsync(hw.data(), c->d_dump.p, hw.size() * 8, hipMemcpyDeviceToHost, st));
+    ULG_HIP(c, hipStreamSynchronize(st));
+    char fn[512];
+    std::snprintf(fn, sizeof fn, "%s/sliced_L%d_p%d.bin", dir, L, ph);
+    if (FILE *f = std::fopen(fn, "wb")) {
+        std::fwrite(hw.data(), 8, hw.size(), f);
+        std::fclose(f);
     }
+    return ULG_OK;
+}
+
+// Diagnostics (ULG_WALK_CLOCK with ULG_WALK_QUEUE_DUMP, after a layer's walk
+// launch): the walk queue of that launch, compacted, with each entry's
+// decision as the walk left it in the table -- scripts/walk_sched_study.cpp
+// replays the walks offline.  File: nseg, W, then per segment its count,
+// count x (1 + 2W) entry words and count decision words (the table's bits at
+// the entry's slot).
+int dump_walk_queue(ulg_ctx *c, hipStream_t st, const uint64_t *queue, const unsigned long long *qc,
+                           uint64_t nseg, int W, uint64_t nslots, const char *dir, int L, int ph) {
+    std::vector<unsigned long long> cnt(nseg * kSegStride);
+    ULG_HIP(c, hipMemcpyAsync(cnt.data(), qc, cnt.size() * 8, hipMemcpyDeviceToHost, st));
+    ULG_HIP(c, hipStreamSynchronize(st));
+    char fn[512];
+    std::snprintf(fn, sizeof fn, "%s/queue_L%d_p%d.bin", dir, L, ph);
+    FILE *f = std::fopen(fn, "wb");
+    if (!f) return ULG_OK;
+    const uint64_t hdr[2] = {nseg, (uint64_t)W};
+    std::fwrite(hdr, 8, 2, f);
+    const uint64_t ew = 1 + 2 * (uint64_t)W;
+    std::vector<uint32_t> tab((size_t)nslots);
+    ULG_HIP(c, hipMemcpyAsync(tab.data(), reinterpret_cast<const uint32_t *>(c->table.p), tab.size() * 4,
+                              hipMemcpyDeviceToHost, st));
+    ULG_HIP(c, hipStreamSynchronize(st));
+    for (uint64_t s = 0; s < nseg; ++s) {
+        const uint64_t n = std::min<uint64_t>(cnt[s * kSegStride], kSegEntries);
+        std::vector<uint64_t> e(n * ew);
+        std::vector<uint32_t> d(n);
+        if (n) {
+            ULG_HIP(c, hipMemcpyAsync(e.data(), queue + s * kSegEntries * ew, e.size() * 8, hipMemcpyDeviceToHost, st));
+            ULG_HIP(c, hipStreamSynchronize(st));
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint32_t slot = (uint32_t)e[i * ew];
+                d[i] = slot < tab.size() ? tab[slot] : 0u;
+            }
+        }
+        std::fwrite(&n, 8, 1, f);
+        std::fwrite(e.data(), 8, e.size(), f);
+        std::fwrite(d.data(), 4, d.size(), f);
+    }
+    std::fclose(f);
+    return ULG_OK;
+}
+
+// The call's error word (kErr* bits) as a status.
+int call_error(ulg_ctx *c, unsigned long long w) {
+    c->last_err_word = w;
+    if (w & kErrWide)
+        return set_err(c, ULG_ERR_UNSUPPORTED,
+                       "ulg_cbic_score: a find_best_subset_score walk in a wide layer exceeded its cap (2^30 steps "
+                       "in walk_wide_kernel, 2^32 iterations or 24 frames in the LDS / host replay)");
+    if (w & (kErrQueue | kErrSlot))
+        return set_err(c, ULG_ERR_STATE,
+                       (w & kErrQueue) ? "ulg_cbic_score: a walk-queue segment overflowed (internal sizing error)"
+                                       : "ulg_cbic_score: a walk entry named a slot past the call's table");
+    return ULG_OK;
+}
+
+// The wide layers of every variable that reaches them, one variable per task
+// (p.pool_order) on G host threads; thread t drives stream gst[t] with stream
+// group t's queue, counter, bitset and hi-cover-metadata slices.  Results are
+// the grouped form's (a variable's decisions read only its own slabs).
+int wide_pool(const ScoreCall &k) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    const int G = p.G;
+    // every stream's earlier layers first (the slabs the wide layers read)
+    for (int g = 0; g < G; ++g) ULG_HIP(c, hipStreamSynchronize(k.gst[g]));
     int rc;
-    if ((rc = upload(c, c->d_vwork, c->mir_vwork, vw))) return rc;
+    if ((rc = upload(c, c->d_vwork, c->mir_vwork, p.vw))) return rc;
     ULG_HIP(c, hipStreamSynchronize(c->stream));  // the other threads' streams read it next
     std::atomic<size_t> next{0};
     std::vector<int> rcs(G, ULG_OK);
@@ -2568,37 +2649,23 @@ int wide_pool(ulg_ctx *c, int L0, int G, const std::vector<hipStream_t> &gst, in
             rcs[t] = set_err(c, ULG_ERR_HIP, "hipSetDevice failed in a wide-layer thread");
             return;
         }
-        for (size_t k = next++; k < order.size(); k = next++) {
-            const int i = order[k];
-            const int top = std::min(mv[i], max_parents);
-            for (int L = L0; L <= top; ++L)
+        for (size_t task = next++; task < p.pool_order.size(); task = next++) {
+            const int top = std::min(k.ls.mv[p.pool_order[task]], k.ls.max_parents);
+            for (int L = kMaxL + 1; L <= top; ++L)
                 for (int ph = 0; ph < 2; ++ph) {
-                    const size_t wo = ((size_t)L * 2 + ph) * (nv + 1);
-                    const uint64_t cnt = vw[k * stride + wo + nv];
+                    const size_t wo = task * p.wstride + ((size_t)L * 2 + ph) * (p.nv + 1);
+                    const uint64_t cnt = p.vw[wo + p.nv];
                     if (cnt == 0) continue;
-                    WideGroup wg;
-                    wg.st = gst[t];
-                    wg.d_work = c->d_vwork.p + k * stride + wo;
-                    wg.h_work = vw.data() + k * stride + wo;
-                    wg.cnt = cnt;
-                    wg.queue = c->d_wqueue.p + t * wqwords;
-                    wg.qc = c->d_qcount.p + (size_t)t * 2 * (kmax + 1) + (L * 2 + ph);
-                    wg.scnt = c->d_scount.p + t;
-                    wg.bits = c->d_wbits.p + (size_t)t * wslice;
-                    wg.d_hmeta = hoff.empty() ? nullptr : c->d_hmeta.p + (size_t)t * (nv + (size_t)(nv + 1) * 8);
-                    wg.hq = c->d_hq.p + (size_t)t * std::max<uint64_t>(wqwords / 6, 1);
-                    wg.hqc = c->d_hqc.p + t;
+                    std::vector<WideGroup> one{wide_group(k, t, L, ph, c->d_vwork.p + wo, p.vw.data() + wo, cnt)};
                     // this slot's counter served the previous variable's launch
-                    if (hipMemsetAsync(wg.qc, 0, 8, wg.st) != hipSuccess) {
+                    if (hipMemsetAsync(one[0].qc, 0, 8, one[0].st) != hipSuccess) {
                         rcs[t] = set_err(c, ULG_ERR_HIP, "hipMemsetAsync failed in a wide-layer thread");
                         return;
                     }
-                    std::vector<WideGroup> one{std::move(wg)};
-                    const int r = score_wide_groups(c, L, ph, one, nv, S, kmax, c->d_qcount.p + nqc - 1, wslice, hoff,
-                                                    meta, c->wide_pinned + 2 * t);
+                    const int r = score_wide_groups(k, L, ph, one, c->wide_pinned + 2 * t);
                     if (r) {
                         rcs[t] = r;
-                        next = order.size();  // the other threads stop at their next task
+                        next = p.pool_order.size();  // the other threads stop at their next task
                         return;
                     }
                 }
@@ -2613,14 +2680,205 @@ int wide_pool(ulg_ctx *c, int L0, int G, const std::vector<hipStream_t> &gst, in
     return ULG_OK;
 }
 
-}  // namespace
+// A wide layer phase in grouped form: every stream group's part, staged together.
+int launch_wide_grouped(const ScoreCall &k, int L, int ph) {
+    const CbicPlan &p = k.p;
+    std::vector<WideGroup> wide;
+    for (int g = 0; g < p.G; ++g) {
+        const uint64_t cnt = p.launch_count(g, L, ph);
+        if (cnt == 0) continue;
+        if ((cnt + kBlock - 1) / kBlock > 0x7fffffffull)
+            return set_err(k.c, ULG_ERR_UNSUPPORTED, "ulg_cbic_score: layer too large");
+        const size_t wo = p.work_offset(g, L, ph);
+        wide.push_back(wide_group(k, g, L, ph, k.d_wk + wo, p.group_work().data() + wo, cnt));
+    }
+    return wide.empty() ? ULG_OK : score_wide_groups(k, L, ph, wide, k.c->wide_pinned);
+}
 
-namespace {
+// The call's first launch: the empty sets' slots, and the queue counters zeroed.
+int launch_prologue(const ScoreCall &k) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    const uint64_t nqc = p.zero_q ? p.nqc : 0;
+    const uint64_t nz = std::max<uint64_t>((uint64_t)p.nv, std::max<uint64_t>(nqc, p.nqseg));
+    const dim3 grid((unsigned)((nz + 255) / 256)), block(256);
+    unsigned long long *qcount = p.zero_q ? c->d_qcount.p : nullptr, *qseg = p.zero_q ? c->d_qseg.p : nullptr;
+    // the twin takes (table, n) where the scoring twins take (table, words)
+    if (k.cons.words)
+        return launch_kernel(c, call_prologue_cons_kernel, grid, block, 0, c->stream, "call_prologue", c->d_tbl_off.p,
+                             p.nv, k.ls.S, c->table.p, qcount, nqc, qseg, p.nqseg, k.cons.dev, k.ls.n);
+    return launch_kernel(c, call_prologue_kernel, grid, block, 0, c->stream, "call_prologue", c->d_tbl_off.p, p.nv,
+                         k.ls.S, c->table.p, qcount, nqc, qseg, p.nqseg);
+}
+
+// A small layer phase (L <= p.Ls) on the context stream, one-pass over all
+// variables; layers <= p.Lf run together in one fused launch, sent at (1, 0).
+int launch_small(const ScoreCall &k, int L, int ph) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    const int n = k.ls.n, nv = p.nv, S = k.ls.S;
+    ScoreArgs ss = k.sa;
+    if (L <= p.Lf) {
+        if (L != 1 || ph != 0) return ULG_OK;
+        ss.hsub_out = p.Lf < p.kmax;  // layer Lf's phase 1 maxima: read only by a layer above
+        return launch_twin(c, k.cons, small_kernel<false>(p.Lf), small_kernel<true>(p.Lf), dim3((unsigned)nv),
+                           dim3(kFusedThreads), lds_layout(n, nv, S, p.Lf, 65).total, c->stream, "score_small_fused",
+                           ss, (const uint64_t *)c->d_work.p);
+    }
+    const size_t wo = p.work_offset(0, L, ph);
+    const uint64_t cnt = p.work[wo + nv];
+    if (cnt == 0) return ULG_OK;
+    ss.work = c->d_work.p + wo;
+    ss.hsub_out = !(L == p.kmax && ph == 1);
+    return launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.vsmall), layer_kernel<true>(L, ph, p.vsmall),
+                       dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock),
+                       lds_layout(n, nv, S, L, p.vsmall).total, c->stream, kLayerNames[ph][L], ss);
+}
+
+// The bucketed walk of an unrolled launch's queue (layers 5 and 6): a
+// counting sort of the queue by walk key, then the table's waves.  The
+// profiled walk time includes the sort (count + scatter).
+int walk_bucketed(const ScoreCall &k, int g, int L, int ph, const ScoreArgs &sa, uint64_t blocks, int wk) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    hipStream_t st = k.gst[g];
+    const unsigned long long *qc = sa.qcount;
+    const uint64_t nseg = seg_count(blocks);
+    const int kl = L == 6 ? (wk >= 8 ? 8 : 4) : (wk >= 4 ? 4 : 2);
+    uint32_t *kbase = c->d_qoffs.p + (size_t)g * kBucketMax * p.nseg_max;
+    uint32_t *sidx = c->d_qsidx.p + (size_t)g * p.qcap;
+    uint32_t *qaux = c->d_qaux.p + (size_t)g * p.qcap;
+    const unsigned int *hdr = reinterpret_cast<const unsigned int *>(qc + nseg * kSegStride);
+    prof_begin_s(c, kWalkNames[ph][L], st);
+    walk_bucket_count_kernel<<<(unsigned)((nseg + kBucketSegs - 1) / kBucketSegs), 256, 0, st>>>(
+        qc, (uint32_t)nseg, L, sa.qkey, qaux, kbase);
+    const uint64_t items = nseg * (kSegEntries / 256);
+    walk_bucket_scatter_kernel<<<(unsigned)std::min<uint64_t>(items, 2048), 256, 0, st>>>(qc, qaux, kbase,
+                                                                                          (uint32_t)nseg, L, sidx);
+    hipLaunchKernelGGL(bucket_fn(L, ph, kl), dim3((unsigned)std::min<uint64_t>(p.wave_cap, 4096)), dim3(64), 0, st,
+                       (const uint64_t *)sa.queue, (const uint32_t *)sidx, hdr, c->table.p,
+                       sa.hsub_out ? sa.hsub : nullptr, k.ls.total_slots, sa.err);
+    prof_end_s(c, st);
+    return ULG_OK;
+}
+
+// The bit-sliced walk of an unrolled launch's queue in queue order: one wave
+// per (queue segment, chunk of 64 * K entries).
+int walk_sliced(const ScoreCall &k, int g, int L, int ph, const ScoreArgs &sa, uint64_t blocks, int wk) {
+    ulg_ctx *c = k.c;
+    hipStream_t st = k.gst[g];
+    const char *wck = k.wck;
+    const int kk = L == 7 ? 2 : (L == 8 ? 1 : wk);
+    const uint64_t per = 64ull * (uint64_t)kk;
+    const uint64_t sb = seg_count(blocks) * ((kSegEntries + per - 1) / per);
+    int rc;
+    if (wck && (rc = ensure(c, c->d_dump, (size_t)3 * sb))) return rc;
+    if (wck) ULG_HIP(c, hipMemsetAsync(c->d_dump.p, 0, 24 * sb, st));
+    prof_begin_s(c, kWalkNames[ph][L], st);
+    hipLaunchKernelGGL(sliced_fn(L, ph, wk), dim3((unsigned)sb), dim3(64), 0, st, sa.queue, sa.qcount, c->table.p,
+                       sa.hsub_out ? sa.hsub : nullptr, wck ? c->d_dump.p : nullptr, k.ls.total_slots, sa.err);
+    prof_end_s(c, st);
+    if (wck && (rc = dump_walk_clock(c, st, sb, wck, L, ph))) return rc;
+    if (wck && std::getenv("ULG_WALK_QUEUE_DUMP") &&
+        (rc = dump_walk_queue(c, st, sa.queue, sa.qcount, seg_count(blocks), bits_words(L), k.ls.total_slots, wck, L,
+                              ph)))
+        return rc;
+    return ULG_OK;
+}
+
+// An unrolled layer phase of stream group g: its scoring launch, then (the
+// two-pass variants) the walk of the undecided lanes it queued, densely
+// packed, in bucketed or queue order.
+int launch_unrolled(const ScoreCall &k, int g, int L, int ph) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    const uint64_t cnt = p.launch_count(g, L, ph);
+    if (cnt == 0) return ULG_OK;
+    const uint64_t blocks = (cnt + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffull) return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_cbic_score: layer too large");
+    const bool two_pass = (p.variant & 16) != 0;
+    const bool bk = p.bucket && (L == 5 || L == 6);
+    ScoreArgs sa = k.sa;
+    sa.work = k.d_wk + p.work_offset(g, L, ph);
+    sa.queue = two_pass ? c->d_queue.p + (size_t)g * p.qwords : nullptr;
+    sa.qcount = two_pass ? c->d_qseg.p + p.segoff[p.seg_slot(g, L, ph)] : nullptr;
+    sa.qkey = bk ? c->d_qkey.p + (size_t)g * p.qcap : nullptr;
+    // nothing reads the subset maxima of the top layer's second phase
+    sa.hsub_out = !(L == p.kmax && ph == 1);
+    int rc;
+    if ((rc = launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.variant), layer_kernel<true>(L, ph, p.variant),
+                          dim3((unsigned)blocks), dim3(kBlock), lds_layout(k.ls.n, p.nv, k.ls.S, L, p.variant).total,
+                          k.gst[g], kLayerNames[ph][L], sa)))
+        return rc;
+    if (!two_pass) return ULG_OK;
+    const int wk = sliced_k(L, cnt, (uint64_t)c->walk_small_sets, c->walk_k6);
+    if (bk) return walk_bucketed(k, g, L, ph, sa, blocks, wk);
+    if ((p.variant & 32) && sliced_fn(L, ph, wk)) return walk_sliced(k, g, L, ph, sa, blocks, wk);
+    return ULG_OK;
+}
+
+// Every layer's launches in order; done_L: the last complete layer (below
+// kmax when the -r budget ran out).  Small layers on the context stream, then
+// the fork: the side streams start after the uploads / prologue / small
+// layers, and the compaction on the context stream waits for every group.
+int launch_layers(const ScoreCall &k, int &done_L) {
+    ulg_ctx *c = k.c;
+    const CbicPlan &p = k.p;
+    const int G = p.G, kmax = p.kmax;
+    // -r (score_calculator.cpp:33-52,78): checked after every complete layer
+    const auto t_call = std::chrono::steady_clock::now();
+    int rc;
+    bool forked = false;
+    done_L = kmax;
+    bool pooled = false;
+    for (int L = 1; L <= kmax && !pooled; ++L) {
+        for (int ph = 0; ph < 2; ++ph) {
+            if (L <= p.Ls) {
+                if ((rc = launch_small(k, L, ph))) return rc;
+                continue;
+            }
+            if (G > 1 && !forked) {
+                ULG_HIP(c, hipEventRecord(c->sync_events[0], c->stream));
+                for (int g = 1; g < G; ++g) ULG_HIP(c, hipStreamWaitEvent(k.gst[g], c->sync_events[0], 0));
+                forked = true;
+            }
+            if (L > kMaxL && p.use_pool) {  // the pool runs every wide layer
+                if ((rc = wide_pool(k))) return rc;
+                pooled = true;
+                break;
+            }
+            if (L > kMaxL) {
+                if ((rc = launch_wide_grouped(k, L, ph))) return rc;
+                continue;
+            }
+            for (int g = 0; g < G; ++g)
+                if ((rc = launch_unrolled(k, g, L, ph))) return rc;
+        }
+        if (c->time_limit_ms > 0 && L < kmax) {
+            for (int g = 0; g < (forked ? G : 1); ++g) ULG_HIP(c, hipStreamSynchronize(k.gst[g]));
+            const double ms =
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+            if (ms > (double)c->time_limit_ms) {
+                done_L = L;
+                c->out_of_time = 1;
+                break;
+            }
+        }
+    }
+    for (int g = 1; g < G && forked; ++g) {
+        ULG_HIP(c, hipEventRecord(c->sync_events[g], k.gst[g]));
+        ULG_HIP(c, hipStreamWaitEvent(c->stream, c->sync_events[g], 0));
+    }
+    ULG_HIP(c, hipGetLastError());
+    return ULG_OK;
+}
+
 uint64_t dbits(double x) {
     uint64_t u;
     std::memcpy(&u, &x, 8);
     return u;
 }
+
 }  // namespace
 
 extern "C" {
@@ -2678,80 +2936,6 @@ int ulg_cbic_gram(ulg_ctx *c, double *out) {
     return ULG_OK;
 }
 
-static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
-                      int64_t *total_stored, int64_t *total_scored, bool async);
-
-// ULG_WALK_CLOCK diagnostics: every walk wave's start / end clock and its
-// union points (steps) into <dir>/sliced_L<L>_p<phase>.bin (synchronising)
-static int dump_walk_clock(ulg_ctx *c, hipStream_t st, uint64_t sb, const char *dir, int L, int ph) {
-    std::vector<uint64_t> hw((size_t)3 * sb);
-    ULG_HIP(c, hipMemcpyAsync(hw.data(), c->d_dump.p, hw.size() * 8, hipMemcpyDeviceToHost, st));
-    ULG_HIP(c, hipStreamSynchronize(st));
-    char fn[512];
-    std::snprintf(fn, sizeof fn, "%s/sliced_L%d_p%d.bin", dir, L, ph);
-    if (FILE *f = std::fopen(fn, "wb")) {
-        std::fwrite(hw.data(), 8, hw.size(), f);
-        std::fclose(f);
-    }
-    return ULG_OK;
-}
-
-// Diagnostics (ULG_WALK_CLOCK with ULG_WALK_QUEUE_DUMP, after a layer's walk
-// launch): the walk queue of that launch, compacted, with each entry's
-// decision as the walk left it in the table -- scripts/walk_sched_study.cpp
-// replays the walks offline.  File: nseg, W, then per segment its count,
-// count x (1 + 2W) entry words and count decision words (the table's bits at
-// the entry's slot).
-static int dump_walk_queue(ulg_ctx *c, hipStream_t st, const uint64_t *queue, const unsigned long long *qc,
-                           uint64_t nseg, int W, uint64_t nslots, const char *dir, int L, int ph) {
-    std::vector<unsigned long long> cnt(nseg * kSegStride);
-    ULG_HIP(c, hipMemcpyAsync(cnt.data(), qc, cnt.size() * 8, hipMemcpyDeviceToHost, st));
-    ULG_HIP(c, hipStreamSynchronize(st));
-    char fn[512];
-    std::snprintf(fn, sizeof fn, "%s/queue_L%d_p%d.bin", dir, L, ph);
-    FILE *f = std::fopen(fn, "wb");
-    if (!f) return ULG_OK;
-    const uint64_t hdr[2] = {nseg, (uint64_t)W};
-    std::fwrite(hdr, 8, 2, f);
-    const uint64_t ew = 1 + 2 * (uint64_t)W;
-    std::vector<uint32_t> tab((size_t)nslots);
-    ULG_HIP(c, hipMemcpyAsync(tab.data(), reinterpret_cast<const uint32_t *>(c->table.p), tab.size() * 4,
-                              hipMemcpyDeviceToHost, st));
-    ULG_HIP(c, hipStreamSynchronize(st));
-    for (uint64_t s = 0; s < nseg; ++s) {
-        const uint64_t n = std::min<uint64_t>(cnt[s * kSegStride], kSegEntries);
-        std::vector<uint64_t> e(n * ew);
-        std::vector<uint32_t> d(n);
-        if (n) {
-            ULG_HIP(c, hipMemcpyAsync(e.data(), queue + s * kSegEntries * ew, e.size() * 8, hipMemcpyDeviceToHost, st));
-            ULG_HIP(c, hipStreamSynchronize(st));
-            for (uint64_t i = 0; i < n; ++i) {
-                const uint32_t slot = (uint32_t)e[i * ew];
-                d[i] = slot < tab.size() ? tab[slot] : 0u;
-            }
-        }
-        std::fwrite(&n, 8, 1, f);
-        std::fwrite(e.data(), 8, e.size(), f);
-        std::fwrite(d.data(), 4, d.size(), f);
-    }
-    std::fclose(f);
-    return ULG_OK;
-}
-
-// The call's error word (kErr* bits) as a status.
-static int call_error(ulg_ctx *c, unsigned long long w) {
-    c->last_err_word = w;
-    if (w & kErrWide)
-        return set_err(c, ULG_ERR_UNSUPPORTED,
-                       "ulg_cbic_score: a find_best_subset_score walk in a wide layer exceeded its cap (2^30 steps "
-                       "in walk_wide_kernel, 2^32 iterations or 24 frames in the LDS / host replay)");
-    if (w & (kErrQueue | kErrSlot))
-        return set_err(c, ULG_ERR_STATE,
-                       (w & kErrQueue) ? "ulg_cbic_score: a walk-queue segment overflowed (internal sizing error)"
-                                       : "ulg_cbic_score: a walk entry named a slot past the call's table");
-    return ULG_OK;
-}
-
 int ulg_cbic_score_finish(ulg_ctx *c, int64_t *total_stored, int64_t *total_scored) {
     if (!c) return ULG_ERR_ARG;
     if (c->async_pending) {
@@ -2772,164 +2956,24 @@ int ulg_cbic_score_finish(ulg_ctx *c, int64_t *total_stored, int64_t *total_scor
     return ULG_OK;
 }
 
-int ulg_cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
-                   int64_t *total_stored, int64_t *total_scored) {
-    return cbic_score(c, vars, nv, candidates, max_parents, total_stored, total_scored, false);
-}
+namespace {
 
-int ulg_cbic_score_async(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents) {
-    return cbic_score(c, vars, nv, candidates, max_parents, nullptr, nullptr, true);
-}
-
-static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
-                      int64_t *total_stored, int64_t *total_scored, bool async) {
-    if (!c) return ULG_ERR_ARG;
-    if (c->async_pending) {  // the previous async call's launches still own the buffers
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
-    if (!c->loaded) return set_err(c, ULG_ERR_STATE, "ulg_cbic_score: call ulg_cbic_load first");
-    if (!vars || !candidates || nv < 1 || nv > c->n) return set_err(c, ULG_ERR_ARG, "ulg_cbic_score: bad variable list");
-    ULG_HIP(c, hipSetDevice(c->device));
-    const int n = c->n;
-    uint64_t seen = 0;
-    for (int i = 0; i < nv; ++i) {
-        if (vars[i] < 0 || vars[i] >= n || ((seen >> vars[i]) & 1ull))
-            return set_err(c, ULG_ERR_ARG, "ulg_cbic_score: variables must be distinct and < n");
-        seen |= 1ull << vars[i];
-    }
-    const uint64_t allmask = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
-    if (max_parents < 1 || max_parents > n - 1) max_parents = n - 1;
-    // per-variable candidate lists (the variable itself never enters a set,
-    // score_calculator.cpp:100)
-    std::vector<uint8_t> cand((size_t)nv * 64, 0);
-    std::vector<int> meta((size_t)nv * 4, 0);
-    std::vector<int> mv(nv);
-    int kmax = 0;
-    for (int i = 0; i < nv; ++i) {
-        const uint64_t C = candidates[i] & allmask & ~(1ull << vars[i]);
-        int m = 0;
-        for (int b = 0; b < n; ++b)
-            if ((C >> b) & 1ull) cand[(size_t)i * 64 + m++] = (uint8_t)b;
-        mv[i] = m;
-        meta[i * 4 + 0] = vars[i];
-        meta[i * 4 + 1] = m;
-        meta[i * 4 + 2] = (C & 1ull) ? 1 : 0;  // variable 0 is a candidate (compact index 0)
-        kmax = std::max(kmax, std::min(m, max_parents));
-    }
-    if (kmax > kWideMax)
-        return set_err(c, ULG_ERR_UNSUPPORTED,
-                       "ulg_cbic_score: parent sets larger than ULG_MAX_PARENTS_GPU (31) are not supported");
-    const int S = kmax + 1;
-    // slab offsets: (vi, L) -> start, final sentinel = total slots
-    std::vector<uint64_t> toff((size_t)nv * S + 1);
-    uint64_t acc = 0;
-    int64_t scored = 0;
-    for (int i = 0; i < nv; ++i)
-        for (int L = 0; L < S; ++L) {
-            toff[(size_t)i * S + L] = acc;
-            const uint64_t cnt = (L <= max_parents) ? binom64(mv[i], L) : 0;
-            acc += cnt;
-            scored += (int64_t)cnt;
-        }
-    toff[(size_t)nv * S] = acc;
-    const uint64_t total_slots = acc;
-    // per launch work prefixes: [L][phase][nv+1]
-    std::vector<uint64_t> work((size_t)(kmax + 1) * 2 * (nv + 1), 0);
-    for (int L = 1; L <= kmax; ++L)
-        for (int ph = 0; ph < 2; ++ph) {
-            uint64_t *w = &work[((size_t)L * 2 + ph) * (nv + 1)];
-            uint64_t s = 0;
-            for (int i = 0; i < nv; ++i) {
-                w[i] = s;
-                const bool z = meta[i * 4 + 2] != 0;
-                uint64_t cnt;
-                if (L > max_parents) cnt = 0;
-                else if (ph == 0) cnt = z ? binom64(mv[i] - 1, L - 1) : 0;
-                else cnt = z ? binom64(mv[i] - 1, L) : binom64(mv[i], L);
-                s += cnt;
-            }
-            w[nv] = s;
-        }
+// Every device buffer the plan sizes, the uploads of its tables (skipped when
+// the device already holds the same bytes) and the groups' streams and events.
+int reserve_buffers(ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p) {
+    const uint64_t total_slots = ls.total_slots;
+    const int nv = ls.nv, G = p.G;
     int rc;
     // the output lists are sized for every slot, so the compaction needs no
     // mid-call sync for the stored count
-    if ((rc = ensure(c, c->table, total_slots)) || (rc = upload(c, c->d_tbl_off, c->mir_tbl_off, toff)) ||
-        (rc = upload(c, c->d_work, c->mir_work, work)) || (rc = upload(c, c->d_cand, c->mir_cand, cand)) ||
-        (rc = upload(c, c->d_meta, c->mir_meta, meta)) || (rc = ensure(c, c->out_sets, total_slots)) ||
+    if ((rc = ensure(c, c->table, total_slots)) || (rc = upload(c, c->d_tbl_off, c->mir_tbl_off, ls.toff)) ||
+        (rc = upload(c, c->d_work, c->mir_work, p.work)) || (rc = upload(c, c->d_cand, c->mir_cand, ls.cand)) ||
+        (rc = upload(c, c->d_meta, c->mir_meta, p.meta)) || (rc = ensure(c, c->out_sets, total_slots)) ||
         (rc = ensure(c, c->out_scores, total_slots)) || (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
         return rc;
-
-    // the call's constraint table: the alternatives of the scored variables in
-    // their compact candidate numbering (cons_violates); none -> the
-    // unconstrained kernels
-    int cons_words = 0;
-    if (!c->cons_var.empty()) {
-        std::vector<uint64_t> ct((size_t)nv + 1, 0);
-        for (int i = 0; i < nv; ++i) {
-            ct[i] = (ct.size() - (size_t)(nv + 1)) / 2;
-            const uint64_t C = candidates[i] & allmask & ~(1ull << vars[i]);
-            auto compact = [&](uint64_t mask) {
-                uint64_t out = 0;
-                for (int k = 0; k < mv[i]; ++k)
-                    if ((mask >> cand[(size_t)i * 64 + k]) & 1ull) out |= 1ull << k;
-                return out;
-            };
-            bool any = false, kept = false;
-            for (size_t j = 0; j < c->cons_var.size(); ++j) {
-                if (c->cons_var[j] != vars[i]) continue;
-                any = true;
-                if (c->cons_req[j] & ~C) continue;  // requires a non-candidate (or the variable itself)
-                kept = true;
-                ct.push_back(compact(c->cons_req[j]));
-                ct.push_back(compact(c->cons_forb[j]));
-            }
-            if (any && !kept) {  // every set of this variable violates
-                ct.push_back(1ull << 63);
-                ct.push_back(0);
-            }
-        }
-        ct[nv] = (ct.size() - (size_t)(nv + 1)) / 2;
-        if (ct[nv] > 0) {
-            if ((rc = upload(c, c->d_cons, c->mir_cons, ct))) return rc;
-            cons_words = (int)ct.size();
-        }
-    }
-    c->cons_call_words = cons_words;
-    const uint64_t *d_cons = cons_words ? c->d_cons.p : nullptr;
-    const int cons_lds = cons_words && cons_words <= kConsLdsWords ? cons_words * 8 : 0;
-
-    ScoreArgs sa;
-    sa.hsub_out = 1;
-    sa.gram = c->gram.p;
-    sa.binom = c->d_binom.p;
-    sa.cand = c->d_cand.p;
-    sa.meta = c->d_meta.p;
-    sa.tbl_off = c->d_tbl_off.p;
-    sa.table = c->table.p;
-    sa.hsub = nullptr;
-    sa.queue = nullptr;
-    sa.qcount = nullptr;
-    sa.err = nullptr;
-    sa.qkey = nullptr;
-    sa.N = (double)c->N;
-    sa.lambda = c->lambda;
-    sa.n = n;
-    sa.nv = nv;
-    sa.S = S;
-    sa.xcd = c->score_xcd;
-    // tables of 2^30 slots or more: the one-pass form with 64-bit slots (the
-    // others keep 32-bit byte offsets in their gathers and slots in entries)
-    const int variant = (total_slots >> 30) ? 1 : c->score_variant;
-    if (variant & 64) {
-        if ((rc = ensure(c, c->d_hsub, total_slots))) return rc;
-        sa.hsub = c->d_hsub.p;
-    }
-    const char *wck = std::getenv("ULG_WALK_CLOCK");  // walk diagnostics (synchronising)
-    // Variables never read each other's slabs, so they are striped over G
-    // groups on concurrent streams: a group's latency-bound walk kernels
-    // overlap the other groups' scoring kernels.  Diagnostics run on one.
-    const int G = ((variant & 16) && !wck) ? std::max(1, std::min(c->score_streams, nv)) : 1;
+    if (p.cons_words && (rc = upload(c, c->d_cons, c->mir_cons, p.ct))) return rc;
+    c->cons_call_words = p.cons_words;
+    if ((p.variant & 64) && (rc = ensure(c, c->d_hsub, total_slots))) return rc;
     while ((int)c->aux_streams.size() < G - 1) {
         hipStream_t st;
         ULG_HIP(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -2940,522 +2984,232 @@ static int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candi
         ULG_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         c->sync_events.push_back(ev);
     }
-    std::vector<hipStream_t> gst(G);
-    gst[0] = c->stream;
-    for (int g = 1; g < G; ++g) gst[g] = c->aux_streams[g - 1];
-    // per group work prefixes (variables outside the group count 0 sets)
-    const size_t wstride = (size_t)(kmax + 1) * 2 * (nv + 1);
-    std::vector<uint64_t> workg(G == 1 ? 0 : (size_t)G * wstride, 0);
-    if (G > 1) {
-        for (int g = 0; g < G; ++g)
-            for (int L = 1; L <= kmax; ++L)
-                for (int ph = 0; ph < 2; ++ph) {
-                    const uint64_t *w = &work[((size_t)L * 2 + ph) * (nv + 1)];
-                    uint64_t *wg = &workg[(size_t)g * wstride + ((size_t)L * 2 + ph) * (nv + 1)];
-                    uint64_t acc2 = 0;
-                    for (int i = 0; i < nv; ++i) {
-                        wg[i] = acc2;
-                        if (i % G == g) acc2 += w[i + 1] - w[i];
-                    }
-                    wg[nv] = acc2;
-                }
-        if ((rc = upload(c, c->d_workg, c->mir_workg, workg))) return rc;
-    }
-    const uint64_t *d_wk = G > 1 ? c->d_workg.p : c->d_work.p;
-    const std::vector<uint64_t> &h_wk = G > 1 ? workg : work;
-    uint64_t qwords = 0;   // per group: every lane of its largest launch may be queued
-    uint64_t wqwords = 0;  // the same for the wide layers' queue (3 words per set)
-    for (int g = 0; g < G; ++g)
-        for (int L = 1; L <= kmax; ++L)
-            for (int ph = 0; ph < 2; ++ph) {
-                const uint64_t cnt = h_wk[(size_t)g * (G > 1 ? wstride : 0) + ((size_t)L * 2 + ph) * (nv + 1) + nv];
-                if (L > kMaxL) wqwords = std::max<uint64_t>(wqwords, 6 * cnt);  // entries + straggler copies
-                else if (variant & 16)
-                    qwords = std::max<uint64_t>(qwords, seg_count((cnt + kBlock - 1) / kBlock) * kSegEntries *
-                                                            (uint64_t)(1 + 2 * bits_words(L)));
-            }
-    // walk-queue segment counters per (group, layer, phase) of the unrolled
-    // two-pass launches (queue_walk), kSegStride words each
-    const size_t nseg_slots = (size_t)G * 2 * (kmax + 1);
-    std::vector<uint64_t> segoff(nseg_slots + 1, 0);
-    for (size_t i = 0; i < nseg_slots; ++i) {
-        const int g = (int)(i / (2 * (size_t)(kmax + 1))), L = (int)((i / 2) % (size_t)(kmax + 1)), ph = (int)(i % 2);
-        const uint64_t cnt = h_wk[(size_t)g * (G > 1 ? wstride : 0) + ((size_t)L * 2 + ph) * (nv + 1) + nv];
-        const bool queued = L >= 1 && L <= kMaxL && (variant & 16);
-        const bool bhdr = queued && (L == 5 || L == 6);  // room for a walk_bucket header
-        segoff[i + 1] = segoff[i] + (queued ? seg_count((cnt + kBlock - 1) / kBlock) * kSegStride : 0) +
-                        (bhdr && cnt ? kBucketHdrWords : 0);
-    }
-    // queue counters per (group, layer, phase), then the wide walks' error flag
-    const size_t nqc = (size_t)G * 2 * (kmax + 1) + 1;
-    if ((variant & 16) || kmax > kMaxL) {
-        if ((rc = ensure(c, c->d_queue, (size_t)G * qwords)) || (rc = ensure(c, c->d_qcount, nqc)) ||
-            (rc = ensure(c, c->d_wqueue, (size_t)G * wqwords)))
-            return rc;
-        if ((rc = ensure(c, c->d_qseg, (size_t)std::max<uint64_t>(segoff.back(), 1)))) return rc;
-    }
-    // bucketed walk launches (walk_bucket, layers 5 and 6): per stream group a
-    // key/rank word and a sorted index per queue entry, the (key, segment)
-    // offsets and the wave table
-    const bool bucket = (variant & 112) == 112 && c->walk_bucket && !wck && kmax >= 5;  // the CMP path queues with keys
-    const uint64_t qcap = (qwords / 3 + 255) & ~255ull;  // queue entries per group (an entry is >= 3 words), 256-aligned
-    uint64_t nseg_max = 1;
-    for (int g = 0; g < G; ++g)
-        for (int L = 5; L <= std::min(kmax, 6); ++L)
-            for (int ph = 0; ph < 2; ++ph) {
-                const uint64_t cnt = h_wk[(size_t)g * (G > 1 ? wstride : 0) + ((size_t)L * 2 + ph) * (nv + 1) + nv];
-                nseg_max = std::max<uint64_t>(nseg_max, seg_count((cnt + kBlock - 1) / kBlock));
-            }
-    const uint64_t wave_cap = qcap / 64 + kBucketMax;  // walk waves of a bucketed launch, at most
-    if (bucket) {
-        if ((rc = ensure(c, c->d_qkey, (size_t)(G * qcap))) || (rc = ensure(c, c->d_qaux, (size_t)(G * qcap))) ||
-            (rc = ensure(c, c->d_qsidx, (size_t)(G * qcap))) ||
-            (rc = ensure(c, c->d_qoffs, (size_t)(G * kBucketMax * nseg_max))))
-            return rc;
-    }
-    // zeroed by call_prologue_kernel (the first launch of the sequence below)
-    const bool zero_q = (variant & 16) || kmax > kMaxL;
-    const uint64_t nqseg = zero_q ? std::max<uint64_t>(segoff.back(), 1) : 0;
-    sa.err = zero_q ? c->d_qcount.p + nqc - 1 : nullptr;
-    // wide-layer walks: one checked-bitset slice per stream group, allocated
-    // before any launch (2^q bits per walking set, q <= kmax + 1)
-    uint64_t wslice = 0;
-    std::vector<uint64_t> hoff;
-    if (kmax > kMaxL) {
-        const uint64_t wpl_max = kmax + 1 <= 6 ? 1ull : (1ull << (kmax + 1 - 6));
-        wslice = std::max<uint64_t>(kWideBitsWords / (uint64_t)G, wpl_max);
-        if ((rc = ensure(c, c->d_wbits, (size_t)(G * wslice))) || (rc = ensure(c, c->d_scount, (size_t)G)) ||
-            (rc = ensure(c, c->d_hq, (size_t)G * std::max<uint64_t>(wqwords / 6, 1))) ||
+    if (G > 1 && (rc = upload(c, c->d_workg, c->mir_workg, p.workg))) return rc;
+    if (p.zero_q &&
+        ((rc = ensure(c, c->d_queue, (size_t)G * p.qwords)) || (rc = ensure(c, c->d_qcount, p.nqc)) ||
+         (rc = ensure(c, c->d_wqueue, (size_t)G * p.wqwords)) || (rc = ensure(c, c->d_qseg, (size_t)p.nqseg))))
+        return rc;
+    if (p.bucket &&
+        ((rc = ensure(c, c->d_qkey, (size_t)(G * p.qcap))) || (rc = ensure(c, c->d_qaux, (size_t)(G * p.qcap))) ||
+         (rc = ensure(c, c->d_qsidx, (size_t)(G * p.qcap))) ||
+         (rc = ensure(c, c->d_qoffs, (size_t)(G * kBucketMax * p.nseg_max)))))
+        return rc;
+    if (p.kmax > kMaxL) {
+        // wide-layer walks: the checked bitsets, allocated before any launch
+        if ((rc = ensure(c, c->d_wbits, (size_t)(G * p.wslice))) || (rc = ensure(c, c->d_scount, (size_t)G)) ||
+            (rc = ensure(c, c->d_hq, (size_t)G * std::max<uint64_t>(p.wqwords / 6, 1))) ||
             (rc = ensure(c, c->d_hqc, (size_t)G)))
             return rc;
-        // hi-cover tables for the variables that reach a wide layer
-        if (c->wide_prune) {
-            hoff.assign(nv, ~0ull);
-            uint64_t htot = 0;
-            for (int i = 0; i < nv; ++i)
-                if (std::min(mv[i], max_parents) > kMaxL && mv[i] <= kHiMaxBits) {
-                    hoff[i] = htot;
-                    htot += 1ull << mv[i];
-                }
-            if (htot > 0) {
-                c->hmax_half = htot;  // d_hmax = [hi-cover maxima][present values]
-                if ((rc = ensure(c, c->d_hmax, (size_t)(2 * htot))) || (rc = upload(c, c->d_hoff, c->mir_hoff, hoff)) ||
-                    (rc = ensure(c, c->d_hmeta, (size_t)G * (nv + (size_t)(nv + 1) * 8))))
-                    return rc;
-            } else {
-                hoff.clear();
-            }
+        if (!p.hoff.empty()) {
+            c->hmax_half = p.htot;  // d_hmax = [hi-cover maxima][present values]
+            if ((rc = ensure(c, c->d_hmax, (size_t)(2 * p.htot))) || (rc = upload(c, c->d_hoff, c->mir_hoff, p.hoff)) ||
+                (rc = ensure(c, c->d_hmeta, (size_t)G * p.hmeta_stride())))
+                return rc;
+        }
+        if ((int)c->wide_host.size() < 2 * G) {
+            if (c->wide_pinned) (void)hipHostFree(c->wide_pinned);
+            c->wide_pinned = nullptr;
+            ULG_HIP(c, hipHostMalloc((void **)&c->wide_pinned, sizeof(unsigned long long) * 2 * (size_t)G,
+                                     hipHostMallocDefault));
+            c->wide_host.assign(2 * G, 0);
         }
     }
-    if (kmax > kMaxL && (int)c->wide_host.size() < 2 * G) {
-        if (c->wide_pinned) (void)hipHostFree(c->wide_pinned);
-        c->wide_pinned = nullptr;
-        ULG_HIP(c, hipHostMalloc((void **)&c->wide_pinned, sizeof(unsigned long long) * 2 * (size_t)G,
-                                 hipHostMallocDefault));
-        c->wide_host.assign(2 * G, 0);
+    return ensure(c, c->d_blk, (size_t)p.nb + 2);
+}
+
+// What a captured launch sequence depends on: the call, the options and every
+// buffer address its kernels were given.
+void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const uint64_t *candidates,
+               std::vector<uint64_t> &gkey) {
+    auto ptr = [](const void *q) { return (uint64_t)(uintptr_t)q; };
+    gkey.assign({(uint64_t)ls.nv, (uint64_t)ls.max_parents, (uint64_t)p.variant, (uint64_t)p.G, (uint64_t)p.Ls,
+                 (uint64_t)c->score_xcd, (uint64_t)ls.n, (uint64_t)c->N, dbits(c->lambda), (uint64_t)c->prof,
+                 (uint64_t)c->walk_small_sets, (uint64_t)c->walk_k6, (uint64_t)c->walk_bucket, ptr(c->d_qaux.p),
+                 ptr(c->d_qsidx.p), ptr(c->d_qkey.p), ptr(c->d_qoffs.p), ptr(c->table.p), ptr(c->d_work.p),
+                 ptr(c->d_workg.p), ptr(c->d_queue.p), ptr(c->d_qcount.p), ptr(c->d_qseg.p), ptr(c->d_cand.p),
+                 ptr(c->d_meta.p), ptr(c->d_tbl_off.p), ptr(c->out_sets.p), ptr(c->out_scores.p),
+                 ptr(c->out_offsets.p), ptr(c->d_blk.p), ptr(c->gram.p), ptr(c->d_binom.p), ptr(c->d_binom64.p),
+                 ptr(c->d_hsub.p), (uint64_t)ls.total_slots, (uint64_t)c->score_small_layers, (uint64_t)c->score_fused,
+                 (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr)});
+    for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
+    for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
+    for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
+}
+
+// The slabs into the output lists: stored sets per block, their scan (the
+// total and the error word land behind it), the (set, score) pairs.  After an
+// exhausted -r budget the layers never launched hold no stored set.
+int compact(const ScoreCall &k, int done_L) {
+    ulg_ctx *c = k.c;
+    const ScoreLists &ls = k.ls;
+    const int nv = ls.nv, S = ls.S;
+    const int64_t nb = k.p.nb;
+    for (int i = 0; i < nv && done_L < ls.kmax; ++i) {
+        const uint64_t b = ls.toff[(size_t)i * S + done_L + 1], e = ls.toff[(size_t)i * S + S];
+        if (e > b) ULG_HIP(c, hipMemsetAsync(c->table.p + b, 0xff, (size_t)(e - b) * 4, c->stream));
     }
-    // Small layers (L <= Ls, little work, latency-bound): one one-pass launch
-    // per phase over all variables on the context stream -- no queue, no walk
-    // launch, no stream groups.  The rest: per group, score + queued walk.
-    const int Ls = (variant & 16) && !wck ? std::min(kmax, std::min(kMaxL, c->score_small_layers)) : 0;
-    const int vsmall = variant & 65;  // the one-pass form (keeping the subset maxima under bit 6)
-    // ... of which layers <= Lf in one launch, a workgroup per variable
-    // (not under -r: the budget is checked after every layer, and a fused
-    // launch would finish layers 2..Lf before the first check)
-    const int Lf = vsmall == 65 && c->time_limit_ms == 0 ? std::min(Ls, c->score_fused) : 0;
-    bool forked = false;
-    // The wide layers variable by variable (wide_pool 1) pay when the
-    // variables that reach them differ in size: the long replays of one then
-    // hold no other's next layer (C4: 2-hop sets of 10..18 candidates).  On
-    // equal candidate sets (C1: a full skeleton) the grouped form's larger
-    // launches keep more replays in flight (C1 at lambda 0.5: 10.7 s against
-    // 15.2 s).  wide_pool 2 (default) picks the pool when the wide variables'
-    // candidate counts span at least 2.
-    bool use_pool = c->wide_pool == 1;
-    if (c->wide_pool == 2) {
-        int lo_m = 64, hi_m = -1;
-        for (int i = 0; i < nv; ++i)
-            if (std::min(mv[i], max_parents) > kMaxL) {
-                lo_m = std::min(lo_m, mv[i]);
-                hi_m = std::max(hi_m, mv[i]);
-            }
-        use_pool = hi_m >= 0 && hi_m - lo_m >= 2;
+    c->completed_layer = done_L;
+    prof_begin(c, "count_stored");
+    count_kernel<<<(unsigned)nb, kBlock, 0, c->stream>>>(c->table.p, ls.total_slots, c->d_blk.p);
+    prof_end(c);
+    prof_begin(c, "scan_stored");
+    scan_kernel<<<1, 1024, 0, c->stream>>>(c->d_blk.p, nb, c->out_offsets.p + nv, k.errf());
+    prof_end(c);
+    const WriteArgs wa{c->table.p,      c->d_blk.p,    c->d_tbl_off.p,  c->d_meta.p,      c->d_cand.p, c->d_binom.p,
+                       c->d_binom64.p,  ls.total_slots, nv,             S,                c->out_sets.p,
+                       c->out_scores.p, c->out_offsets.p};
+    const size_t nseg = (size_t)nv * (size_t)S;
+    const size_t toff_bytes = nseg <= (size_t)kWriteLdsSegs ? (nseg + 1) * sizeof(uint64_t) : 0;
+    prof_begin(c, "write_stored");
+    write_kernel<<<(unsigned)nb, kBlock, toff_bytes, c->stream>>>(wa);
+    prof_end(c);
+    ULG_HIP(c, hipGetLastError());
+    return ULG_OK;
+}
+
+// An early return between BeginCapture and EndCapture (a failed launch,
+// "layer too large") must not leave the context stream capturing: the
+// guard ends the capture, drops the partial graph and the key.
+struct CaptureGuard {
+    ulg_ctx *c;
+    bool active;
+    ~CaptureGuard() {
+        if (!active) return;
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(c->stream, &g);
+        if (g) (void)hipGraphDestroy(g);
+        c->gkey.clear();
+        (void)hipGetLastError();
     }
-    // -r (score_calculator.cpp:33-52,78): checked after every complete layer
-    const auto t_call = std::chrono::steady_clock::now();
-    c->out_of_time = 0;
-    int done_L = kmax;
-    const int64_t nb = (int64_t)((total_slots + kSlotsPerBlock - 1) / kSlotsPerBlock);
-    if ((rc = ensure(c, c->d_blk, (size_t)nb + 2))) return rc;
-    // The launch sequence from here to write_kernel has no host sync when
-    // every layer is unrolled and no budget / diagnostic is on, and it is the
-    // same on every call with the same variables, limits and buffers: it is
-    // captured once into a hipGraph (all stream groups, the fork and join
-    // events, the profiling events) and replayed, which removes the host
-    // launch path of ~40 kernels per call (score_graph, default on).
-    const bool use_graph =
-        c->score_graph && !c->prof && kmax <= kMaxL && c->time_limit_ms == 0 && !wck;
+};
+
+// The call's launches, prologue to write_kernel.  The sequence has no host
+// sync when every layer is unrolled and no budget / diagnostic is on, and it
+// is the same on every call with the same variables, limits and buffers: it
+// is captured once into a hipGraph (all stream groups, the fork and join
+// events, the profiling events) and replayed, which removes the host launch
+// path of ~40 kernels per call (score_graph, default on).
+int launch_call(const ScoreCall &k, const uint64_t *candidates) {
+    ulg_ctx *c = k.c;
+    const int kmax = k.p.kmax;
+    const bool use_graph = c->score_graph && !c->prof && kmax <= kMaxL && c->time_limit_ms == 0 && !k.wck;
     std::vector<uint64_t> gkey;
-    // An early return between BeginCapture and EndCapture (a failed launch,
-    // "layer too large") must not leave the context stream capturing: the
-    // guard ends the capture, drops the partial graph and the key.
-    struct CaptureGuard {
-        ulg_ctx *c;
-        bool active;
-        ~CaptureGuard() {
-            if (!active) return;
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(c->stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-            c->gkey.clear();
-            (void)hipGetLastError();
-        }
-    } capture_guard{c, false};
+    CaptureGuard capture_guard{c, false};
+    c->out_of_time = 0;
     if (use_graph) {
-        gkey.assign({(uint64_t)nv, (uint64_t)max_parents, (uint64_t)variant, (uint64_t)G, (uint64_t)Ls,
-                     (uint64_t)c->score_xcd, (uint64_t)n, (uint64_t)c->N, dbits(c->lambda), (uint64_t)c->prof,
-                     (uint64_t)c->walk_small_sets, (uint64_t)c->walk_k6,
-                     (uint64_t)c->walk_bucket, (uint64_t)(uintptr_t)c->d_qaux.p, (uint64_t)(uintptr_t)c->d_qsidx.p,
-                     (uint64_t)(uintptr_t)c->d_qkey.p,
-                     (uint64_t)(uintptr_t)c->d_qoffs.p,
-                     (uint64_t)(uintptr_t)c->table.p, (uint64_t)(uintptr_t)c->d_work.p,
-                     (uint64_t)(uintptr_t)c->d_workg.p, (uint64_t)(uintptr_t)c->d_queue.p,
-                     (uint64_t)(uintptr_t)c->d_qcount.p, (uint64_t)(uintptr_t)c->d_qseg.p, (uint64_t)(uintptr_t)c->d_cand.p,
-                     (uint64_t)(uintptr_t)c->d_meta.p, (uint64_t)(uintptr_t)c->d_tbl_off.p,
-                     (uint64_t)(uintptr_t)c->out_sets.p, (uint64_t)(uintptr_t)c->out_scores.p,
-                     (uint64_t)(uintptr_t)c->out_offsets.p, (uint64_t)(uintptr_t)c->d_blk.p,
-                     (uint64_t)(uintptr_t)c->gram.p, (uint64_t)(uintptr_t)c->d_binom.p,
-                     (uint64_t)(uintptr_t)c->d_binom64.p, (uint64_t)(uintptr_t)c->d_hsub.p, (uint64_t)total_slots,
-                     (uint64_t)c->score_small_layers, (uint64_t)c->score_fused, (uint64_t)cons_words,
-                     (uint64_t)(uintptr_t)d_cons});
-        for (int i = 0; i < nv; ++i) gkey.push_back((uint64_t)vars[i]);
-        for (int i = 0; i < nv; ++i) gkey.push_back(candidates[i]);
-        for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
+        graph_key(c, k.ls, k.p, candidates, gkey);
         if (c->gexec && gkey == c->gkey) {
             c->completed_layer = kmax;
             ULG_HIP(c, hipGraphLaunch(c->gexec, c->stream));
             for (const ProfRec &r : c->gprof) c->pending.push_back(r);
-            goto launched;
+            return ULG_OK;
         }
         graph_reset(c);
         ULG_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
         capture_guard.active = true;
     }
-    {
     const size_t pend0 = c->pending.size();
-    {
-        const uint64_t nz = std::max<uint64_t>((uint64_t)nv, std::max<uint64_t>(zero_q ? nqc : 0, nqseg));
-        prof_begin(c, "call_prologue");
-        if (d_cons)
-            call_prologue_cons_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, c->stream>>>(
-                c->d_tbl_off.p, nv, S, c->table.p, zero_q ? c->d_qcount.p : nullptr, zero_q ? nqc : 0,
-                zero_q ? c->d_qseg.p : nullptr, nqseg, d_cons, n);
-        else
-        call_prologue_kernel<<<(unsigned)((nz + 255) / 256), 256, 0, c->stream>>>(
-            c->d_tbl_off.p, nv, S, c->table.p, zero_q ? c->d_qcount.p : nullptr, zero_q ? nqc : 0,
-            zero_q ? c->d_qseg.p : nullptr, nqseg);
-        prof_end(c);
-    }
-    for (int L = 1; L <= kmax; ++L) {
-        for (int ph = 0; ph < 2; ++ph) {
-            if (L <= Lf) {
-                if (L == 1 && ph == 0) {
-                    ScoreArgs ss = sa;
-                    ss.work = nullptr;
-                    ss.queue = nullptr;
-                    ss.qcount = nullptr;
-                    ss.hsub_out = Lf < kmax;  // layer Lf's phase 1 maxima: read only by a layer above
-                    const LdsLayout lay = lds_layout(n, nv, S, Lf, 65);
-                    if (d_cons) {
-                        const SmallConsFn cfn = small_cons_kernel(Lf);
-                        const int lds = align16(lay.total) + cons_lds;
-                        if (lds > 64 * 1024)
-                            ULG_HIP(c, hipFuncSetAttribute((const void *)cfn,
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                        prof_begin_s(c, "score_small_fused", c->stream);
-                        hipLaunchKernelGGL(cfn, dim3((unsigned)nv), dim3(kFusedThreads), (size_t)lds, c->stream, ss,
-                                           (const uint64_t *)c->d_work.p, d_cons, cons_words);
-                        prof_end_s(c, c->stream);
-                        continue;
-                    }
-                    const SmallFn kfn = small_kernel(Lf);
-                    if (lay.total > 64 * 1024)
-                        ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       lay.total));
-                    prof_begin_s(c, "score_small_fused", c->stream);
-                    hipLaunchKernelGGL(kfn, dim3((unsigned)nv), dim3(kFusedThreads), (size_t)lay.total, c->stream, ss,
-                                       (const uint64_t *)c->d_work.p);
-                    prof_end_s(c, c->stream);
-                }
-                continue;
-            }
-            if (L <= Ls) {
-                const size_t wo = ((size_t)L * 2 + ph) * (nv + 1);
-                const uint64_t cnt = work[wo + nv];
-                if (cnt == 0) continue;
-                ScoreArgs ss = sa;
-                ss.work = c->d_work.p + wo;
-                ss.queue = nullptr;
-                ss.qcount = nullptr;
-                ss.hsub_out = !(L == kmax && ph == 1);
-                const LdsLayout lay = lds_layout(n, nv, S, L, vsmall);
-                if (d_cons) {
-                    const ConsKernelFn cfn = layer_cons_kernel(L, ph, vsmall);
-                    const int lds = align16(lay.total) + cons_lds;
-                    if (lds > 64 * 1024)
-                        ULG_HIP(c, hipFuncSetAttribute((const void *)cfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                    prof_begin_s(c, kLayerNames[ph][L], c->stream);
-                    hipLaunchKernelGGL(cfn, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock), (size_t)lds,
-                                       c->stream, ss, d_cons, cons_words);
-                    prof_end_s(c, c->stream);
-                    continue;
-                }
-                const KernelFn kfn = layer_kernel(L, ph, vsmall);
-                if (lay.total > 64 * 1024)
-                    ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
-                prof_begin_s(c, kLayerNames[ph][L], c->stream);
-                hipLaunchKernelGGL(kfn, dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock), (size_t)lay.total,
-                                   c->stream, ss);
-                prof_end_s(c, c->stream);
-                continue;
-            }
-            // fork: the side streams start after the uploads / empty-set
-            // kernel / small layers
-            if (G > 1 && !forked) {
-                ULG_HIP(c, hipEventRecord(c->sync_events[0], c->stream));
-                for (int g = 1; g < G; ++g) ULG_HIP(c, hipStreamWaitEvent(gst[g], c->sync_events[0], 0));
-                forked = true;
-            }
-            if (L > kMaxL && G > 1 && c->time_limit_ms == 0 && use_pool) {
-                // The wide layers variable by variable on G host threads (one
-                // stream each): a variable's layers depend only on its own
-                // lower layers, and the long LDS replays of one variable no
-                // longer hold every other variable's next layer (the grouped
-                // form waits for each layer's slowest group).  Largest
-                // candidate sets first.
-                if ((rc = wide_pool(c, L, G, gst, nv, S, kmax, max_parents, mv, meta, work, wqwords, wslice, hoff,
-                                    nqc)))
-                    return rc;
-                break;
-            }
-            std::vector<WideGroup> wide;  // a wide layer: every group's part, staged together
-            for (int g = 0; g < G; ++g) {
-                const size_t wo = (size_t)g * (G > 1 ? wstride : 0) + ((size_t)L * 2 + ph) * (nv + 1);
-                const uint64_t cnt = h_wk[wo + nv];
-                if (cnt == 0) continue;
-                hipStream_t st = gst[g];
-                sa.work = d_wk + wo;
-                unsigned long long *qc =
-                    (variant & 16) ? c->d_qseg.p + segoff[(size_t)g * 2 * (kmax + 1) + (size_t)L * 2 + ph] : nullptr;
-                sa.queue = (variant & 16) ? c->d_queue.p + (size_t)g * qwords : nullptr;
-                sa.qcount = qc;
-                const bool bk = bucket && (L == 5 || L == 6);
-                sa.qkey = bk ? c->d_qkey.p + (size_t)g * qcap : nullptr;
-                // nothing reads the subset maxima of the top layer's second phase
-                sa.hsub_out = !(L == kmax && ph == 1);
-                const uint64_t blocks = (cnt + kBlock - 1) / kBlock;
-                if (blocks > 0x7fffffffull) return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_cbic_score: layer too large");
-                if (L > kMaxL) {
-                    WideGroup wg;
-                    wg.st = st;
-                    wg.d_work = d_wk + wo;
-                    wg.h_work = h_wk.data() + wo;
-                    wg.cnt = cnt;
-                    wg.queue = c->d_wqueue.p + g * wqwords;
-                    wg.qc = c->d_qcount.p + (size_t)g * 2 * (kmax + 1) + (L * 2 + ph);
-                    wg.scnt = c->d_scount.p + g;
-                    wg.bits = c->d_wbits.p + (size_t)g * wslice;
-                    wg.d_hmeta = hoff.empty() ? nullptr : c->d_hmeta.p + (size_t)g * (nv + (size_t)(nv + 1) * 8);
-                    wg.hq = c->d_hq.p + (size_t)g * std::max<uint64_t>(wqwords / 6, 1);
-                    wg.hqc = c->d_hqc.p + g;
-                    wide.push_back(std::move(wg));
-                    continue;
-                }
-                const LdsLayout lay = lds_layout(n, nv, S, L, variant);
-                if (d_cons) {
-                    const ConsKernelFn cfn = layer_cons_kernel(L, ph, variant);
-                    const int lds = align16(lay.total) + cons_lds;
-                    if (lds > 64 * 1024)
-                        ULG_HIP(c, hipFuncSetAttribute((const void *)cfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-                    prof_begin_s(c, kLayerNames[ph][L], st);
-                    hipLaunchKernelGGL(cfn, dim3((unsigned)blocks), dim3(kBlock), (size_t)lds, st, sa, d_cons, cons_words);
-                    prof_end_s(c, st);
-                } else {
-                const KernelFn kfn = layer_kernel(L, ph, variant);
-                if (lay.total > 64 * 1024)
-                    ULG_HIP(c, hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
-                prof_begin_s(c, kLayerNames[ph][L], st);
-                hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(kBlock), (size_t)lay.total, st, sa);
-                prof_end_s(c, st);
-                }
-                if (variant & 16) {
-                    // the undecided lanes of this launch, densely packed
-                    const int wk = sliced_k(L, cnt, (uint64_t)c->walk_small_sets, c->walk_k6);
-                    if (bk) {
-                        // counting sort of the queue by walk key, then the table's waves
-                        const uint64_t nseg = seg_count(blocks);
-                        const int kl = L == 6 ? (wk >= 8 ? 8 : 4) : (wk >= 4 ? 4 : 2);
-                        uint32_t *kbase = c->d_qoffs.p + (size_t)g * kBucketMax * nseg_max;
-                        uint32_t *sidx = c->d_qsidx.p + (size_t)g * qcap;
-                        uint32_t *qaux = c->d_qaux.p + (size_t)g * qcap;
-                        const unsigned int *hdr = reinterpret_cast<const unsigned int *>(qc + nseg * kSegStride);
-                        // the profiled walk time includes the sort (count + scatter)
-                        prof_begin_s(c, kWalkNames[ph][L], st);
-                        walk_bucket_count_kernel<<<(unsigned)((nseg + kBucketSegs - 1) / kBucketSegs), 256, 0, st>>>(
-                            qc, (uint32_t)nseg, L, sa.qkey, qaux, kbase);
-                        const uint64_t items = nseg * (kSegEntries / 256);
-                        walk_bucket_scatter_kernel<<<(unsigned)std::min<uint64_t>(items, 2048), 256, 0, st>>>(
-                            qc, qaux, kbase, (uint32_t)nseg, L, sidx);
-                        hipLaunchKernelGGL(bucket_fn(L, ph, kl), dim3((unsigned)std::min<uint64_t>(wave_cap, 4096)),
-                                           dim3(64), 0, st, (const uint64_t *)sa.queue, (const uint32_t *)sidx, hdr,
-                                           c->table.p, sa.hsub_out ? sa.hsub : nullptr, total_slots, sa.err);
-                        prof_end_s(c, st);
-                    } else if ((variant & 32) && sliced_fn(L, ph, wk)) {
-                        // one wave per (queue segment, chunk of 64 * K entries)
-                        const int kk = L == 7 ? 2 : (L == 8 ? 1 : wk);
-                        const uint64_t per = 64ull * (uint64_t)kk;
-                        const uint64_t sb = seg_count(blocks) * ((kSegEntries + per - 1) / per);
-                        if (wck && (rc = ensure(c, c->d_dump, (size_t)3 * sb))) return rc;
-                        if (wck) ULG_HIP(c, hipMemsetAsync(c->d_dump.p, 0, 24 * sb, st));
-                        prof_begin_s(c, kWalkNames[ph][L], st);
-                        hipLaunchKernelGGL(sliced_fn(L, ph, wk), dim3((unsigned)sb), dim3(64), 0, st, sa.queue, qc,
-                                           c->table.p, sa.hsub_out ? sa.hsub : nullptr, wck ? c->d_dump.p : nullptr,
-                                           total_slots, sa.err);
-                        prof_end_s(c, st);
-                        if (wck && (rc = dump_walk_clock(c, st, sb, wck, L, ph))) return rc;
-                        if (wck && std::getenv("ULG_WALK_QUEUE_DUMP") &&
-                            (rc = dump_walk_queue(c, st, sa.queue, qc, seg_count(blocks), bits_words(L), total_slots, wck, L,
-                                                  ph)))
-                            return rc;
-                    }
-                }
-            }
-            if (!wide.empty() && (rc = score_wide_groups(c, L, ph, wide, nv, S, kmax, c->d_qcount.p + nqc - 1, wslice,
-                                                         hoff, meta, c->wide_pinned)))
-                return rc;
-        }
-        if (L > kMaxL && G > 1 && c->time_limit_ms == 0 && use_pool) break;  // the pool ran every wide layer
-        if (c->time_limit_ms > 0 && L < kmax) {
-            for (int g = 0; g < (forked ? G : 1); ++g) ULG_HIP(c, hipStreamSynchronize(gst[g]));
-            const double ms =
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            if (ms > (double)c->time_limit_ms) {
-                done_L = L;
-                c->out_of_time = 1;
-                break;
-            }
-        }
-    }
-    // join: the compaction on the context stream waits for every group
-    for (int g = 1; g < G && forked; ++g) {
-        ULG_HIP(c, hipEventRecord(c->sync_events[g], gst[g]));
-        ULG_HIP(c, hipStreamWaitEvent(c->stream, c->sync_events[g], 0));
-    }
-    ULG_HIP(c, hipGetLastError());
+    int rc, done_L = kmax;
+    if ((rc = launch_prologue(k)) || (rc = launch_layers(k, done_L)) || (rc = compact(k, done_L))) return rc;
+    if (!use_graph) return ULG_OK;
+    hipGraph_t graph = nullptr;
+    capture_guard.active = false;
+    ULG_HIP(c, hipStreamEndCapture(c->stream, &graph));
+    c->graph = graph;
+    ULG_HIP(c, hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0));
+    c->gkey = gkey;
+    // the profiling events recorded inside the graph belong to it now
+    c->gprof.assign(c->pending.begin() + (std::ptrdiff_t)pend0, c->pending.end());
+    for (ProfRec &r : c->gprof) r.graph = true;
+    c->pending.resize(pend0);
+    ULG_HIP(c, hipGraphLaunch(c->gexec, c->stream));
+    for (const ProfRec &r : c->gprof) c->pending.push_back(r);
+    return ULG_OK;
+}
 
-    if (done_L < kmax) {
-        // out of time: the layers never launched hold no stored set
-        scored = 0;
-        for (int i = 0; i < nv; ++i) {
-            const uint64_t b = toff[(size_t)i * S + done_L + 1], e = toff[(size_t)i * S + S];
-            if (e > b) ULG_HIP(c, hipMemsetAsync(c->table.p + b, 0xff, (size_t)(e - b) * 4, c->stream));
-            for (int L = 0; L <= done_L; ++L) scored += (int64_t)(toff[(size_t)i * S + L + 1] - toff[(size_t)i * S + L]);
-        }
-    }
-    c->completed_layer = done_L;
-    // compaction
-    prof_begin(c, "count_stored");
-    count_kernel<<<(unsigned)nb, kBlock, 0, c->stream>>>(c->table.p, total_slots, c->d_blk.p);
-    prof_end(c);
-    prof_begin(c, "scan_stored");
-    scan_kernel<<<1, 1024, 0, c->stream>>>(c->d_blk.p, nb, c->out_offsets.p + nv, sa.err);
-    prof_end(c);
-    WriteArgs wa;
-    wa.table = c->table.p;
-    wa.blk = c->d_blk.p;
-    wa.tbl_off = c->d_tbl_off.p;
-    wa.meta = c->d_meta.p;
-    wa.cand = c->d_cand.p;
-    wa.binom = c->d_binom.p;
-    wa.binom64 = c->d_binom64.p;
-    wa.total = total_slots;
-    wa.nv = nv;
-    wa.S = S;
-    wa.sets = c->out_sets.p;
-    wa.scores = c->out_scores.p;
-    wa.offsets = c->out_offsets.p;
-    prof_begin(c, "write_stored");
-    {
-        const size_t nseg = (size_t)nv * (size_t)S;
-        const size_t toff_bytes = nseg <= (size_t)kWriteLdsSegs ? (nseg + 1) * sizeof(uint64_t) : 0;
-        write_kernel<<<(unsigned)nb, kBlock, toff_bytes, c->stream>>>(wa);
-    }
-    prof_end(c);
-    ULG_HIP(c, hipGetLastError());
-    if (use_graph) {
-        hipGraph_t graph = nullptr;
-        capture_guard.active = false;
-        ULG_HIP(c, hipStreamEndCapture(c->stream, &graph));
-        c->graph = graph;
-        ULG_HIP(c, hipGraphInstantiate(&c->gexec, graph, nullptr, nullptr, 0));
-        c->gkey = gkey;
-        // the profiling events recorded inside the graph belong to it now
-        c->gprof.assign(c->pending.begin() + (std::ptrdiff_t)pend0, c->pending.end());
-        for (ProfRec &r : c->gprof) r.graph = true;
-        c->pending.resize(pend0);
-        ULG_HIP(c, hipGraphLaunch(c->gexec, c->stream));
-        for (const ProfRec &r : c->gprof) c->pending.push_back(r);
-    }
-    }
-launched:
-    if (async && kmax <= kMaxL && c->time_limit_ms == 0) {
-        // no host sync on this path: the stored count is copied into pinned
-        // memory behind the launches and collected by ulg_cbic_score_finish
-        if (!c->async_pinned)
-            ULG_HIP(c, hipHostMalloc((void **)&c->async_pinned, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-        ULG_HIP(c, hipMemcpyAsync(c->async_pinned, c->d_blk.p + nb, 16, hipMemcpyDeviceToHost, c->stream));
-        c->nv = nv;
-        c->kmax = kmax;
-        c->vars.assign(vars, vars + nv);
-        c->m = mv;
-        c->tbl_off = toff;
-        c->total_slots = (int64_t)total_slots;
-        c->total_stored = 0;
-        c->total_scored = scored;
-        c->scored = true;
-        c->async_pending = true;
-        return ULG_OK;
-    }
-    // the stored count and the error word through the context's pinned words
-    // (a pageable destination goes through a staging copy)
+// The stored count and the error word through the context's pinned words (a
+// pageable destination goes through a staging copy), and the call's lists
+// into the context.  Async: no host sync; ulg_cbic_score_finish collects the
+// words once the launches are done.
+int collect(ulg_ctx *c, const ScoreLists &ls, int64_t nb, bool async, int64_t *total_stored, int64_t *total_scored) {
     if (!c->async_pinned)
         ULG_HIP(c, hipHostMalloc((void **)&c->async_pinned, 2 * sizeof(unsigned long long), hipHostMallocDefault));
     ULG_HIP(c, hipMemcpyAsync(c->async_pinned, c->d_blk.p + nb, 16, hipMemcpyDeviceToHost, c->stream));
-    ULG_HIP(c, hipStreamSynchronize(c->stream));
-    const uint64_t stored = c->async_pinned[0];
-    prof_collect(c);
-    if ((rc = call_error(c, c->async_pinned[1]))) return rc;
-
-    c->nv = nv;
-    c->kmax = kmax;
-    c->vars.assign(vars, vars + nv);
-    c->m = mv;
-    c->tbl_off = toff;
-    c->total_slots = (int64_t)total_slots;
-    c->total_stored = (int64_t)stored;
-    c->total_scored = scored;
-    c->scored = true;
-    if (total_stored) *total_stored = (int64_t)stored;
-    if (total_scored) *total_scored = scored;
+    int64_t stored = 0;
+    if (!async) {
+        ULG_HIP(c, hipStreamSynchronize(c->stream));
+        stored = (int64_t)c->async_pinned[0];
+        prof_collect(c);
+        if (int rc = call_error(c, c->async_pinned[1])) return rc;
+    }
+    publish(c, ls, stored, async);
+    if (total_stored) *total_stored = c->total_stored;
+    if (total_scored) *total_scored = c->total_scored;
     return ULG_OK;
+}
+
+int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
+               int64_t *total_stored, int64_t *total_scored, bool async) {
+    if (!c) return ULG_ERR_ARG;
+    if (int rc0 = finish_pending(c)) return rc0;
+    if (!c->loaded) return set_err(c, ULG_ERR_STATE, "ulg_cbic_score: call ulg_cbic_load first");
+    ScoreLists &ls = c->lists;
+    CbicPlan &p = c->plan;
+    if (ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents))
+        return lists_error(c, "ulg_cbic_score", st);
+    ULG_HIP(c, hipSetDevice(c->device));
+    CbicOptions o;
+    o.score_variant = c->score_variant;
+    o.score_streams = c->score_streams;
+    o.score_small_layers = c->score_small_layers;
+    o.score_fused = c->score_fused;
+    o.walk_bucket = c->walk_bucket;
+    o.wide_prune = c->wide_prune;
+    o.wide_pool = c->wide_pool;
+    o.time_limit_ms = c->time_limit_ms;
+    const char *wck = std::getenv("ULG_WALK_CLOCK");
+    o.wck = wck != nullptr;
+    p.build(ls, c->cons_var, c->cons_req, c->cons_forb, o);
+    if (int rc = reserve_buffers(c, ls, p)) return rc;
+
+    ScoreCall k{c, ls, p, ConsTable{p.cons_words ? c->d_cons.p : nullptr, p.cons_words, p.cons_lds}, ScoreArgs{},
+                p.G > 1 ? c->d_workg.p : c->d_work.p, std::vector<hipStream_t>(p.G), wck};
+    k.gst[0] = c->stream;
+    for (int g = 1; g < p.G; ++g) k.gst[g] = c->aux_streams[g - 1];
+    ScoreArgs &sa = k.sa;  // work, queue, qcount and qkey stay null: each launch sets its own
+    sa.hsub_out = 1;
+    sa.gram = c->gram.p;
+    sa.binom = c->d_binom.p;
+    sa.cand = c->d_cand.p;
+    sa.meta = c->d_meta.p;
+    sa.tbl_off = c->d_tbl_off.p;
+    sa.table = c->table.p;
+    sa.hsub = (p.variant & 64) ? c->d_hsub.p : nullptr;
+    sa.err = k.errf();
+    sa.N = (double)c->N;
+    sa.lambda = c->lambda;
+    sa.n = ls.n;
+    sa.nv = ls.nv;
+    sa.S = ls.S;
+    sa.xcd = c->score_xcd;
+    if (int rc = launch_call(k, candidates)) return rc;
+    return collect(c, ls, p.nb, async && p.kmax <= kMaxL && c->time_limit_ms == 0, total_stored, total_scored);
+}
+
+}  // namespace
+
+int ulg_cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents,
+                   int64_t *total_stored, int64_t *total_scored) {
+    return cbic_score(c, vars, nv, candidates, max_parents, total_stored, total_scored, false);
+}
+
+int ulg_cbic_score_async(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, int max_parents) {
+    return cbic_score(c, vars, nv, candidates, max_parents, nullptr, nullptr, true);
 }
 
 int ulg_cbic_fetch(ulg_ctx *c, uint64_t *sets, float *scores, int64_t *offsets, int device_ptrs) {
     if (!c) return ULG_ERR_ARG;
-    if (c->async_pending) {
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;
     if (!c->scored) return set_err(c, ULG_ERR_STATE, "ulg_cbic_fetch: nothing scored");
     ULG_HIP(c, hipSetDevice(c->device));
     const hipMemcpyKind k = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
@@ -3487,10 +3241,7 @@ int ulg_cbic_set_constraints(ulg_ctx *c, int count, const int *vars, const uint6
                            "ulg_cbic_set_constraints: more than ULG_MAX_CONSTRAINT_ALTERNATIVES (64) alternatives "
                            "for variable " + std::to_string(vars[i]));
     }
-    if (c->async_pending) {  // the launches in flight read the tables
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;  // the launches in flight read the tables
     ULG_HIP(c, hipSetDevice(c->device));
     // the captured scoring graph holds the kernels and the table pointer of
     // the constraints it was captured under
@@ -3545,14 +3296,15 @@ int ulg_cbic_score_sets(ulg_ctx *c, int64_t count, const int *vars, const uint64
     int rc;
     if ((rc = ensure(c, c->d_sets_in, (size_t)count * 2)) || (rc = ensure(c, c->qbuf_out, (size_t)count))) return rc;
     ULG_HIP(c, hipMemcpyAsync(c->d_sets_in.p, pairs.data(), (size_t)count * 16, hipMemcpyHostToDevice, c->stream));
-    prof_begin(c, "score_sets");
-    if (!c->cons_var.empty())
-        score_sets_cons_kernel<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, (size_t)n * n * 8, c->stream>>>(
-            c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p, c->d_cons_var.p);
-    else
-    score_sets_kernel<<<(unsigned)((count + kBlock - 1) / kBlock), kBlock, (size_t)n * n * 8, c->stream>>>(
-        c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p);
-    prof_end(c);
+    // the twin takes the by-variable table (ulg_cbic_set_constraints) after the common arguments
+    const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
+    if ((rc = c->cons_var.empty()
+                  ? launch_kernel(c, score_sets_kernel, grid, block, n * n * 8, c->stream, "score_sets", c->gram.p,
+                                  c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p)
+                  : launch_kernel(c, score_sets_cons_kernel, grid, block, n * n * 8, c->stream, "score_sets",
+                                  c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p,
+                                  c->d_cons_var.p)))
+        return rc;
     ULG_HIP(c, hipMemcpyAsync(neg_scores, c->qbuf_out.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);

@@ -16,7 +16,7 @@ namespace {
 
 using namespace ulg;
 
-constexpr int kBlock = 256;
+// kBlock and the queue / table sizing constants: score_plan.h
 
 // How a kernel loads slab values written by other workgroups: every writer
 // of a slab is an earlier launch on the same stream (a layer is complete
@@ -325,8 +325,7 @@ __device__ __forceinline__ void presence_unrolled(Bits<W> &present, Bits<W> &hi,
     }
 }
 
-// bitset words per lane over the subsets of L + 1 local bits
-__host__ __device__ constexpr int bits_words(int L) { return (L + 1) <= 6 ? 1 : (1 << ((L + 1) - 6)); }
+// bitset words per lane over the subsets of L + 1 local bits: bits_words(L), score_plan.h
 
 template <class BS>
 __device__ __forceinline__ BS make_bits(uint64_t *lds_base) {

@@ -442,10 +442,7 @@ int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int 
         return set_err(c, ULG_ERR_ARG, "ulg_disc_load: bad arguments");
     for (int j = 0; j < n; ++j)
         if (arity[j] < 1 || arity[j] > 255) return set_err(c, ULG_ERR_ARG, "ulg_disc_load: arity must be 1..255");
-    if (c->async_pending) {
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;
     ULG_HIP(c, hipSetDevice(c->device));
     int rc;
     if ((rc = ensure(c, c->d_codes, (size_t)(N * n))) || (rc = ensure(c, c->d_disc_word, 4))) return rc;
@@ -488,40 +485,21 @@ int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int 
 int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t *candidates, int max_parents,
                    int64_t *total_stored, int64_t *total_scored) {
     if (!c) return ULG_ERR_ARG;
-    if (c->async_pending) {
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score: call ulg_disc_load first");
     if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC");
-    if (!vars || !candidates || nv < 1 || nv > c->n) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: bad variable list");
-    const int n = c->n;
-    uint64_t seen = 0;
-    for (int i = 0; i < nv; ++i) {
-        if (vars[i] < 0 || vars[i] >= n || ((seen >> vars[i]) & 1ull))
-            return set_err(c, ULG_ERR_ARG, "ulg_disc_score: variables must be distinct and < n");
-        seen |= 1ull << vars[i];
-    }
-    const uint64_t allmask = (1ull << n) - 1ull;
-    if (max_parents < 1 || max_parents > n - 1) max_parents = n - 1;
-    std::vector<uint8_t> cand((size_t)nv * 64, 0);
-    std::vector<int> vm((size_t)nv * 2, 0), mv(nv);
-    int kmax = 0;
+    ScoreLists &ls = c->lists;
+    const ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents);
+    if (st != ScoreLists::kOk && st != ScoreLists::kTooWide) return lists_error(c, "ulg_disc_score", st);
+    std::vector<int> vm((size_t)nv * 2, 0);
     uint64_t max_cells = 0;
     for (int i = 0; i < nv; ++i) {
-        const uint64_t C = candidates[i] & allmask & ~(1ull << vars[i]);
-        int m = 0;
-        std::vector<int> ar;
-        for (int b = 0; b < n; ++b)
-            if ((C >> b) & 1ull) {
-                cand[(size_t)i * 64 + m++] = (uint8_t)b;
-                ar.push_back(c->disc_arity[b]);
-            }
-        mv[i] = m;
+        const int m = ls.mv[i];
+        std::vector<int> ar(m);
+        for (int j = 0; j < m; ++j) ar[j] = c->disc_arity[ls.cand[(size_t)i * 64 + j]];
         vm[2 * i] = vars[i];
         vm[2 * i + 1] = m;
-        const int k = std::min(m, max_parents);
-        kmax = std::max(kmax, k);
+        const int k = std::min(m, ls.max_parents);
         // the variable's largest table: its k candidates of largest arity
         std::sort(ar.begin(), ar.end(), std::greater<int>());
         unsigned __int128 cells = (unsigned)c->disc_arity[vars[i]];
@@ -530,26 +508,19 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_disc_score: a contingency table of 2^63 cells or more");
         if (c->disc_arity[vars[i]] > 1) max_cells = std::max(max_cells, (uint64_t)cells);
     }
-    if (kmax > kWideMax)
-        return set_err(c, ULG_ERR_UNSUPPORTED,
-                       "ulg_disc_score: parent sets larger than ULG_MAX_PARENTS_GPU (31) are not supported");
-    const int S = kmax + 1;
+    if (st != ScoreLists::kOk) return lists_error(c, "ulg_disc_score", st);
+    const int kmax = ls.kmax, S = ls.S;
+    const uint64_t total_slots = ls.total_slots;
+    const std::vector<uint8_t> &cand = ls.cand;
     // [toff: nv * S + 1][work: S x (nv + 1)]
     std::vector<uint64_t> meta((size_t)nv * S + 1 + (size_t)S * (nv + 1), 0);
-    uint64_t *toff = meta.data(), *work = meta.data() + (size_t)nv * S + 1;
-    uint64_t acc = 0;
-    for (int i = 0; i < nv; ++i)
-        for (int L = 0; L < S; ++L) {
-            toff[(size_t)i * S + L] = acc;
-            acc += L <= std::min(mv[i], max_parents) ? binom64(mv[i], L) : 0;
-        }
-    toff[(size_t)nv * S] = acc;
-    const uint64_t total_slots = acc;
+    std::copy(ls.toff.begin(), ls.toff.end(), meta.begin());
+    uint64_t *work = meta.data() + (size_t)nv * S + 1;
     for (int L = 0; L < S; ++L) {
         uint64_t s = 0;
         for (int i = 0; i < nv; ++i) {
             work[(size_t)L * (nv + 1) + i] = s;
-            s += toff[(size_t)i * S + L + 1] - toff[(size_t)i * S + L];
+            s += ls.slab_count(i, L);
         }
         work[(size_t)L * (nv + 1) + nv] = s;
     }
@@ -612,9 +583,6 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             }
         }
     }
-    int64_t scored = 0;
-    for (int i = 0; i < nv; ++i)
-        for (int L = 0; L <= done_L; ++L) scored += (int64_t)(toff[(size_t)i * S + L + 1] - toff[(size_t)i * S + L]);
     c->completed_layer = done_L;
     if ((rc = ensure(c, c->out_sets, total_slots)) || (rc = ensure(c, c->out_scores, total_slots)) ||
         (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
@@ -635,17 +603,9 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     c->last_err_word = 0;
     c->disc_path_sets[0] = (int64_t)word[1];
     c->disc_path_sets[1] = (int64_t)word[2];
-    c->nv = nv;
-    c->kmax = kmax;
-    c->vars.assign(vars, vars + nv);
-    c->m = mv;
-    c->tbl_off.assign(toff, toff + (size_t)nv * S + 1);
-    c->total_slots = (int64_t)total_slots;
-    c->total_stored = (int64_t)word[3];
-    c->total_scored = scored;
-    c->scored = true;
+    publish(c, ls, (int64_t)word[3], false);
     if (total_stored) *total_stored = c->total_stored;
-    if (total_scored) *total_scored = scored;
+    if (total_scored) *total_scored = c->total_scored;
     return ULG_OK;
 }
 
@@ -695,10 +655,7 @@ static int disc_sets_launch(ulg_ctx *c, const char *what, int64_t count, const i
 int ulg_disc_score_sets(ulg_ctx *c, int kind, int64_t count, const int *vars, const uint64_t *parents,
                         float *scores) {
     if (!c || count < 0 || (count > 0 && (!vars || !parents || !scores))) return ULG_ERR_ARG;
-    if (c->async_pending) {
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score_sets: call ulg_disc_load first");
     if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC");
     if (count == 0) return ULG_OK;
@@ -711,10 +668,7 @@ int ulg_disc_score_sets(ulg_ctx *c, int kind, int64_t count, const int *vars, co
 
 int ulg_disc_counts(ulg_ctx *c, int var, uint64_t parents, int32_t *counts, int64_t cap, int64_t *ncells) {
     if (!c || !counts || !ncells) return ULG_ERR_ARG;
-    if (c->async_pending) {
-        int rc0 = ulg_cbic_score_finish(c, nullptr, nullptr);
-        if (rc0) return rc0;
-    }
+    if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_counts: call ulg_disc_load first");
     if (var < 0 || var >= c->n || (parents >> c->n)) return set_err(c, ULG_ERR_ARG, "ulg_disc_counts: bad variable or parents");
     const uint64_t P = parents & ~(1ull << var);

@@ -39,14 +39,6 @@ const std::vector<uint64_t> &host_binom64() {
     return t;
 }
 
-uint64_t binom64(int a, int b) {
-    if (b < 0 || b > a) return 0;
-    if (b > a - b) b = a - b;
-    unsigned __int128 r = 1;
-    for (int i = 1; i <= b; ++i) r = r * (unsigned)(a - b + i) / (unsigned)i;
-    return r > ~0ull ? ~0ull : (uint64_t)r;
-}
-
 void prof_begin(ulg_ctx *c, const char *name) { prof_begin_s(c, name, c->stream); }
 void prof_end(ulg_ctx *c) { prof_end_s(c, c->stream); }
 

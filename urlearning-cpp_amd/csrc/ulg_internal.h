@@ -12,12 +12,10 @@
 #include <vector>
 
 #include "../../include/ulg.h"
+#include "score_plan.h"  // kMaxVars, kMaxL, kWideMax, binom64, ScoreLists, CbicPlan
 
 namespace ulg {
 
-constexpr int kMaxVars = 63;               // varset = uint64, bit 63 kept free
-constexpr int kMaxL = ULG_UNROLLED_PARENTS_GPU;  // unrolled layers on the device
-constexpr int kWideMax = ULG_MAX_PARENTS_GPU;   // wide layers kMaxL+1 .. kWideMax (cbic.hip)
 constexpr int kBinomK = kMaxL + 2;          // binomial table columns C(a, 0..kBinomK-1)
 constexpr uint32_t kAbsentBits = 0xFFFFFFFFu;  // "not in the FloatMap" sentinel (a NaN payload)
 
@@ -60,6 +58,8 @@ struct ulg_ctx {
     ulg::DevBuf<double> raw, z, gram, partials, colstat;
 
     // ---- scoring state ----
+    ulg::ScoreLists lists;  // the scoring call being prepared (published into the fields below when it is launched)
+    ulg::CbicPlan plan;     // ... and ulg_cbic_score's plan for it; both keep their vectors' capacity across calls
     int nv = 0;
     int kmax = 0;
     std::vector<int> vars;
@@ -201,8 +201,9 @@ int ensure(ulg_ctx *c, DevBuf<T> &b, size_t elems) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
-    // 16 bytes of slack: kernels copy whole 16-byte chunks (fill_lds), so the
-    // last chunk of an array may read up to 15 bytes past its end
+    // 16 bytes of slack: kernels read whole 16-byte chunks (the uint4 key
+    // loads of walk_bucket_count_kernel, cbic.hip), so the last chunk of an
+    // array may read up to 15 bytes past its end
     hipError_t e = hipMalloc(&b.p, elems * sizeof(T) + 16);
     if (e != hipSuccess)
         return set_err(c, ULG_ERR_HIP, std::string("hipMalloc failed: ") + hipGetErrorString(e));
@@ -243,6 +244,30 @@ void pss_release(ulg_ctx *c);    // pss.hip
 const std::vector<uint32_t> &host_binom();
 // C(a, b) for a, b < 64 (saturating at 2^64 - 1), [a * 64 + b]
 const std::vector<uint64_t> &host_binom64();
-uint64_t binom64(int a, int b);
+
+// An async scoring call's launches still own the buffers and the lists: every
+// entry point that reads or replaces them collects that call first.
+inline int finish_pending(ulg_ctx *c) {
+    return c->async_pending ? ulg_cbic_score_finish(c, nullptr, nullptr) : ULG_OK;
+}
+// ScoreLists::build's refusal as the status and message of ABI function `who`
+inline int lists_error(ulg_ctx *c, const char *who, ScoreLists::Status st) {
+    return set_err(c, st == ScoreLists::kTooWide ? ULG_ERR_UNSUPPORTED : ULG_ERR_ARG,
+                   std::string(who) + ScoreLists::status_text(st));
+}
+// A launched scoring call's lists become the context's (ulg_cbic_fetch, the
+// search and the .pss writer read them); completed_layer names its last layer.
+inline void publish(ulg_ctx *c, const ScoreLists &ls, int64_t stored, bool async_pending) {
+    c->nv = ls.nv;
+    c->kmax = ls.kmax;
+    c->vars = ls.vars;
+    c->m = ls.mv;
+    c->tbl_off = ls.toff;
+    c->total_slots = (int64_t)ls.total_slots;
+    c->total_stored = stored;
+    c->total_scored = ls.scored_up_to(c->completed_layer);
+    c->scored = true;
+    c->async_pending = async_pending;
+}
 
 }  // namespace ulg

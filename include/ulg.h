@@ -224,6 +224,42 @@ int ulg_disc_score_sets(ulg_ctx *ctx, int kind, int64_t count, const int *vars,
  * ULG_ERR_ARG if cap is smaller. */
 int ulg_disc_counts(ulg_ctx *ctx, int var, uint64_t parents, int32_t *counts, int64_t cap, int64_t *ncells);
 
+/* ---- discrete skeleton: G^2 tests and MMPC (no reference counterpart) ---- */
+/* ln of the chi-square survival function: ln P(chi2_dof >= x), pure host FP64,
+ * no context.  x <= 0 gives 0.  Computed in log space (the series of the lower
+ * tail below x/2 = dof/2 + 1, a Lentz continued fraction of the upper tail
+ * above), so it stays finite where the probability underflows; valid for dof
+ * up to 32768 and x up to 1e7.  dof = 2 gives -x/2. */
+double ulg_chi2_log_sf(double x, double dof);
+/* The raw statistics of count conditional-independence tests of xs[i] and
+ * ts[i] given the variables in conds[i] (a mask) on the loaded value codes,
+ * whether the MMPC below would call them reliable or not:
+ *   cells[i] = q r_x r_t, q = prod_{s in conds} r_s;  dof[i] = (r_x - 1)(r_t - 1) q
+ *   (both saturate at INT64_MAX);
+ *   g2[i] = 2 [sum n_xtz ln n_xtz + sum n_z ln n_z - sum n_xz ln n_xz - sum n_tz ln n_tz],
+ *   clamped at 0, empty cells contributing nothing; NaN where cells > 32768 (the
+ *   table is counted in a 128 KB LDS histogram).
+ * Each n ln n term is accumulated as a fixed-point integer (as ulg_disc_score's),
+ * so g2 does not depend on scheduling, on the other tests of the call or on
+ * their order.  ULG_ERR_ARG for x = t, for x or t in conds and for an index or
+ * a mask bit out of range; ULG_ERR_STATE without discrete data.  The context's
+ * lists stay as they are. */
+int ulg_disc_g2(ulg_ctx *ctx, int64_t count, const int *xs, const int *ts, const uint64_t *conds,
+                double *g2, int64_t *dof, int64_t *cells);
+/* ulg_mmpc for the value codes of ulg_disc_load: MMPC with G^2 tests, rows as
+ * ulg_mmpc returns them.  A test (X, T | S) is performed iff N >= min_per_cell
+ * cells and cells <= 32768 (the heuristic power rule; a test not performed
+ * contributes nothing, a pair whose marginal test is not performed is never a
+ * candidate); its association is -ln p = -ulg_chi2_log_sf(G^2, dof), 0 for
+ * dof = 0; X and T are independent given S iff that is <= -ln alpha.  Rounds,
+ * tie-breaks and the AND rule as ulg_mmpc; max_cond < 0 or > 24 means 24; a
+ * candidate set of more than 24 is ULG_ERR_UNSUPPORTED.  One launch per round,
+ * one workgroup per test.  Exact rules: csrc/disc_mmpc.hip.  ULG_ERR_ARG for
+ * alpha outside (0, 1) or min_per_cell < 1, ULG_ERR_STATE without discrete
+ * data; the context's lists stay as they are.  ulg_get_info("disc_mmpc_tests")
+ * and ("disc_mmpc_skipped") count the last call's tests performed and left out. */
+int ulg_disc_mmpc(ulg_ctx *ctx, double alpha, int max_cond, int min_per_cell, uint64_t *rows);
+
 /* The .pss "%f" + atof round trip the A* input goes through
  * (score_main.cpp:191, score_cache.cpp:151), computed exactly on the
  * device: cost = float(-1 * strtod(printf("%f", score))). */
@@ -460,7 +496,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * "exact_cache_misses" (the last exact-order A*'s user-space host counters on
  * the calling thread, perf_event_open; -1 where the host does not grant
  * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
- * counted on each path), "score_error_word" (the last scoring call's device error word: 0,
+ * counted on each path), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
+ * ulg_disc_mmpc performed / left out by its reliability rule), "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero
  * word also made that call return a nonzero status). */

@@ -27,6 +27,8 @@
 #               VARS, default 23, ULG_WALK_STATS) for c4_replay_summary.py
 #   exact       scripts/probe_exact.py c3 per ULG_EXACT_PF mode in PF_MODES
 #               (default "6"), two alternating rounds -> exact_<mode>_<rep>.json
+#   disc_mmpc   scripts/disc_mmpc_profile.py (discrete MMPC, n = 30,
+#               N = 100k)                                     -> disc_mmpc.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -132,6 +134,9 @@ for step in ${STEPS:-suite smoke bench}; do
         ULG_EXACT_PF=$pf timeout -k 10 240 python3 scripts/probe_exact.py c3 > "$OUT/exact_${pf}_$rep.json" 2> "$OUT/exact_${pf}_$rep.err"
         echo "exact pf=$pf rep=$rep $(cat "$OUT/exact_${pf}_$rep.json")"
       done; done ;;
+    disc_mmpc)
+      timeout -k 10 300 python3 scripts/disc_mmpc_profile.py "$OUT/disc_mmpc.json" > "$OUT/disc_mmpc.log" 2>&1
+      tail -n 1 "$OUT/disc_mmpc.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

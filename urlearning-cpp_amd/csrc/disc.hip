@@ -25,6 +25,7 @@
 #include <chrono>
 #include <cmath>
 
+#include "disc_dev.h"  // DiscData, fix_nlogn, disc_ready, disc_data
 #include "ulg_internal.h"
 
 using namespace ulg;
@@ -38,15 +39,6 @@ constexpr int kHashLdsSlots = 8192;                 // 8192 x 12 B = 96 KB of th
 constexpr int kScanPerThread = 8;
 constexpr int kScanPerBlock = kDiscBlock * kScanPerThread;
 constexpr unsigned long long kErrCode = 1ull;       // a value code >= its column's arity
-
-struct DiscData {
-    const uint8_t *codes;  // [n][N]
-    int64_t N;
-    int n;
-    int shift;             // fixed point: 2^-shift
-    double half_ln_N;
-    uint8_t arity[64];
-};
 
 struct DiscWork {
     unsigned long long *slab;  // sparse path in HBM: hslots keys, then hslots uint32 counts, per workgroup
@@ -72,12 +64,6 @@ __device__ __forceinline__ bool disc_violates(const uint64_t *ct, int n, int v, 
     for (uint64_t i = 0; i < e - b; ++i)
         if ((p[2 * i] & ~set) == 0 && (p[2 * i + 1] & set) == 0) return false;
     return true;
-}
-
-// fix(n ln n): zero cells contribute nothing (ilogi[0] = 0), and 1 ln 1 = 0
-__device__ __forceinline__ long long fix_nlogn(unsigned int n, int shift) {
-    if (n <= 1u) return 0;
-    return __double2ll_rn(ldexp((double)n * log((double)n), shift));
 }
 
 // Thread 0: the item's parents (ascending variable order), bases and table
@@ -380,22 +366,6 @@ __global__ void disc_offsets_kernel(const float *table, const uint64_t *toff, in
 }
 
 // ---- host ----------------------------------------------------------------------
-bool disc_ready(const ulg_ctx *c) { return c->disc_loaded && !c->loaded; }
-
-DiscData disc_data(const ulg_ctx *c) {
-    DiscData D{};
-    D.codes = c->d_codes.p;
-    D.N = c->N;
-    D.n = c->n;
-    // the largest power-of-two scale at which N ln N stays below 2^62, at most 2^32
-    int ex = 0;
-    (void)std::frexp((double)c->N * std::log((double)c->N), &ex);  // N ln N < 2^ex
-    D.shift = std::min(32, 62 - ex);
-    D.half_ln_N = std::log((double)c->N) / 2.0;
-    for (int j = 0; j < c->n; ++j) D.arity[j] = (uint8_t)c->disc_arity[j];
-    return D;
-}
-
 // q r_v of (v, parents), or 2^63 where it does not fit
 uint64_t table_cells(const ulg_ctx *c, int v, uint64_t parents) {
     unsigned __int128 cells = (unsigned)c->disc_arity[v];

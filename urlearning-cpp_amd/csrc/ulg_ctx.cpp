@@ -164,6 +164,7 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
     release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
     release(c->d_disc_table); release(c->d_disc_blk);
+    release(c->d_g2_tests); release(c->d_g2_out);
     pss_release(c);
     if (c->search) {
         c->search->release_all();
@@ -319,6 +320,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table
     if (std::strcmp(name, "disc_dense_sets") == 0 || std::strcmp(name, "disc_sparse_sets") == 0) {
         *value = c->disc_path_sets[name[5] == 's' ? 1 : 0];
+        return ULG_OK;
+    }
+    // the last ulg_disc_mmpc: G^2 tests performed / left out by the reliability rule
+    if (std::strcmp(name, "disc_mmpc_tests") == 0 || std::strcmp(name, "disc_mmpc_skipped") == 0) {
+        *value = c->disc_mmpc_stat[name[10] == 's' ? 1 : 0];
         return ULG_OK;
     }
     // alternatives held by ulg_cbic_set_constraints

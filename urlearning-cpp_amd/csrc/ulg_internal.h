@@ -146,6 +146,10 @@ struct ulg_ctx {
     ulg::DevBuf<unsigned long long> d_disc_slab;  // sparse path: per-workgroup hash tables
     ulg::DevBuf<unsigned long long> d_disc_word;  // [error word, dense sets, sparse sets, stored]
     ulg::DevBuf<int32_t> d_disc_counts;           // ulg_disc_counts' table
+    // ---- discrete G^2 tests and MMPC (disc_mmpc.hip) ----
+    ulg::DevBuf<uint64_t> d_g2_tests;             // per test: (x, t), conditioning mask
+    ulg::DevBuf<unsigned long long> d_g2_out;     // per test: the fixed-point sum
+    int64_t disc_mmpc_stat[2] = {0, 0};           // last ulg_disc_mmpc: tests performed / skipped
 
     ulg::DevBuf<float> qbuf_in, qbuf_out;
     ulg::DevBuf<uint64_t> d_sets_in;              // ulg_cbic_score_sets: (variable, parent mask) pairs

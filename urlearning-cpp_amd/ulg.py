@@ -49,6 +49,10 @@ def lib():
         L.ulg_disc_score.argtypes = [P, I, P, I, P, I, C.POINTER(I64), C.POINTER(I64)]
         L.ulg_disc_score_sets.argtypes = [P, I, I64, P, P, P]
         L.ulg_disc_counts.argtypes = [P, I, C.c_uint64, P, I64, C.POINTER(I64)]
+        L.ulg_chi2_log_sf.argtypes = [D, D]
+        L.ulg_chi2_log_sf.restype = D
+        L.ulg_disc_g2.argtypes = [P, I64, P, P, P, P, P, P]
+        L.ulg_disc_mmpc.argtypes = [P, D, I, I, P]
         L.ulg_quantize_costs.argtypes = [P, P, P, I64]
         L.ulg_search_load.argtypes = [P, I, P, P, P]
         L.ulg_search_from_scores.argtypes = [P]
@@ -90,6 +94,11 @@ def header_symbols():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def chi2_log_sf(x: float, dof: float) -> float:
+    """ulg_chi2_log_sf: ln of the chi-square survival function (pure host, no GPU)."""
+    return lib().ulg_chi2_log_sf(float(x), float(dof))
 
 
 class Context:
@@ -271,6 +280,28 @@ class Context:
         self._check(lib().ulg_disc_counts(self._h, int(variable), C.c_uint64(int(parents)), _ptr(out), int(cap),
                                           C.byref(nc)), "ulg_disc_counts")
         return out[:nc.value]
+
+    def g2_discrete(self, xs, ts, conds):
+        """ulg_disc_g2: the G^2 statistic of each test (xs[i], ts[i] | conds[i] as a mask)
+        -> (g2 float64, dof int64, cells int64); g2 is NaN where cells > 32768."""
+        x = np.ascontiguousarray(xs, dtype=np.int32)
+        t = np.ascontiguousarray(ts, dtype=np.int32)
+        s = np.ascontiguousarray([int(m) for m in conds], dtype=np.uint64)
+        if not (x.shape == t.shape == s.shape):
+            raise ValueError("g2_discrete: xs, ts and conds differ in length")
+        g2 = np.zeros(max(len(x), 1), dtype=np.float64)
+        dof = np.zeros(max(len(x), 1), dtype=np.int64)
+        cells = np.zeros(max(len(x), 1), dtype=np.int64)
+        self._check(lib().ulg_disc_g2(self._h, len(x), _ptr(x), _ptr(t), _ptr(s), _ptr(g2), _ptr(dof), _ptr(cells)),
+                    "ulg_disc_g2")
+        return g2[:len(x)], dof[:len(x)], cells[:len(x)]
+
+    def mmpc_discrete(self, alpha=0.05, max_cond=-1, min_per_cell=5):
+        """ulg_disc_mmpc on the loaded value codes -> skeleton rows (bit j of row i = edge i-j)."""
+        rows = np.zeros(64, dtype=np.uint64)
+        self._check(lib().ulg_disc_mmpc(self._h, float(alpha), int(max_cond), int(min_per_cell), _ptr(rows)),
+                    "ulg_disc_mmpc")
+        return [int(x) for x in rows[:self.n]]
 
     def quantize(self, scores: np.ndarray) -> np.ndarray:
         s = np.ascontiguousarray(scores, dtype=np.float32)
@@ -458,7 +489,8 @@ class Context:
 
     def info(self, name: str) -> int:
         """ulg_get_info: "out_of_time", "highest_completed_layer", "score_error_word",
-        "exact_cycles", "exact_instructions", "exact_cache_misses"."""
+        "exact_cycles", "exact_instructions", "exact_cache_misses", "disc_mmpc_tests",
+        "disc_mmpc_skipped"."""
         v = C.c_int64()
         self._check(lib().ulg_get_info(self._h, name.encode(), C.byref(v)), "ulg_get_info")
         return v.value

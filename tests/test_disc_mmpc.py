@@ -259,6 +259,24 @@ def dense(N, seed):
     return codes
 
 
+ARITY36 = [(2, 3, 2, 4, 3, 2)[j % 6] for j in range(36)]
+
+
+def wide36(N, seed):
+    """syn6's chain (each column follows its left neighbour with probability 0.4) in the columns 31 to
+    35 of 36; the columns 0 to 30 are independent.  Every decision that matters sits on bits >= 31."""
+    rng = np.random.default_rng(seed)
+    codes = np.zeros((N, 36), dtype=np.uint8)
+    for j in range(36):
+        col = rng.integers(0, ARITY36[j], size=N)
+        if j >= 31:
+            col = np.where(rng.random(N) < 0.4, codes[:, j - 1] % ARITY36[j], col)
+        codes[:, j] = col
+    for j in range(36):
+        codes[:ARITY36[j], j] = np.arange(ARITY36[j])
+    return codes
+
+
 def hepatitis():
     rows = [ln.strip().split(",") for ln in open(HEP).read().splitlines()][1:]
     maps = [dict() for _ in rows[0]]
@@ -269,7 +287,7 @@ def hepatitis():
 
 INPUTS = ([f"syn6-N{N}-s{s}" for N, seeds in ((64, (1, 2, 3)), (300, (1, 2, 3, 4, 5)), (2500, (1, 2, 3, 4, 5)))
            for s in seeds] + ["const8-N2500-s1"] +
-          [f"dense8-N{N}-s{s}" for N in (2500, 300) for s in (1, 2, 3, 4)] + ["hepatitis"])
+          [f"dense8-N{N}-s{s}" for N in (2500, 300) for s in (1, 2, 3, 4)] + ["hepatitis", "wide36-N1000-s1"])
 ALPHAS = (0.05, 0.01)
 MAX_CONDS = (-1, 0, 1, 3)
 MIN_PER_CELL = (5, 1)
@@ -287,6 +305,8 @@ def input_case(name):
             codes, arity = synthetic(6, N, ARITY6, s), ARITY6
         elif kind == "const8":
             codes, arity = synthetic(8, N, ARITY8C, s), ARITY8C
+        elif kind == "wide36":
+            codes, arity = wide36(N, s), ARITY36
         else:
             codes, arity = dense(N, s), ARITY8D
     codes.setflags(write=False)

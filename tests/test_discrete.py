@@ -14,7 +14,46 @@ Tolerance.  Any order of T float additions of terms x_i is within
 (T + 2) 2^-24 sum|x_i| of the exact sum; the bound counts one more rounding for
 each table entry and for the penalty product.  Per set
     B = (T + 2) 2^-24 (sum_cells n ln n + sum_j n_j ln n_j + t ln(N) / 2) + ulp_float(|score|)
-with T = the number of terms added or subtracted."""
+with T = the number of terms added or subtracted.
+
+The kernel's own bound.  B is the error of the reference's float32 summation.
+The kernel promises more: the exactly summed FP64 value, rounded to float once
+(csrc/disc_dev.h, item_value in csrc/disc.hip).  exact_value() below restates
+that value without walking the cells (numpy.unique on the 64-bit cell index,
+math.fsum), so it also serves tables far too large to enumerate, and returns
+(exact64, T, A): the value, the number T of n ln n terms (non-empty cells plus
+non-empty parent configurations) and A = sum |n ln n|.  With pen =
+(r_v - 1) q ln(N) / 2 the kernel's float differs from exact64 by at most
+    Bk = ulp_f32(exact64) / 2 + T 2^-(shift+1) + (T + 3) 2^-52 (A + pen),
+term by term:
+  * T 2^-(shift+1): fix_nlogn rounds each of the T terms to a multiple of
+    2^-shift once; the integer sum of those is exact.
+  * the FP64 part.  The kernel: each term is the device's log (two ulps,
+    relative 2^-51) times n (one rounding, 2^-53): 3 2^-52 A; the int64 sum
+    converted to double, (double)q, the two products of the penalty and the
+    subtraction ll - pen are one rounding each: at most 2 2^-52 (A + pen)
+    together.  This restatement: numpy's log (one ulp) and the product, 2^-52 A;
+    the penalty's two roundings and fsum's single one, 2^-52 (A + pen).  That is
+    6 2^-52 (A + pen) in all, which (T + 3) 2^-52 (A + pen) covers from T = 3 on
+    (T = 2 happens only for a column with a single value, where both sides give
+    exactly 0).
+  * ulp_f32(exact64) / 2: the one rounding to float.  Where the FP64 sum lies
+    within the two terms above of a float rounding boundary, the float may fall
+    on the boundary's other side; it is then still within ulp / 2 of the
+    kernel's FP64 sum, hence within ulp / 2 plus those two terms of exact64.
+The tests assert ulp_f32(exact64) / 2 + 2 (T 2^-(shift+1) + (T + 3) 2^-52 (A + pen)),
+the doubled small terms standing for that last case.  shift is disc_data()'s:
+min(32, 62 - exponent of N ln N).  Nothing in Bk is measured.
+
+What Bk can see.  For tables of up to 10^6 cells Bk stays below 1e-3 of the
+smallest |score| of every input the GPU shape tests use, and one record moved
+to another cell changes a score by about 1, so a miscounted record cannot hide
+(test_kernel_bound_resolves_one_record).  Beyond that the penalty
+(r_v - 1) q ln(N) / 2 grows with q while the log-likelihood stays below
+N ln N, and half an ulp of the float32 result swamps the log-likelihood: those
+cases check the table's shape, the 64-bit q and -- where the counts are read
+back -- the counts, not the log-likelihood."""
+import functools
 import itertools
 import math
 import os
@@ -94,6 +133,87 @@ def restated(codes, arity, v, mask):
     ulp = float(np.spacing(np.float32(abs(exact))))
     bound = (terms + 2) * 2.0 ** -24 * sum_abs + ulp
     return score, exact, bound
+
+
+def exact_from_counts(njk, nj, rv, q, N):
+    """(exact64, T, A) from the non-empty cell counts njk and parent-configuration counts nj."""
+    njk = np.asarray(njk, dtype=np.float64)
+    nj = np.asarray(nj, dtype=np.float64)
+    plus, minus = njk * np.log(njk), nj * np.log(nj)
+    pen = float((rv - 1) * q) * math.log(N) / 2
+    exact = math.fsum(itertools.chain(plus.tolist(), (-minus).tolist(), [-pen]))
+    return exact, int(njk.size + nj.size), math.fsum(plus.tolist()) + math.fsum(minus.tolist())
+
+
+def exact_value(codes, arity, v, mask):
+    """The value the kernel promises, in FP64: sum n_jk ln n_jk - sum n_j ln n_j - (r_v - 1) q ln(N) / 2
+    over the non-empty cells and parent configurations -> (exact64, T, A), see the module docstring.
+    Never allocates q r_v entries; q r_v < 2^63 (the scorer refuses anything larger)."""
+    N = codes.shape[0]
+    ps = parents_of(mask & ~(1 << v))
+    cfg = np.zeros(N, dtype=np.int64)
+    q = 1
+    for p in ps:
+        cfg += codes[:, p].astype(np.int64) * q
+        q *= int(arity[p])
+    rv = int(arity[v])
+    assert q * rv < 2 ** 63
+    cell = cfg + codes[:, v].astype(np.int64) * q
+    njk = np.unique(cell, return_counts=True)[1]
+    nj = np.unique(cfg, return_counts=True)[1]
+    return exact_from_counts(njk, nj, rv, q, N)
+
+
+def exact_value_batch(codes, arity, v, parent_sets):
+    """exact_value for many parent sets of v at once: parent_sets is an S x L array of parent indices,
+    ascending in each row, every column involved of arity <= 2 -> (exact64[S], T[S], A[S]).  One
+    bincount over set_id * cells + cell; the row sums are plain FP64 sums (at most 48 terms of size
+    <= N ln N with N a few dozen: their rounding is ~1e-14, far inside Bk)."""
+    ps = np.asarray(parent_sets, dtype=np.int64).reshape(len(parent_sets), -1)
+    S, L = ps.shape
+    ar = np.asarray(arity, dtype=np.int64)
+    assert ar[v] <= 2 and (S == 0 or L == 0 or ar[ps].max() <= 2)
+    N = codes.shape[0]
+    c = codes.astype(np.int64)
+    cfg = np.zeros((S, N), dtype=np.int64)
+    for a in range(L):
+        cfg += c[:, ps[:, a]].T << a
+    q2 = 1 << L
+    row = np.arange(S, dtype=np.int64)[:, None]
+    njk = np.bincount((row * (2 * q2) + cfg + c[:, v][None, :] * q2).ravel(), minlength=S * 2 * q2)
+    nj = np.bincount((row * q2 + cfg).ravel(), minlength=S * q2)
+
+    def nlogn(x, width):
+        x = x.reshape(S, width).astype(np.float64)
+        return np.where(x > 0, x * np.log(np.maximum(x, 1.0)), 0.0).sum(axis=1), (x > 0).sum(axis=1)
+
+    (plus, tp), (minus, tm) = nlogn(njk, 2 * q2), nlogn(nj, q2)
+    q = ar[ps].prod(axis=1)
+    pen = ((int(ar[v]) - 1) * q).astype(np.float64) * math.log(N) / 2
+    return plus - minus - pen, tp + tm, plus + minus
+
+
+def disc_shift(N):
+    """disc_data()'s fixed-point scale (csrc/disc_dev.h)."""
+    return min(32, 62 - math.frexp(N * math.log(N))[1])
+
+
+def ulp_f32(x):
+    """The spacing of float32 at |x| (x a double, normal range)."""
+    return math.ldexp(1.0, max(math.frexp(abs(float(x)))[1], -125) - 24)
+
+
+def kernel_bound(exact, T, A, rv, q, N):
+    """What the GPU tests allow between the kernel's float and exact64 (module docstring)."""
+    pen = float((rv - 1) * q) * math.log(N) / 2
+    return ulp_f32(exact) / 2 + 2.0 * (T * 2.0 ** -(disc_shift(N) + 1) + (T + 3) * 2.0 ** -52 * (A + pen))
+
+
+def q_of(arity, v, mask):
+    q = 1
+    for p in parents_of(mask & ~(1 << v)):
+        q *= int(arity[p])
+    return q
 
 
 def restated_lists(codes, arity, variables, candidates, max_parents, constraints=()):
@@ -242,6 +362,213 @@ def test_counts_table_layout():
     # parents 0 (base 1) and 2 (base 2), q = 6, child base 6
     assert q == 6 and tab.sum() == 4
     assert tab[0 + 2 * 2 + 1 * 6] == 2 and tab[1 + 2 * 2 + 0 * 6] == 1 and tab[1 + 0 * 2 + 1 * 6] == 1
+
+
+# ---- the kernel's own bound, and the inputs of test_gpu_discrete_shapes.py ------------
+def pairs_up_to(n, variables, k):
+    """Every (v, parent mask) with at most k parents out of the other n - 1 variables."""
+    vs, ps = [], []
+    for v in variables:
+        others = [p for p in range(n) if p != v]
+        for L in range(k + 1):
+            for comb in itertools.combinations(others, L):
+                vs.append(v)
+                ps.append(sum(1 << p for p in comb))
+    return vs, ps
+
+
+def _mask(*ps):
+    return sum(1 << p for p in ps)
+
+
+def combos(items, L):
+    """The L-subsets of items as an S x L array (one empty row for L = 0)."""
+    return np.array(list(itertools.combinations(items, L)), dtype=np.int64).reshape(math.comb(len(items), L), L)
+
+
+ARITY_A = [4, 4, 4, 4, 4, 4, 4, 3]
+# (v, parents): 192, 768, 1024 (q = 256), 3072, 4096 (q = 1024), 12288 (q = 4096), 12288 (q = 3072),
+# 16384 (q = 4096) and two of 49152 cells
+SETS_A = [(7, _mask(0, 1, 2)), (7, _mask(0, 1, 2, 3)), (0, _mask(1, 2, 3, 4)), (7, _mask(0, 1, 2, 3, 4)),
+          (0, _mask(1, 2, 3, 4, 5)), (7, _mask(0, 1, 2, 3, 4, 5)), (0, _mask(1, 2, 3, 4, 5, 7)),
+          (0, _mask(1, 2, 3, 4, 5, 6)), (7, _mask(0, 1, 2, 3, 4, 5, 6)), (0, _mask(1, 2, 3, 4, 5, 6, 7))]
+ARITY_A2 = [2] * 15 + [3]
+# 16384, 24576, 32768 (the option's maximum), 49152 and 98304 cells
+SETS_A2 = [(0, _mask(*range(1, 14))), (15, _mask(*range(0, 13))), (0, _mask(*range(1, 15))),
+           (15, _mask(*range(0, 14))), (0, _mask(*range(1, 16)))]
+# test_a_dense_limit_at_its_maximum also lists all 2^14 parent sets of variable 0 among the binary
+# columns and holds these positions of the list (layers ascending, masks ascending) to Bk
+CAND_A2 = _mask(*range(1, 15))
+SAMPLE_A2 = [0, 1, 200, 5000] + list(range((1 << 14) - 15, 1 << 14))
+ARITY_B = ARITY_A + [255] * 6 + [200]
+# 13,005,000 cells; 2.08e8 cells; q = 255^5 * 200, 5.5e16 cells
+SETS_B = [(8, _mask(9, 14)), (0, _mask(1, 8, 9, 14)), (8, _mask(9, 10, 11, 12, 13, 14))]
+# the same records in tables small enough for the histogram: 1020, 3200, 1020 and 3060 cells
+SMALL_B = [(8, _mask(0)), (14, _mask(1, 2)), (0, _mask(8)), (9, _mask(3, 7))]
+ARITY_C = [2, 3, 4, 5, 2, 3, 4, 5, 6, 7]
+ARITY_D = [3] * 6
+ARITY_E = [1 if j in (7, 19) else 2 for j in range(30)]
+ARITY_F = [(2, 3, 2, 4)[j % 4] for j in range(44)]
+ARITY_F63 = [(2, 3, 2, 4)[j % 4] for j in range(63)]
+VARS_F = [3, 10, 21, 30, 33, 38, 40, 43]
+CAND_F = _mask(26, 28, 29, 30, 31, 32, 33, 35, 37, 40, 41, 43)
+ARITY_G = [3, 4]
+N_G = 62_000_000
+
+
+def pairs_f():
+    """200 seeded pairs with one to four parents among the variables 30..43."""
+    rng = np.random.default_rng(44)
+    vs, ps = [], []
+    for _ in range(200):
+        par = rng.choice(np.arange(30, 44), size=int(rng.integers(1, 5)), replace=False)
+        v = int(rng.choice([x for x in range(44) if x not in par]))
+        vs.append(v)
+        ps.append(_mask(*[int(p) for p in par]))
+    return vs, ps
+
+
+@functools.lru_cache(maxsize=None)
+def shape_input(name):
+    """The inputs of the GPU shape tests -> (codes, arity): built once per session, never modified."""
+    if name == "g":
+        rng = np.random.default_rng(62)
+        codes = np.empty((N_G, 2), dtype=np.uint8)
+        for j, r in enumerate(ARITY_G):
+            codes[:, j] = rng.integers(0, r, size=N_G, dtype=np.uint8)
+            codes[:r, j] = np.arange(r)
+        arity = ARITY_G
+    else:
+        n_N_arity_seed = {"a": (3000, ARITY_A, 81), "a2": (3000, ARITY_A2, 82), "b1500": (1500, ARITY_B, 83),
+                          "b2100": (2100, ARITY_B, 84), "c300": (300, ARITY_C, 85), "c2100": (2100, ARITY_C, 86),
+                          "d": (20000, ARITY_D, 87), "e": (16, ARITY_E, 88), "f": (500, ARITY_F, 89),
+                          "f63": (200, ARITY_F63, 90)}
+        N, arity, seed = n_N_arity_seed[name]
+        codes = synthetic(len(arity), N, arity, seed)
+    assert all(len(np.unique(codes[:, j])) == arity[j] for j in range(len(arity)))  # every value present
+    codes.setflags(write=False)
+    return codes, list(arity)
+
+
+def list_order(candidates, k):
+    """The parent masks of one variable's list in the order ulg_disc_score stores them."""
+    return [m for L in range(min(len(candidates), k) + 1)
+            for m in sorted(_mask(*comb) for comb in itertools.combinations(candidates, L))]
+
+
+def shape_pairs(name):
+    """The (variable, parent mask) pairs the GPU shape tests score on shape_input(name)."""
+    if name == "a":  # and the lists of variables 7 and 0 with every other column a candidate
+        vs, ps = pairs_up_to(8, [7, 0], 7)
+        return [v for v, _ in SETS_A] + vs, [m for _, m in SETS_A] + ps
+    if name == "a2":
+        order = list_order(parents_of(CAND_A2), 14)
+        return [v for v, _ in SETS_A2] + [0] * len(SAMPLE_A2), [m for _, m in SETS_A2] + [order[i] for i in SAMPLE_A2]
+    if name in ("b1500", "b2100"):
+        return [v for v, _ in SETS_B + SMALL_B], [m for _, m in SETS_B + SMALL_B]
+    if name in ("c300", "c2100"):
+        return pairs_up_to(10, range(10), 4)
+    if name == "d":
+        return pairs_up_to(6, range(6), 5)
+    if name == "f":
+        vs, ps = pairs_f()
+        for v in VARS_F:
+            cs = parents_of(CAND_F & ~(1 << v))
+            for L in range(4):
+                for comb in itertools.combinations(cs, L):
+                    vs.append(v)
+                    ps.append(_mask(*comb))
+        return vs, ps
+    if name == "f63":
+        return [0, 62, 5], [_mask(31, 62), _mask(0, 61), _mask(62)]
+    if name == "g":
+        return [0, 1, 0, 1], [0, 0, 2, 1]
+    raise KeyError(name)
+
+
+@functools.lru_cache(maxsize=None)
+def g_joint(rows=None):
+    codes = shape_input("g")[0][:rows]
+    return np.bincount(codes[:, 0] + np.uint8(3) * codes[:, 1], minlength=12).reshape(4, 3)  # [code 1][code 0]
+
+
+def g_counts(v, m, rows=None):
+    """Input g's dense table of (v, m) in the kernel's layout (counts_table's) and its q, from one pass
+    over the records; rows: only the first so many."""
+    joint = g_joint(rows)
+    if m & ~(1 << v) == 0:
+        return joint.sum(axis=v).astype(np.int64), 1
+    return (joint.T if v == 0 else joint).ravel().astype(np.int64), ARITY_G[1 - v]
+
+
+def test_exact_value_equals_restatement():
+    codes, arity = n6_case()
+    vs, ps = pairs_up_to(6, range(6), 3)
+    assert len(vs) == 156
+    for v, m in zip(vs, ps):
+        want = restated(codes, arity, v, m)[1]
+        got, T, A = exact_value(codes, arity, v, m)
+        assert abs(got - want) <= 1e-9 * abs(want), (v, m, got, want)
+        tab, q = counts_table(codes, arity, v, m)
+        assert T == int((tab > 0).sum() + (tab.reshape(-1, q).sum(axis=0) > 0).sum()) and A > 0
+
+
+def test_exact_value_batch_equals_scalar():
+    rng = np.random.default_rng(30)
+    codes = rng.integers(0, 2, size=(16, 30)).astype(np.uint8)
+    codes[:2, :] = [[0], [1]]
+    arity = [2] * 30
+    for L, count in ((0, 1), (1, 50), (2, 100), (3, 150), (4, 200)):  # the empty set and 500 random sets
+        v = int(rng.integers(0, 30))
+        others = [p for p in range(30) if p != v]
+        sets = np.array([sorted(rng.choice(others, size=L, replace=False)) for _ in range(count)], dtype=np.int64)
+        ex, T, A = exact_value_batch(codes, arity, v, sets.reshape(count, L))
+        for i in range(count):
+            e1, T1, A1 = exact_value(codes, arity, v, _mask(*[int(p) for p in sets[i]]))
+            assert abs(ex[i] - e1) <= 1e-12 * abs(e1) and T[i] == T1 and abs(A[i] - A1) <= 1e-12 * max(A1, 1.0)
+    # columns with a single value: they count in q as 1 and leave every count alone
+    codes_e, arity_e = shape_input("e")
+    sets = np.array([[3, 7, 19, 22], [0, 1, 7, 29]])
+    ex, T, A = exact_value_batch(codes_e, arity_e, 5, sets)
+    for i in range(2):
+        e1, T1, A1 = exact_value(codes_e, arity_e, 5, _mask(*[int(p) for p in sets[i]]))
+        assert abs(ex[i] - e1) <= 1e-12 * abs(e1) and T[i] == T1
+    assert exact_value_batch(codes_e, arity_e, 7, sets[:, [0, 2]])[0].tolist() == [0.0, 0.0]
+
+
+@pytest.mark.parametrize("name", ["a", "a2", "b1500", "b2100", "c300", "c2100", "d", "e", "f", "f63", "g"])
+def test_kernel_bound_resolves_one_record(name):
+    """Bk < 1e-3 of the smallest |score| over every table of at most 10^6 cells the GPU shape tests
+    hold to Bk on this input (shape_pairs; of input e's 835,230 sets, all those of three variables)."""
+    codes, arity = shape_input(name)
+    N = codes.shape[0]
+    rel, smallest = 0.0, math.inf
+    if name == "e":
+        for v in (0, 13, 29):
+            others = [p for p in range(30) if p != v]
+            for L in range(5):
+                sets = combos(others, L)
+                ex, T, A = exact_value_batch(codes, arity, v, sets)
+                q = np.asarray(arity)[sets].prod(axis=1)
+                bk = np.array([kernel_bound(e, int(t), float(a), 2, int(qq), N) for e, t, a, qq in zip(ex, T, A, q)])
+                rel, smallest = max(rel, float((bk / np.abs(ex)).max())), min(smallest, float(np.abs(ex).min()))
+    else:
+        for v, m in zip(*shape_pairs(name)):
+            q = q_of(arity, v, m)
+            if q * arity[v] > 10 ** 6:
+                continue
+            if name == "g":  # exact_value's sort of 62e6 indices takes a minute; the counts are the same
+                tab, _ = g_counts(v, m)
+                want, _ = counts_table(codes[:5000], arity, v, m)
+                assert np.array_equal(g_counts(v, m, 5000)[0], want) and tab.sum() == N
+                nj = tab.reshape(-1, q).sum(axis=0)
+                ex, T, A = exact_from_counts(tab[tab > 0], nj[nj > 0], arity[v], q, N)
+            else:
+                ex, T, A = exact_value(codes, arity, v, m)
+            rel = max(rel, kernel_bound(ex, T, A, arity[v], q, N) / abs(ex))
+            smallest = min(smallest, abs(ex))
+    print(f"{name}: Bk <= {rel:.2e} |score|, smallest |score| {smallest:.1f}")
+    assert rel < 1e-3 and smallest > 1
 
 
 # ---- command line refusals -------------------------------------------------------

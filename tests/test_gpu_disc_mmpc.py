@@ -2,7 +2,8 @@
 against the Python restatement in test_disc_mmpc.py.
 
 Values.  The kernel adds every n ln n term as an integer multiple of 2^-shift
-(shift = 32 for every N used here: N ln N < 2^30).  One such term is within
+(shift = 32 for every N used here: N ln N < 2^30; test_gpu_discrete_shapes.py
+has the one input with shift = 31).  One such term is within
 2^-(shift+1) of the device's FP64 n ln n, which is within two ulps of the
 device log (relative 2^-51) plus the product's rounding of the exact value; the
 restatement's FP64 terms carry one ulp of numpy's log and the product's
@@ -139,6 +140,51 @@ def test_g2_does_not_depend_on_order_or_call(ctx):
     one = ctx.g2_discrete(xs[1234:1235], ts[1234:1235], ms[1234:1235])[0]
     assert a.tobytes() == b.tobytes() == c.tobytes() and one[0] == a[1234]
     assert len(ctx.g2_discrete([], [], [])[0]) == 0
+
+
+def test_g2_high_arity(ctx):
+    """Arities 255 x 128: a marginal table of 32,640 cells (codes up to 254 and 127, the r_t loop of
+    128, 255 x 128 products summed by one thread for n_z); an arity-1 conditioning column is skipped
+    by the kernel and leaves the table as it is; one binary column more is 65,280 cells: not performed."""
+    arity = [255, 128, 2, 3, 1]
+    codes = synthetic(5, 4000, arity, 255)
+    assert codes[:, 0].max() == 254 and codes[:, 1].max() == 127
+    ctx.load_discrete(codes, arity)
+    xs, ts, ms = [0, 0, 1, 0, 0, 2, 1], [1, 1, 0, 1, 2, 0, 2], [0, 1 << 4, 0, 1 << 2, 1 << 3, 1 << 3, 1 << 4 | 1 << 3]
+    g2, dof, cells = ctx.g2_discrete(xs, ts, ms)
+    assert cells.tolist() == [32640, 32640, 32640, 65280, 1530, 1530, 768]
+    assert dof.tolist() == [254 * 127, 254 * 127, 254 * 127, 254 * 127 * 2, 254 * 3, 254 * 3, 127 * 3]
+    assert math.isnan(g2[3])
+    keep = [0, 1, 2, 4, 5, 6]
+    _check_values(ctx, codes, arity, [xs[i] for i in keep], [ts[i] for i in keep], [ms[i] for i in keep])
+    assert g2[0] == g2[1] == g2[2] and g2[4] == g2[5] and g2[0] > 0
+
+
+def test_g2_more_tests_than_workgroups(ctx):
+    """2352 tests on 2048 workgroups, every one against the restatement: a workgroup's second test
+    reuses its histogram."""
+    codes, arity, _ = input_case("dense8-N2500-s1")
+    ctx.load_discrete(codes, arity)
+    xs, ts, ms = _all_tests(8, 3)
+    assert len(xs) == 2352 > 2048
+    _check_values(ctx, codes, arity, xs, ts, ms)
+
+
+def test_g2_variables_from_bit_30_up(ctx):
+    """x, t and the conditioning set among the variables 30..39 of 40: masks with bits on both sides of 32."""
+    arity = [2 + (j * 7 % 5 == 0) for j in range(40)]
+    codes = synthetic(40, 300, arity, 40)
+    ctx.load_discrete(codes, arity)
+    xs, ts, ms = [], [], []
+    for x, t in itertools.permutations(range(30, 40), 2):
+        others = [v for v in range(30, 40) if v not in (x, t)]
+        for s in range(3):
+            for comb in itertools.combinations(others, s):
+                xs.append(x)
+                ts.append(t)
+                ms.append(sum(1 << v for v in comb))
+    assert len(xs) == 90 * 37 and max(ms) >> 39 and set(arity[30:]) == {2, 3}
+    _check_values(ctx, codes, arity, xs, ts, ms)
 
 
 # ---- skeletons -----------------------------------------------------------------------

@@ -1,7 +1,12 @@
 """Discrete BIC on the GPU (ulg_disc_*, `score -f BIC`) against the Python
 restatement of the reference in test_discrete.py, within its derived bound B
 (see that module's docstring); counts, path identity and list structure are
-exact."""
+exact.
+
+B is the error of the reference's float32 summation, which is looser than what
+the kernel promises (the exactly summed FP64 value, rounded once).
+test_gpu_discrete_shapes.py holds the kernel to that FP64 bound, Bk, and covers
+the shapes these small inputs never reach."""
 import itertools
 import math
 import os

@@ -211,7 +211,23 @@ int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n,
  * (ulg_cbic_fetch, ulg_pss_format, ulg_search_from_scores read them);
  * time_limit_ms is checked after each complete layer.  q r_v >= 2^63 cells
  * (q = prod r_p) returns ULG_ERR_UNSUPPORTED, as do sets of more than
- * ULG_MAX_PARENTS_GPU parents.  A refused call leaves the previous lists. */
+ * ULG_MAX_PARENTS_GPU parents.  A refused call leaves the previous lists.
+ *
+ * Option "disc_prune" (ulg_set_option, 0 or 1, default 0, sticky; any other
+ * value is ULG_ERR_ARG; only this call reads it): 1 applies the reference's
+ * end-of-scoring prune() (score_calculator.cpp:137-197, whose call the
+ * reference commented out in score_main.cpp:166-171 for the continuous case)
+ * to every variable's list before it is stored.  On the float values above, a
+ * set P is removed iff a kept proper subset Q has (float)(s(Q) - s(P)) >=
+ * -2 FLT_EPSILON (2.3841858e-07f): Q scores at least as well, ties included.
+ * Only stored sets dominate, but through any number of sets that are not
+ * stored; a removed set removes nothing.  That is prune()'s sort-and-scan
+ * wherever its comparator is a strict weak order (|score| >= 4).  One extra
+ * launch per completed layer (disc_prune_kernel) and one float per table
+ * slot; with 0 no kernel runs and nothing is allocated.  total_stored then
+ * counts the kept sets, total_scored is unchanged and
+ * ulg_get_info("disc_pruned") gives the sets removed (0 with the option off).
+ * ulg_disc_score_sets, ulg_disc_counts and ulg_cbic_* ignore the option. */
 int ulg_disc_score(ulg_ctx *ctx, int kind, const int *vars, int nv, const uint64_t *candidates,
                    int max_parents, int64_t *total_stored, int64_t *total_scored);
 /* calculateScore(vars[i], parents[i]) for arbitrary pairs: the value above
@@ -451,6 +467,8 @@ int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_co
  * histogram; larger tables are counted in a hash table of their non-empty
  * cells (in LDS when 4N slots fit, else in a per-workgroup HBM slab).  Both
  * give bit-identical values.
+ * "disc_prune" (0/1, default 0): ulg_disc_score drops every set that a kept
+ * proper subset dominates (the reference's prune(); see ulg_disc_score).
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -496,7 +514,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * "exact_cache_misses" (the last exact-order A*'s user-space host counters on
  * the calling thread, perf_event_open; -1 where the host does not grant
  * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
- * counted on each path), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
+ * counted on each path), "disc_pruned" (sets its prune pass removed, option
+ * "disc_prune"), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
  * ulg_disc_mmpc performed / left out by its reliability rule), "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero

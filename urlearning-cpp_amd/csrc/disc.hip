@@ -21,11 +21,16 @@
 // a function of the counts alone and integer adds commute, so the sum -- and
 // the float it is rounded to once -- does not depend on the path, the hash
 // placement or the scheduling.
+//
+// Option disc_prune adds the reference's prune() (score_calculator.cpp:
+// 137-197, disabled in its score_main.cpp:166-171) between the last layer and
+// the compaction: disc_prune_kernel below.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 
 #include "disc_dev.h"  // DiscData, fix_nlogn, disc_ready, disc_data
+#include "disc_prune.h"  // for_each_subset_rank, kPruneTwoEps
 #include "ulg_internal.h"
 
 using namespace ulg;
@@ -39,13 +44,14 @@ constexpr int kHashLdsSlots = 8192;                 // 8192 x 12 B = 96 KB of th
 constexpr int kScanPerThread = 8;
 constexpr int kScanPerBlock = kDiscBlock * kScanPerThread;
 constexpr unsigned long long kErrCode = 1ull;       // a value code >= its column's arity
+constexpr int kDiscWords = 5;                       // the call's words: [error word, dense sets, sparse sets, stored, pruned]
 
 struct DiscWork {
     unsigned long long *slab;  // sparse path in HBM: hslots keys, then hslots uint32 counts, per workgroup
     uint64_t hslots;           // power of two >= 4N
     int hash_lds;              // the hash table fits LDS
     int64_t dense_cells;
-    unsigned long long *word;  // [error word, dense sets, sparse sets, stored]
+    unsigned long long *word;  // [error word, dense sets, sparse sets, stored, pruned]
 };
 
 // One work item, decoded by thread 0.
@@ -262,6 +268,62 @@ __global__ void __launch_bounds__(kDiscBlock) disc_layer_kernel(DiscData D, Disc
     }
 }
 
+// ---- prune pass (option disc_prune) ------------------------------------------
+// R8, the reference's prune() (score_calculator.cpp:137-197) per variable: a
+// stored set P goes iff a kept proper subset Q has (float)(s(Q) - s(P)) >=
+// -2 FLT_EPSILON.  best[slot] = the largest kept score among the slot's set
+// and all its subsets (-inf: none); a hole (violating or arity-1 set) stores
+// nothing of its own but passes its subsets' maximum on, so every kept proper
+// subset of P is seen through P's L immediate subsets.  One launch per layer
+// (layer L reads best of layer L - 1), one slot per thread: it alone reads and
+// writes table[slot] and best[slot] in this launch.
+struct PruneArgs {
+    const int *vm;           // [nv][2]: variable, candidate count
+    const uint64_t *toff;    // [nv * S + 1] slot prefixes
+    const uint64_t *work;    // [nv + 1] this layer's item prefixes
+    const uint64_t *binom64; // [64][64]
+    float *table;            // per slot: the stored value, or absent
+    float *best;             // per slot: B
+    unsigned long long *pruned;
+    int nv, S, L;
+};
+
+__global__ void __launch_bounds__(kDiscBlock) disc_prune_kernel(PruneArgs A) {
+    const uint64_t total = A.work[A.nv];
+    unsigned int gone = 0;
+    for (uint64_t w = (uint64_t)blockIdx.x * kDiscBlock + threadIdx.x; w < total; w += (uint64_t)gridDim.x * kDiscBlock) {
+        // the variable: the last i with work[i] <= w (w < work[nv], so i < nv)
+        int lo = 0, hi = A.nv;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (A.work[mid] <= w) lo = mid; else hi = mid;
+        }
+        const int i = lo;
+        const uint64_t r = w - A.work[i];
+        const uint64_t slot = A.toff[(uint64_t)i * A.S + A.L] + r;
+        float M = -INFINITY;
+        if (A.L > 0) {
+            const float *below = A.best + A.toff[(uint64_t)i * A.S + A.L - 1];  // slab (i, L - 1): C(m, L - 1) slots
+            for_each_subset_rank(A.binom64, A.vm[2 * i + 1], A.L, r,
+                                 [&](int, int, uint64_t sub) { M = fmaxf(M, below[sub]); });
+        }
+        const float own = A.table[slot];
+        float B = M;
+        if (__float_as_uint(own) != kAbsentBits) {
+            if (__fsub_rn(M, own) < -kPruneTwoEps) {  // M = -inf: no kept subset
+                B = fmaxf(M, own);
+            } else {
+                A.table[slot] = __uint_as_float(kAbsentBits);
+                ++gone;
+            }
+        }
+        A.best[slot] = B;
+    }
+    // every lane is here: one add per wave
+    for (int d = 32; d >= 1; d >>= 1) gone += __shfl_down(gone, d, 64);
+    if ((threadIdx.x & 63) == 0 && gone) atomicAdd(A.pruned, (unsigned long long)gone);
+}
+
 // ---- arbitrary pairs / one table ---------------------------------------------
 __global__ void __launch_bounds__(kDiscBlock)
 disc_sets_kernel(DiscData D, DiscWork W, const uint64_t *pairs, int64_t count, const uint64_t *cons, float *out,
@@ -415,10 +477,10 @@ int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int 
     if (int rc0 = finish_pending(c)) return rc0;
     ULG_HIP(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->d_codes, (size_t)(N * n))) || (rc = ensure(c, c->d_disc_word, 4))) return rc;
+    if ((rc = ensure(c, c->d_codes, (size_t)(N * n))) || (rc = ensure(c, c->d_disc_word, kDiscWords))) return rc;
     c->disc_loaded = false;  // the previous codes are gone
     ULG_HIP(c, hipMemcpyAsync(c->d_codes.p, codes, (size_t)(N * n), hipMemcpyHostToDevice, c->stream));
-    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, kDiscWords * sizeof(unsigned long long), c->stream));
     DiscData D{};
     D.codes = c->d_codes.p;
     D.N = N;
@@ -502,7 +564,7 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     if ((rc = ensure(c, c->d_disc_meta, meta.size())) || (rc = ensure(c, c->d_disc_cand, cand.size())) ||
         (rc = ensure(c, c->d_disc_vm, vm.size())) || (rc = ensure(c, c->d_disc_table, total_slots)) ||
         (rc = ensure(c, c->d_disc_sets, total_slots)) || (rc = ensure(c, c->d_disc_blk, (size_t)nb + 1)) ||
-        (rc = ensure(c, c->d_disc_word, 4)))
+        (rc = ensure(c, c->d_disc_word, kDiscWords)))
         return rc;
     DiscWork W;
     size_t lds = 0;
@@ -513,7 +575,7 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_vm.p, vm.data(), vm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemsetAsync(c->d_disc_table.p, 0xFF, total_slots * sizeof(float), c->stream));  // absent
-    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, kDiscWords * sizeof(unsigned long long), c->stream));
     // pageable sources: the copies above must be done before `meta` goes away
     ULG_HIP(c, hipStreamSynchronize(c->stream));
 
@@ -554,6 +616,30 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
         }
     }
     c->completed_layer = done_L;
+    if (c->disc_prune) {
+        // the completed layers only: nothing above done_L was stored
+        if ((rc = ensure(c, c->d_disc_best, total_slots))) return rc;
+        PruneArgs P{};
+        P.vm = c->d_disc_vm.p;
+        P.toff = c->d_disc_meta.p;
+        P.binom64 = c->d_binom64.p;
+        P.table = c->d_disc_table.p;
+        P.best = c->d_disc_best.p;
+        P.pruned = c->d_disc_word.p + 4;
+        P.nv = nv;
+        P.S = S;
+        for (int L = 0; L <= done_L; ++L) {
+            const uint64_t items = work[(size_t)L * (nv + 1) + nv];
+            if (!items) continue;
+            P.L = L;
+            P.work = c->d_disc_meta.p + (size_t)nv * S + 1 + (size_t)L * (nv + 1);
+            prof_begin(c, "disc_prune");
+            disc_prune_kernel<<<(unsigned)std::min<uint64_t>((items + kDiscBlock - 1) / kDiscBlock, 2048), kDiscBlock, 0,
+                                c->stream>>>(P);
+            prof_end(c);
+            ULG_HIP(c, hipGetLastError());
+        }
+    }
     if ((rc = ensure(c, c->out_sets, total_slots)) || (rc = ensure(c, c->out_scores, total_slots)) ||
         (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
         return rc;
@@ -566,13 +652,14 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
                                                                  c->d_disc_blk.p, c->out_offsets.p);
     prof_end(c);
     ULG_HIP(c, hipGetLastError());
-    unsigned long long word[4] = {0, 0, 0, 0};
+    unsigned long long word[kDiscWords] = {0, 0, 0, 0, 0};
     ULG_HIP(c, hipMemcpyAsync(word, c->d_disc_word.p, sizeof word, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     c->last_err_word = 0;
     c->disc_path_sets[0] = (int64_t)word[1];
     c->disc_path_sets[1] = (int64_t)word[2];
+    c->disc_pruned = (int64_t)word[4];
     publish(c, ls, (int64_t)word[3], false);
     if (total_stored) *total_stored = c->total_stored;
     if (total_scored) *total_scored = c->total_scored;
@@ -604,7 +691,7 @@ static int disc_sets_launch(ulg_ctx *c, const char *what, int64_t count, const i
     }
     ULG_HIP(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->d_sets_in, (size_t)count * 2)) || (rc = ensure(c, c->d_disc_word, 4))) return rc;
+    if ((rc = ensure(c, c->d_sets_in, (size_t)count * 2)) || (rc = ensure(c, c->d_disc_word, kDiscWords))) return rc;
     DiscWork W;
     size_t lds = 0;
     unsigned grid = 1;

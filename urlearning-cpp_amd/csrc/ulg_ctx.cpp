@@ -163,7 +163,7 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->d_cons); release(c->d_cons_var);
     release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
     release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
-    release(c->d_disc_table); release(c->d_disc_blk);
+    release(c->d_disc_table); release(c->d_disc_blk); release(c->d_disc_best);
     release(c->d_g2_tests); release(c->d_g2_out);
     pss_release(c);
     if (c->search) {
@@ -209,6 +209,11 @@ int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
     if (std::strcmp(name, "disc_dense_cells") == 0) {
         if (value < 1 || value > 32768) return set_err(c, ULG_ERR_ARG, "disc_dense_cells must be 1..32768");
         c->disc_dense_cells = value;
+        return ULG_OK;
+    }
+    if (std::strcmp(name, "disc_prune") == 0) {
+        if (value != 0 && value != 1) return set_err(c, ULG_ERR_ARG, "disc_prune must be 0 or 1");
+        c->disc_prune = (int)value;
         return ULG_OK;
     }
     if (std::strcmp(name, "table_budget_kb") == 0) {
@@ -320,6 +325,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table
     if (std::strcmp(name, "disc_dense_sets") == 0 || std::strcmp(name, "disc_sparse_sets") == 0) {
         *value = c->disc_path_sets[name[5] == 's' ? 1 : 0];
+        return ULG_OK;
+    }
+    // the last ulg_disc_score: sets its prune pass removed (0 with disc_prune off)
+    if (std::strcmp(name, "disc_pruned") == 0) {
+        *value = c->disc_pruned;
         return ULG_OK;
     }
     // the last ulg_disc_mmpc: G^2 tests performed / left out by the reliability rule

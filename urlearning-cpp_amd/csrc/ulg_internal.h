@@ -144,7 +144,10 @@ struct ulg_ctx {
     ulg::DevBuf<unsigned long long> d_disc_blk;   // compaction: stored sets per block, then their prefix
     ulg::DevBuf<uint64_t> d_disc_sets;            // per table slot: the set's variable mask
     ulg::DevBuf<unsigned long long> d_disc_slab;  // sparse path: per-workgroup hash tables
-    ulg::DevBuf<unsigned long long> d_disc_word;  // [error word, dense sets, sparse sets, stored]
+    ulg::DevBuf<unsigned long long> d_disc_word;  // [error word, dense sets, sparse sets, stored, pruned]
+    int disc_prune = 0;                           // ulg_disc_score: drop dominated sets (the reference's prune())
+    int64_t disc_pruned = 0;                      // ... sets the last call dropped
+    ulg::DevBuf<float> d_disc_best;               // ... per table slot: the best kept score among the set and its subsets
     ulg::DevBuf<int32_t> d_disc_counts;           // ulg_disc_counts' table
     // ---- discrete G^2 tests and MMPC (disc_mmpc.hip) ----
     ulg::DevBuf<uint64_t> d_g2_tests;             // per test: (x, t), conditioning mask

@@ -3,7 +3,7 @@
 // by libulg.so on one GPU, and the .pss score cache is written in the
 // reference's exact text format.
 //
-//   score <in.csv> <out.pss> [-f BIC] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
+//   score <in.csv> <out.pss> [-f BIC] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //
 // -f BIC (the default, as in the reference) is the discrete score: the tokens
@@ -14,6 +14,14 @@
 // reference).  Options that only matter for those or for the reference's
 // AD-tree (-m, -e, -w, -a, -o) are accepted; -e still feeds the "META ess"
 // header line as in score_main.cpp:388.
+//
+// --prune (-f BIC only) applies the reference's end-of-scoring prune()
+// (score_calculator.cpp:137-197; its call is commented out in
+// score_main.cpp:166-171 because it "might not work with continuous case") on
+// the GPU: a parent set goes when a kept proper subset scores at least as well
+// (within 2 FLT_EPSILON).  The .pss then holds the kept sets only, stdout gains
+// "Size before pruning" / "Size after pruning" and the metrics line "pruned".
+// -f cBIC refuses it: its store rule already tests dominance.
 #include <cmath>
 #include <cctype>
 #include <cstdio>
@@ -41,7 +49,8 @@ int main(int argc, char **argv) {
             {"t", "threads", true, "1", "Host threads in the reference; the GPU scores every variable at once."},
             {"r", "time", true, "-1", "The maximum amount of time (s) to use for each variable (every variable is scored at once: the budget of the whole call, checked after each layer). A value less than 1 means no limit."},
             {"s", "hasHeader", false, "", "Add this flag if the first line of the input file gives the variable names."},
-            {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171)."},
+            {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171; --prune runs it for -f BIC)."},
+            {"", "prune", false, "", "Drop every parent set that a kept proper subset dominates (the reference's prune(); -f BIC only)."},
             {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC."},
             {"", "device", true, "0", "HIP device to use."},
             {"h", "help", false, "", "Show this help message."},
@@ -66,6 +75,12 @@ int main(int argc, char **argv) {
     const bool discrete = sf == "bic";
     if (discrete && args.has("enableDeCamposPruning")) {
         std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC (it is a no-op for -f cBIC)\n");
+        return 2;
+    }
+    const bool prune = args.has("prune");
+    if (prune && !discrete) {
+        std::fprintf(stderr, "score: --prune is for -f BIC: the store rule of -f cBIC already tests dominance, and the "
+                             "reference disabled prune() for the continuous case\n");
         return 2;
     }
     const std::string input = args.get("input"), output = args.get("output");
@@ -159,10 +174,16 @@ int main(int argc, char **argv) {
     if (rc == ULG_OK && !cons.vars.empty())
         rc = ulg_cbic_set_constraints(ctx, (int)cons.vars.size(), cons.vars.data(), cons.required.data(),
                                       cons.forbidden.data());
+    if (rc == ULG_OK && prune) rc = ulg_set_option(ctx, "disc_prune", 1);
     if (rc == ULG_OK)
         rc = discrete ? ulg_disc_score(ctx, ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
                       : ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
-    int64_t oot = 0, done_layer = 0;
+    int64_t oot = 0, done_layer = 0, pruned = 0;
+    if (rc == ULG_OK && prune) {
+        ulg_get_info(ctx, "disc_pruned", &pruned);
+        // score_main.cpp:159,170, once for the whole call
+        std::printf("Size before pruning: %lld\nSize after pruning: %lld\n", (long long)(stored + pruned), (long long)stored);
+    }
     if (rc == ULG_OK && running_time > 0) {
         ulg_get_info(ctx, "out_of_time", &oot);
         ulg_get_info(ctx, "highest_completed_layer", &done_layer);
@@ -210,11 +231,13 @@ int main(int argc, char **argv) {
                 "file write %.3f s (%lld bytes)\n",
                 (long long)scored, (long long)stored, t1 - t0, (double)scored / (t1 - t0), t2 - t1, t3 - t2,
                 (long long)len);
+    char pruned_field[48] = "";
+    if (prune) std::snprintf(pruned_field, sizeof pruned_field, ", \"pruned\": %lld", (long long)pruned);
     std::fprintf(stderr,
                  "ulg_metrics {\"tool\": \"score\", \"function\": \"%s\", \"n\": %d, \"N\": %lld, \"k\": %d, \"lambda\": %g, "
                  "\"scored\": %lld, \"stored\": %lld, \"score_s\": %.6f, \"sets_per_s\": %.6g, \"format_s\": %.6f, "
-                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d}\n",
+                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d%s}\n",
                  sf.c_str(), n, (long long)N, maxp, lambda, (long long)scored, (long long)stored, t1 - t0,
-                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot);
+                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot, pruned_field);
     return 0;
 }

@@ -245,8 +245,14 @@ class Context:
         self.n = n
         self.N = N
 
-    def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC):
-        """ulg_disc_score -> (total_stored, total_scored); fetch() reads the lists."""
+    def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC, prune=None):
+        """ulg_disc_score -> (total_stored, total_scored); fetch() reads the lists.
+        prune: True / False sets option "disc_prune" (sticky) before the call -- the
+        reference's prune(): a set goes when a kept proper subset scores at least as
+        well; total_stored then counts the kept sets and info("disc_pruned") the
+        removed ones.  None leaves the option as it is."""
+        if prune is not None:
+            self.set_option("disc_prune", 1 if prune else 0)
         v = np.ascontiguousarray(variables, dtype=np.int32)
         c = np.ascontiguousarray(candidates, dtype=np.uint64)
         st, sc = C.c_int64(), C.c_int64()
@@ -490,7 +496,8 @@ class Context:
     def info(self, name: str) -> int:
         """ulg_get_info: "out_of_time", "highest_completed_layer", "score_error_word",
         "exact_cycles", "exact_instructions", "exact_cache_misses", "disc_mmpc_tests",
-        "disc_mmpc_skipped"."""
+        "disc_mmpc_skipped", "disc_pruned" (sets the last score_discrete's prune pass
+        removed; 0 with option "disc_prune" off)."""
         v = C.c_int64()
         self._check(lib().ulg_get_info(self._h, name.encode(), C.byref(v)), "ulg_get_info")
         return v.value

@@ -107,8 +107,31 @@ int ulg_cbic_gram(ulg_ctx *ctx, double *gram_out);
  * partial-correlation tests on the loaded data's Gram matrix.  Independent
  * iff |atanh(r)| sqrt(N - |S| - 3) <= Phi^-1(1 - alpha/2); conditioning sets
  * of at most max_cond variables (< 0: 24); AND symmetry rule.  rows[i] bit j
- * = edge i-j (no diagonal).  Exact rules: oracle/ora_mmpc.c. */
+ * = edge i-j (no diagonal).  A constant column (every test on it is NaN) has
+ * no edge.  Exact rules: oracle/ora_mmpc.c. */
 int ulg_mmpc(ulg_ctx *ctx, double alpha, int max_cond, uint64_t *rows);
+/* The raw statistics behind ulg_mmpc, for count queries on the loaded data's
+ * Gram matrix (tests and diagnostics; the continuous counterpart of
+ * ulg_disc_g2): out[i] = the minimum of |z(xs[i], ts[i] | S)| =
+ * |atanh(r)| sqrt(N - |S| - 3) over the subsets S of pools[i] (a variable
+ * mask) with |S| <= max_cond (< 0 or > 24: 24) that contain musts[i]
+ * (musts[i] < 0: every subset; its bit may be set in pools[i] or not).
+ * Subsets are taken as subset masks ascending over the pool without must in
+ * ascending variable order, the empty (or {must}) set first, and the
+ * enumeration stops at the first value <= stops[i] (-inf: never; +inf: the
+ * first set's value is the result).  No set of at most max_cond variables
+ * (max_cond = 0 with a must) gives +inf; N - |S| - 3 <= 0 or a residual
+ * variance <= 0 gives 0; r is clamped to +-(1 - 1e-15); a set whose
+ * value is NaN (a constant column) never replaces the minimum, so a query
+ * with nothing else gives +inf.  Each query is one lane of
+ * ulg_mmpc's own query launch (mmpc_query_kernel, the instance chosen by the
+ * largest conditioning set of the call as there).  ULG_ERR_ARG for x = t, for
+ * x or t equal to must or in the pool, for an index or a mask bit out of
+ * range and for more than 24 conditioning variables (pool and must);
+ * ULG_ERR_STATE without continuous data.  The context's lists stay as they
+ * are. */
+int ulg_mmpc_min_z(ulg_ctx *ctx, int64_t count, const int *ts, const int *xs, const int *musts,
+                   const uint64_t *pools, int max_cond, const double *stops, double *out);
 
 /* Score all parent sets of size <= max_parents within each variable's
  * candidate set (candidates[i] for variable vars[i]; the variable's own bit

@@ -46,6 +46,21 @@ def test_oracle_skeleton_shape(oracle_built):
             assert ((rows[i] >> j) & 1) == ((rows[j] >> i) & 1)
 
 
+@pytest.mark.parametrize("col", [0, 4, 11])
+def test_oracle_constant_column_has_no_edge(oracle_built, col):
+    """A constant column normalises to NaN and every test on it gives NaN: that is no
+    association, wherever the column stands (a NaN that is merely never <= z_crit would be
+    taken as the strongest candidate of every target)."""
+    X, _ = synth.gaussian_sem(12, 2001, 9930)
+    plain = oracle_built.Dataset(np.delete(X, col, 1)).mmpc(0.01)
+    X[:, col] = 3.0
+    rows = oracle_built.Dataset(X).mmpc(0.01)
+    assert rows[col] == 0 and not any((r >> col) & 1 for r in rows)
+    # the other eleven keep the skeleton they have without that column
+    squeeze = lambda r: (r & ((1 << col) - 1)) | (r >> (col + 1) << col)
+    assert [squeeze(r) for i, r in enumerate(rows) if i != col] == plain
+
+
 def test_cli_help():
     r = subprocess.run([MMPC, "--help"], capture_output=True, text=True)
     assert r.returncode == 0 and "--alpha" in r.stdout

@@ -66,6 +66,7 @@ def lib():
         L.ulg_triplet_solve.argtypes = [P, P, I64, I, P, P]
         L.ulg_triplet_memo_put.argtypes = [P, P, I64, I, P]
         L.ulg_mmpc.argtypes = [P, D, I, P]
+        L.ulg_mmpc_min_z.argtypes = [P, I64, P, P, P, P, I, P, P]
         L.ulg_pss_format.argtypes = [P, C.c_char_p, P, P, C.POINTER(C.c_void_p), C.POINTER(I64)]
         L.ulg_pss_format_lists.argtypes = [P, I, P, P, P, C.c_char_p, P, P, C.POINTER(C.c_void_p), C.POINTER(I64)]
         L.ulg_astar_scc.argtypes = [P, P, I, I, C.c_uint64, C.c_uint64, P, P, C.POINTER(F), C.POINTER(I64),
@@ -145,6 +146,22 @@ class Context:
         rows = np.zeros(64, dtype=np.uint64)
         self._check(lib().ulg_mmpc(self._h, float(alpha), int(max_cond), _ptr(rows)), "ulg_mmpc")
         return [int(x) for x in rows[:self.n]]
+
+    def mmpc_min_z(self, ts, xs, musts, pools, max_cond=-1, stops=None) -> np.ndarray:
+        """ulg_mmpc_min_z: per query the minimum |Fisher z| of (xs[i], ts[i] | S) over the
+        subsets S of pools[i] (a variable mask) with |S| <= max_cond that contain musts[i]
+        (< 0: every subset), stopping at the first value <= stops[i] (default -inf: never)."""
+        t = np.ascontiguousarray(ts, dtype=np.int32)
+        x = np.ascontiguousarray(xs, dtype=np.int32)
+        m = np.ascontiguousarray(musts, dtype=np.int32)
+        p = np.ascontiguousarray([int(v) for v in pools], dtype=np.uint64)
+        s = np.full(len(t), -np.inf) if stops is None else np.ascontiguousarray(stops, dtype=np.float64)
+        if not (t.shape == x.shape == m.shape == p.shape == s.shape):
+            raise ValueError("mmpc_min_z: ts, xs, musts, pools and stops differ in length")
+        out = np.zeros(max(len(t), 1), dtype=np.float64)
+        self._check(lib().ulg_mmpc_min_z(self._h, len(t), _ptr(t), _ptr(x), _ptr(m), _ptr(p), int(max_cond), _ptr(s),
+                                         _ptr(out)), "ulg_mmpc_min_z")
+        return out[:len(t)]
 
     def gram(self) -> np.ndarray:
         g = np.empty((self.n, self.n), dtype=np.float64)

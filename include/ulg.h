@@ -207,8 +207,11 @@ int ulg_cbic_set_constraints(ulg_ctx *ctx, int count, const int *vars,
 int ulg_cbic_score_sets(ulg_ctx *ctx, int64_t count, const int *vars,
                         const uint64_t *parents, float *neg_scores);
 
-/* ---- discrete BIC scoring (bic_scoring_function.cpp, log_likelihood_calculator.cpp) ---- */
+/* ---- discrete scoring: BIC (bic_scoring_function.cpp, log_likelihood_calculator.cpp)
+ *      and BDeu (bdeu_scoring_function.cpp) ---- */
 #define ULG_SCORE_BIC 1
+/* 2 is not a kind: it has always been refused with ULG_ERR_ARG and stays so. */
+#define ULG_SCORE_BDEU 3
 /* codes_colmajor: N x n value codes, column-major (column j = variable j);
  * arity[j] = cardinality of variable j.  n <= 63, 1 <= arity <= 255,
  * 2 <= N < 2^31.  Every code must be below its column's arity; the upload
@@ -219,7 +222,8 @@ int ulg_cbic_score_sets(ulg_ctx *ctx, int64_t count, const int *vars,
  * likewise.  Either load clears ulg_cbic_set_constraints. */
 int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n, const int *arity);
 /* ulg_cbic_score's arguments and counts for a discrete score (kind =
- * ULG_SCORE_BIC; anything else is ULG_ERR_ARG).  max_parents is taken as
+ * ULG_SCORE_BIC or ULG_SCORE_BDEU, see below; anything else is ULG_ERR_ARG).
+ * What follows is the BIC value.  max_parents is taken as
  * given (< 1 or > n - 1 means n - 1): the BIC limit log(2N / log N) is the
  * command line's job (score_main.cpp:300-304).  The value of (v, P) is
  *   sum_cells n_jk ln n_jk - sum_j n_j ln n_j - (r_v - 1) prod_{p in P} r_p ln(N) / 2
@@ -250,11 +254,39 @@ int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n,
  * slot; with 0 no kernel runs and nothing is allocated.  total_stored then
  * counts the kept sets, total_scored is unchanged and
  * ulg_get_info("disc_pruned") gives the sets removed (0 with the option off).
- * ulg_disc_score_sets, ulg_disc_counts and ulg_cbic_* ignore the option. */
+ * ulg_disc_score_sets, ulg_disc_counts and ulg_cbic_* ignore the option.
+ *
+ * kind = ULG_SCORE_BDEU: the Bayesian Dirichlet equivalent uniform score with
+ * equivalent sample size ess (ulg_disc_set_ess).  With r = r_v, q = prod r_p,
+ *   a_j = ess / q,  a_jk = ess / (q r)                                  (FP64)
+ *   s(v, P) = sum over non-empty cells   [ lgamma(a_jk + n_jk) - lgamma(a_jk) ]
+ *           + sum over non-empty configs [ lgamma(a_j) - lgamma(a_j + n_j) ]
+ * Each bracketed term is computed in FP64 from the exact integer count and
+ * rounded once to a fixed-point integer (scale 2^-shift, a function of N and
+ * ess: csrc/disc_bdeu.h); the integer sum is converted back and rounded to
+ * float once.  The value is therefore bit-identical on the dense and sparse
+ * counting paths, across calls and for any grid.  Everything else is as for
+ * BIC: the store rule (the empty set iff < 1, every other set iff < 0), 0 for
+ * a variable of arity 1, 1 and never stored for a set that violates the
+ * constraints, ULG_ERR_UNSUPPORTED from 2^63 cells or above
+ * ULG_MAX_PARENTS_GPU parents, time_limit_ms, option "disc_prune" and every
+ * ulg_get_info value.  BDeu has no parent limit of its own: the reference
+ * applies log(2N / log N) to "bic" only (score_main.cpp:300-304).
+ * Two departures from the reference: it keeps a_j, a_jk, their lgamma and the
+ * running sum in float, and it computes q r in int, which overflows from 2^31
+ * cells on; here a_j and a_jk are FP64 for every q r < 2^63 and the sum is
+ * exact, as for BIC.  De Campos pruning (enableDeCamposPruning) is not built.
+ * Replaces BDeuScoringFunction::lg, calculateScore and calculate
+ * (bdeu_scoring_function.cpp:21-35, 69-79, 117-166). */
 int ulg_disc_score(ulg_ctx *ctx, int kind, const int *vars, int nv, const uint64_t *candidates,
                    int max_parents, int64_t *total_stored, int64_t *total_scored);
-/* calculateScore(vars[i], parents[i]) for arbitrary pairs: the value above
- * without the store rule (a violating set gives 1). */
+/* The equivalent sample size of ULG_SCORE_BDEU: sticky, default 1.0, kept
+ * across ulg_disc_load; nothing but BDeu reads it.  ess must be finite with
+ * 1e-6 <= ess <= 1e6; anything else is ULG_ERR_ARG and leaves the previous
+ * value. */
+int ulg_disc_set_ess(ulg_ctx *ctx, double ess);
+/* calculateScore(vars[i], parents[i]) for arbitrary pairs: the value above (of
+ * either kind) without the store rule (a violating set gives 1). */
 int ulg_disc_score_sets(ulg_ctx *ctx, int kind, int64_t count, const int *vars,
                         const uint64_t *parents, float *scores);
 /* diagnostics: the dense contingency table of one (variable, parent set).

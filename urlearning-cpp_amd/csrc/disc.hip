@@ -1,5 +1,6 @@
-// disc.hip -- discrete BIC scoring (ulg_disc_*): contingency counts of the
-// records per (variable, parent set), then the n ln n reduction.
+// disc.hip -- discrete scoring (ulg_disc_*): contingency counts of the
+// records per (variable, parent set), then the score's reduction of those
+// counts: n ln n terms and the penalty for BIC, lgamma terms for BDeu.
 //
 // Replaces, for `score -f BIC`, the reference's RecordFile / ADTree state
 // (score/score_main.cpp:283-292), the AD-tree count queries
@@ -22,6 +23,15 @@
 // the float it is rounded to once -- does not depend on the path, the hash
 // placement or the scheduling.
 //
+// The reduction is a compile-time policy (BicReduce, BdeuReduce below) of
+// decode_item, sparse_count, item_value and the two scoring kernels: what
+// thread 0 prepares per item, the term of a cell, the term of a parent
+// configuration and the float made of the integer sum.  BDeu (ULG_SCORE_BDEU,
+// csrc/disc_bdeu.h) replaces BDeuScoringFunction::calculateScore and calculate
+// (bdeu_scoring_function.cpp:21-35, 69-79, 117-166) with the same counting and
+// its own terms [lgamma(a_jk + n_jk) - lgamma(a_jk)] and
+// [lgamma(a_j) - lgamma(a_j + n_j)].
+//
 // Option disc_prune adds the reference's prune() (score_calculator.cpp:
 // 137-197, disabled in its score_main.cpp:166-171) between the last layer and
 // the compaction: disc_prune_kernel below.
@@ -29,6 +39,7 @@
 #include <chrono>
 #include <cmath>
 
+#include "disc_bdeu.h"  // BdeuItem, bdeu_cell_term, bdeu_cfg_term, bdeu_fix, bdeu_shift
 #include "disc_dev.h"  // DiscData, fix_nlogn, disc_ready, disc_data
 #include "disc_prune.h"  // for_each_subset_rank, kPruneTwoEps
 #include "ulg_internal.h"
@@ -61,6 +72,42 @@ struct Item {
     uint64_t q, cells, mask;
     int col[ULG_MAX_PARENTS_GPU];
     uint64_t base[ULG_MAX_PARENTS_GPU];
+    BdeuItem bdeu;             // BdeuReduce only
+};
+
+// ---- the reductions ----------------------------------------------------------
+// prepare(): thread 0, once per decoded item that is counted.  cell() / config():
+// the fixed-point term of a count (0 for an empty one).  finish(): the value
+// from the integer sum.
+struct BicReduce {
+    __device__ __forceinline__ void prepare(Item &) const {}
+    __device__ __forceinline__ long long cell(const DiscData &D, const Item &, unsigned int c) const {
+        return fix_nlogn(c, D.shift);
+    }
+    __device__ __forceinline__ long long config(const DiscData &D, const Item &, unsigned int nj) const {
+        return -fix_nlogn(nj, D.shift);
+    }
+    // R4: the log-likelihood from the exact counts, the penalty, one rounding
+    __device__ __forceinline__ float finish(const DiscData &D, const Item &it, long long sum) const {
+        const double ll = ldexp((double)sum, -D.shift);
+        const double pen = (double)(it.rv - 1) * (double)it.q * D.half_ln_N;
+        return (float)(ll - pen);
+    }
+};
+
+struct BdeuReduce {
+    double ess;
+    int shift;  // bdeu_shift(N, ess)
+    __device__ __forceinline__ void prepare(Item &it) const { it.bdeu = bdeu_item(ess, it.q, it.cells); }
+    __device__ __forceinline__ long long cell(const DiscData &, const Item &it, unsigned int c) const {
+        return c ? bdeu_fix(bdeu_cell_term(it.bdeu, c), shift) : 0;
+    }
+    __device__ __forceinline__ long long config(const DiscData &, const Item &it, unsigned int nj) const {
+        return nj ? bdeu_fix(bdeu_cfg_term(it.bdeu, nj), shift) : 0;
+    }
+    __device__ __forceinline__ float finish(const DiscData &, const Item &, long long sum) const {
+        return (float)bdeu_unfix(sum, shift);
+    }
 };
 
 __device__ __forceinline__ bool disc_violates(const uint64_t *ct, int n, int v, uint64_t set) {
@@ -75,7 +122,8 @@ __device__ __forceinline__ bool disc_violates(const uint64_t *ct, int n, int v, 
 // Thread 0: the item's parents (ascending variable order), bases and table
 // size; R5 (arity 1) and R6 (constraints) settle the value without counting.
 // The host has checked that q r_v < 2^63 for every set of the call.
-__device__ void decode_item(const DiscData &D, int v, uint64_t pmask, const uint64_t *cons, Item &it) {
+template <class R>
+__device__ void decode_item(const DiscData &D, const R &red, int v, uint64_t pmask, const uint64_t *cons, Item &it) {
     it.v = v;
     it.mask = pmask;
     it.rv = D.arity[v];
@@ -97,7 +145,9 @@ __device__ void decode_item(const DiscData &D, int v, uint64_t pmask, const uint
         it.value = 1.0f;  // bic_scoring_function.cpp:34-37
     } else if (it.rv == 1) {
         it.skip = 1;
-        it.value = 0.0f;  // penalty 0, log-likelihood 0
+        it.value = 0.0f;  // penalty 0, log-likelihood 0; BDeu: every cell term cancels its configuration's
+    } else {
+        red.prepare(it);
     }
 }
 
@@ -111,9 +161,9 @@ __device__ __forceinline__ uint64_t cell_of(const DiscData &D, const Item &it, i
 // Counts the item's records in the hash table (keys / cnt, hslots entries) and
 // adds the fixed-point terms to *acc; counts_out (optional) receives the
 // non-empty cells of the dense table.
-template <class KP, class CP>
-__device__ __forceinline__ void sparse_count(const DiscData &D, const Item &it, KP keys, CP cnt, uint64_t hslots,
-                                             unsigned long long *acc, int32_t *counts_out) {
+template <class R, class KP, class CP>
+__device__ __forceinline__ void sparse_count(const DiscData &D, const R &red, const Item &it, KP keys, CP cnt,
+                                             uint64_t hslots, unsigned long long *acc, int32_t *counts_out) {
     const int tid = threadIdx.x;
     for (uint64_t h = tid; h < hslots; h += kDiscBlock) {
         keys[h] = kEmptyKey;
@@ -143,11 +193,10 @@ __device__ __forceinline__ void sparse_count(const DiscData &D, const Item &it, 
         const unsigned long long key = keys[h];
         if (key == kEmptyKey) continue;
         const unsigned int c = cnt[h];
-        const long long f = fix_nlogn(c, D.shift);
         if (key & kCfgTag) {
-            a -= f;
+            a += red.config(D, it, c);
         } else {
-            a += f;
+            a += red.cell(D, it, c);
             if (counts_out) counts_out[key] = (int32_t)c;
         }
     }
@@ -158,8 +207,9 @@ __device__ __forceinline__ void sparse_count(const DiscData &D, const Item &it, 
 // The whole workgroup: the value of the decoded item `it` (in LDS).  smem:
 // the dynamic LDS behind the item (histogram or hash table).  counts_out
 // (optional, zeroed by the caller, it.cells entries): the dense table.
-__device__ float item_value(const DiscData &D, const DiscWork &W, const Item &it, unsigned long long *acc,
-                            unsigned char *smem, int32_t *counts_out, bool count_path) {
+template <class R>
+__device__ float item_value(const DiscData &D, const DiscWork &W, const R &red, const Item &it,
+                            unsigned long long *acc, unsigned char *smem, int32_t *counts_out, bool count_path) {
     const int tid = threadIdx.x;
     if (it.skip && !counts_out) return it.value;
     if (tid == 0) *acc = 0ull;
@@ -182,9 +232,9 @@ __device__ float item_value(const DiscData &D, const DiscWork &W, const Item &it
             for (int kk = 0; kk < it.rv; ++kk) {
                 const unsigned int c = (unsigned int)hist[j + kk * q];
                 nj += c;
-                a += fix_nlogn(c, D.shift);
+                a += red.cell(D, it, c);
             }
-            a -= fix_nlogn(nj, D.shift);
+            a += red.config(D, it, nj);
         }
         if (a) atomicAdd(acc, (unsigned long long)a);
         if (counts_out)
@@ -195,19 +245,16 @@ __device__ float item_value(const DiscData &D, const DiscWork &W, const Item &it
         if (W.hash_lds) {
             unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
             unsigned int *cnt = reinterpret_cast<unsigned int *>(keys + W.hslots);
-            sparse_count(D, it, keys, cnt, W.hslots, acc, counts_out);
+            sparse_count(D, red, it, keys, cnt, W.hslots, acc, counts_out);
         } else {
             unsigned long long *keys = W.slab + (uint64_t)blockIdx.x * (W.hslots + W.hslots / 2);
             unsigned int *cnt = reinterpret_cast<unsigned int *>(keys + W.hslots);
-            sparse_count(D, it, keys, cnt, W.hslots, acc, counts_out);
+            sparse_count(D, red, it, keys, cnt, W.hslots, acc, counts_out);
         }
         if (count_path && tid == 0) atomicAdd(&W.word[2], 1ull);
     }
     if (it.skip) return it.value;
-    // R4: the log-likelihood from the exact counts, the penalty, one rounding
-    const double ll = ldexp((double)(long long)*acc, -D.shift);
-    const double pen = (double)(it.rv - 1) * (double)it.q * D.half_ln_N;
-    return (float)(ll - pen);
+    return red.finish(D, it, (long long)*acc);
 }
 
 // ---- upload check ------------------------------------------------------------
@@ -232,7 +279,8 @@ struct LayerArgs {
     int nv, S, L;
 };
 
-__global__ void __launch_bounds__(kDiscBlock) disc_layer_kernel(DiscData D, DiscWork W, LayerArgs A) {
+template <class R>
+__global__ void __launch_bounds__(kDiscBlock) disc_layer_kernel(DiscData D, DiscWork W, LayerArgs A, R red) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ Item it;
     __shared__ unsigned long long acc;
@@ -255,10 +303,10 @@ __global__ void __launch_bounds__(kDiscBlock) disc_layer_kernel(DiscData D, Disc
                 --c;
             }
             slot = A.toff[(uint64_t)i * A.S + A.L] + (w - A.work[i]);
-            decode_item(D, A.vm[2 * i], pmask, A.cons, it);
+            decode_item(D, red, A.vm[2 * i], pmask, A.cons, it);
         }
         __syncthreads();
-        const float val = item_value(D, W, it, &acc, smem, nullptr, true);
+        const float val = item_value(D, W, red, it, &acc, smem, nullptr, true);
         if (threadIdx.x == 0) {
             // R3: the empty set is stored iff < 1, every other set iff < 0
             const bool keep = A.L == 0 ? val < 1.0f : val < 0.0f;
@@ -325,17 +373,18 @@ __global__ void __launch_bounds__(kDiscBlock) disc_prune_kernel(PruneArgs A) {
 }
 
 // ---- arbitrary pairs / one table ---------------------------------------------
+template <class R>
 __global__ void __launch_bounds__(kDiscBlock)
 disc_sets_kernel(DiscData D, DiscWork W, const uint64_t *pairs, int64_t count, const uint64_t *cons, float *out,
-                 int32_t *counts_out) {
+                 int32_t *counts_out, R red) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ Item it;
     __shared__ unsigned long long acc;
     for (int64_t w = blockIdx.x; w < count; w += gridDim.x) {
         __syncthreads();
-        if (threadIdx.x == 0) decode_item(D, (int)pairs[2 * w], pairs[2 * w + 1], cons, it);
+        if (threadIdx.x == 0) decode_item(D, red, (int)pairs[2 * w], pairs[2 * w + 1], cons, it);
         __syncthreads();
-        const float val = item_value(D, W, it, &acc, smem, counts_out, false);
+        const float val = item_value(D, W, red, it, &acc, smem, counts_out, false);
         if (threadIdx.x == 0 && out) out[w] = val;
     }
 }
@@ -464,6 +513,10 @@ int disc_work(ulg_ctx *c, uint64_t max_cells, uint64_t items, DiscWork &W, size_
     return ULG_OK;
 }
 
+bool kind_ok(int kind) { return kind == ULG_SCORE_BIC || kind == ULG_SCORE_BDEU; }
+
+BdeuReduce bdeu_reduce(const ulg_ctx *c) { return BdeuReduce{c->disc_ess, bdeu_shift(c->N, c->disc_ess)}; }
+
 }  // namespace
 
 extern "C" {
@@ -519,7 +572,7 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     if (!c) return ULG_ERR_ARG;
     if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score: call ulg_disc_load first");
-    if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC");
+    if (!kind_ok(kind)) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC or ULG_SCORE_BDEU");
     ScoreLists &ls = c->lists;
     const ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents);
     if (st != ScoreLists::kOk && st != ScoreLists::kTooWide) return lists_error(c, "ulg_disc_score", st);
@@ -570,7 +623,10 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     size_t lds = 0;
     unsigned grid_cap = 1;
     if ((rc = disc_work(c, max_cells, total_slots, W, lds, grid_cap))) return rc;
-    ULG_HIP(c, hipFuncSetAttribute((const void *)disc_layer_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // each instantiation is a kernel of its own, with its own attribute
+    const bool bdeu = kind == ULG_SCORE_BDEU;
+    const void *layer_fn = bdeu ? (const void *)disc_layer_kernel<BdeuReduce> : (const void *)disc_layer_kernel<BicReduce>;
+    ULG_HIP(c, hipFuncSetAttribute(layer_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_vm.p, vm.data(), vm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -600,7 +656,11 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             A.L = L;
             A.work = c->d_disc_meta.p + (size_t)nv * S + 1 + (size_t)L * (nv + 1);
             prof_begin(c, "disc_layer");
-            disc_layer_kernel<<<(unsigned)std::min<uint64_t>(items, grid_cap), kDiscBlock, lds, c->stream>>>(D, W, A);
+            const unsigned grid = (unsigned)std::min<uint64_t>(items, grid_cap);
+            if (bdeu)
+                disc_layer_kernel<BdeuReduce><<<grid, kDiscBlock, lds, c->stream>>>(D, W, A, bdeu_reduce(c));
+            else
+                disc_layer_kernel<BicReduce><<<grid, kDiscBlock, lds, c->stream>>>(D, W, A, BicReduce{});
             prof_end(c);
             ULG_HIP(c, hipGetLastError());
         }
@@ -667,8 +727,8 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
 }
 
 // the pairs on the device, the counting resources and one launch of disc_sets_kernel
-static int disc_sets_launch(ulg_ctx *c, const char *what, int64_t count, const int *vars, const uint64_t *parents,
-                            float *out_dev, int32_t *counts_dev) {
+static int disc_sets_launch(ulg_ctx *c, const char *what, int kind, int64_t count, const int *vars,
+                            const uint64_t *parents, float *out_dev, int32_t *counts_dev) {
     const int n = c->n;
     const uint64_t allmask = (1ull << n) - 1ull;
     std::vector<uint64_t> pairs((size_t)count * 2);
@@ -696,12 +756,18 @@ static int disc_sets_launch(ulg_ctx *c, const char *what, int64_t count, const i
     size_t lds = 0;
     unsigned grid = 1;
     if ((rc = disc_work(c, max_cells, (uint64_t)count, W, lds, grid))) return rc;
-    ULG_HIP(c, hipFuncSetAttribute((const void *)disc_sets_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const bool bdeu = kind == ULG_SCORE_BDEU;
+    const void *sets_fn = bdeu ? (const void *)disc_sets_kernel<BdeuReduce> : (const void *)disc_sets_kernel<BicReduce>;
+    ULG_HIP(c, hipFuncSetAttribute(sets_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ULG_HIP(c, hipMemcpyAsync(c->d_sets_in.p, pairs.data(), (size_t)count * 16, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, "disc_sets");
-    disc_sets_kernel<<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count,
-                                                           c->cons_var.empty() || counts_dev ? nullptr : c->d_cons_var.p,
-                                                           out_dev, counts_dev);
+    const uint64_t *cons = c->cons_var.empty() || counts_dev ? nullptr : c->d_cons_var.p;
+    if (bdeu)
+        disc_sets_kernel<BdeuReduce><<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count, cons,
+                                                                           out_dev, counts_dev, bdeu_reduce(c));
+    else
+        disc_sets_kernel<BicReduce><<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count, cons,
+                                                                          out_dev, counts_dev, BicReduce{});
     prof_end(c);
     ULG_HIP(c, hipGetLastError());
     ULG_HIP(c, hipStreamSynchronize(c->stream));  // `pairs` is a pageable source
@@ -714,11 +780,12 @@ int ulg_disc_score_sets(ulg_ctx *c, int kind, int64_t count, const int *vars, co
     if (!c || count < 0 || (count > 0 && (!vars || !parents || !scores))) return ULG_ERR_ARG;
     if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score_sets: call ulg_disc_load first");
-    if (kind != ULG_SCORE_BIC) return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC");
+    if (!kind_ok(kind))
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC or ULG_SCORE_BDEU");
     if (count == 0) return ULG_OK;
     int rc;
     if ((rc = ensure(c, c->qbuf_out, (size_t)count))) return rc;
-    if ((rc = disc_sets_launch(c, "ulg_disc_score_sets", count, vars, parents, c->qbuf_out.p, nullptr))) return rc;
+    if ((rc = disc_sets_launch(c, "ulg_disc_score_sets", kind, count, vars, parents, c->qbuf_out.p, nullptr))) return rc;
     ULG_HIP(c, hipMemcpy(scores, c->qbuf_out.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return ULG_OK;
 }
@@ -738,7 +805,7 @@ int ulg_disc_counts(ulg_ctx *c, int var, uint64_t parents, int32_t *counts, int6
     int rc;
     if ((rc = ensure(c, c->d_disc_counts, (size_t)cells))) return rc;
     ULG_HIP(c, hipMemsetAsync(c->d_disc_counts.p, 0, (size_t)cells * 4, c->stream));
-    if ((rc = disc_sets_launch(c, "ulg_disc_counts", 1, &var, &P, nullptr, c->d_disc_counts.p))) return rc;
+    if ((rc = disc_sets_launch(c, "ulg_disc_counts", ULG_SCORE_BIC, 1, &var, &P, nullptr, c->d_disc_counts.p))) return rc;
     ULG_HIP(c, hipMemcpy(counts, c->d_disc_counts.p, (size_t)cells * 4, hipMemcpyDeviceToHost));
     return ULG_OK;
 }

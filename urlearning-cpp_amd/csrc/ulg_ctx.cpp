@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "disc_bdeu.h"  // kBdeuEssMin, kBdeuEssMax
 #include "search_internal.h"
 
 namespace ulg {
@@ -176,6 +177,15 @@ void ulg_destroy(ulg_ctx *c) {
 }
 
 const char *ulg_last_error(const ulg_ctx *c) { return c ? c->err.c_str() : "null context"; }
+
+int ulg_disc_set_ess(ulg_ctx *c, double ess) {
+    if (!c) return ULG_ERR_ARG;
+    // !(a <= x && x <= b) is also true for a NaN
+    if (!(ess >= ulg::kBdeuEssMin && ess <= ulg::kBdeuEssMax))
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_set_ess: ess must be finite, 1e-6 <= ess <= 1e6");
+    c->disc_ess = ess;
+    return ULG_OK;
+}
 
 int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return ULG_ERR_ARG;

@@ -145,6 +145,7 @@ struct ulg_ctx {
     ulg::DevBuf<uint64_t> d_disc_sets;            // per table slot: the set's variable mask
     ulg::DevBuf<unsigned long long> d_disc_slab;  // sparse path: per-workgroup hash tables
     ulg::DevBuf<unsigned long long> d_disc_word;  // [error word, dense sets, sparse sets, stored, pruned]
+    double disc_ess = 1.0;                        // ulg_disc_set_ess: BDeu's equivalent sample size (sticky)
     int disc_prune = 0;                           // ulg_disc_score: drop dominated sets (the reference's prune())
     int64_t disc_pruned = 0;                      // ... sets the last call dropped
     ulg::DevBuf<float> d_disc_best;               // ... per table slot: the best kept score among the set and its subsets

@@ -4,16 +4,22 @@
 // reference's exact text format.
 //
 //   score <in.csv> <out.pss> [-f BIC] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
+//   score <in.csv> <out.pss> --bdeu [-e ESS] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //
 // -f BIC (the default, as in the reference) is the discrete score: the tokens
 // of each column are its values (load_discrete_csv), the parent limit is
 // min(-p, (int) log(2N / log N)) (score_main.cpp:300-304) and --lambda is
-// ignored.  -f cBIC reads the columns as numbers.  BDeu and fNML are not
-// built; nor is --enableDeCamposPruning with -f BIC (experimental in the
-// reference).  Options that only matter for those or for the reference's
-// AD-tree (-m, -e, -w, -a, -o) are accepted; -e still feeds the "META ess"
-// header line as in score_main.cpp:388.
+// ignored.  -f cBIC reads the columns as numbers.  --bdeu is the discrete
+// BDeu score (the reference's -f BDeu -e ESS; -f BDeu itself keeps being
+// refused, as it was before BDeu was built): same reader, equivalent sample
+// size -e (default 1, 1e-6 .. 1e6), "META score_type = bdeu", and no parent
+// limit besides -p, since the reference applies log(2N / log N) to "bic" only
+// (score_main.cpp:300-304) -- without -p every subset of the candidates is
+// scored.  fNML is not built; nor is --enableDeCamposPruning with a discrete
+// score (experimental in the reference).  Options that only matter for the
+// reference's AD-tree or its other paths (-m, -w, -a, -o) are accepted; -e
+// feeds the "META ess" header line as in score_main.cpp:388 whatever the score.
 //
 // --prune (-f BIC only) applies the reference's end-of-scoring prune()
 // (score_calculator.cpp:137-197; its call is commented out in
@@ -44,14 +50,15 @@ int main(int argc, char **argv) {
             {"k", "skeleton", true, "", "The file specifying the skeleton superstructure"},
             {"m", "rMin", true, "5", "The minimum number of records in the AD-tree nodes (no effect: the counts are exact)."},
             {"f", "function", true, "BIC", "The scoring function to use (BIC or cBIC)."},
-            {"e", "ess", true, "1", "The equivalent sample size (written to META ess)."},
+            {"e", "ess", true, "1", "The equivalent sample size of --bdeu, 1e-6 to 1e6 (always written to META ess)."},
             {"p", "maxParents", true, "0", "The maximum number of parents for any variable. A value less than 1 means no limit."},
             {"t", "threads", true, "1", "Host threads in the reference; the GPU scores every variable at once."},
             {"r", "time", true, "-1", "The maximum amount of time (s) to use for each variable (every variable is scored at once: the budget of the whole call, checked after each layer). A value less than 1 means no limit."},
             {"s", "hasHeader", false, "", "Add this flag if the first line of the input file gives the variable names."},
             {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171; --prune runs it for -f BIC)."},
             {"", "prune", false, "", "Drop every parent set that a kept proper subset dominates (the reference's prune(); -f BIC only)."},
-            {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC."},
+            {"", "bdeu", false, "", "Score with BDeu (the reference's -f BDeu) and equivalent sample size -e. There is no BIC parent limit: without -p every subset of the candidates is scored."},
+            {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC and --bdeu."},
             {"", "device", true, "0", "HIP device to use."},
             {"h", "help", false, "", "Show this help message."},
         },
@@ -72,14 +79,27 @@ int main(int argc, char **argv) {
                      args.get("function").c_str());
         return 2;
     }
-    const bool discrete = sf == "bic";
+    const bool bdeu = args.has("bdeu");
+    if (bdeu && sf != "bic") {
+        std::fprintf(stderr, "score: --bdeu is a discrete score of its own; it does not go with -f %s\n",
+                     args.get("function").c_str());
+        return 2;
+    }
+    // boost::lexical_cast<float>(-e) in the reference; the same float, widened, is what BDeu uses
+    const double ess = (double)std::strtof(args.get("ess").c_str(), nullptr);
+    if (bdeu && !(ess >= 1e-6 && ess <= 1e6)) {
+        std::fprintf(stderr, "score: --bdeu needs 1e-6 <= -e <= 1e6 (got '%s')\n", args.get("ess").c_str());
+        return 2;
+    }
+    if (bdeu) sf = "bdeu";
+    const bool discrete = sf == "bic" || bdeu;
     if (discrete && args.has("enableDeCamposPruning")) {
-        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC (it is a no-op for -f cBIC)\n");
+        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC or --bdeu (it is a no-op for -f cBIC)\n");
         return 2;
     }
     const bool prune = args.has("prune");
     if (prune && !discrete) {
-        std::fprintf(stderr, "score: --prune is for -f BIC: the store rule of -f cBIC already tests dominance, and the "
+        std::fprintf(stderr, "score: --prune is for -f BIC and --bdeu: the store rule of -f cBIC already tests dominance, and the "
                              "reference disabled prune() for the continuous case\n");
         return 2;
     }
@@ -124,11 +144,14 @@ int main(int argc, char **argv) {
     if (discrete) {
         // score_main.cpp:300-304; the reference divides by log 1 at N = 1
         if (N < 2) {
-            std::fprintf(stderr, "score: -f BIC needs at least 2 records ('%s' has %lld)\n", input.c_str(), (long long)N);
+            std::fprintf(stderr, "score: %s needs at least 2 records ('%s' has %lld)\n", bdeu ? "--bdeu" : "-f BIC",
+                         input.c_str(), (long long)N);
             return 2;
         }
-        const int lim = (int)std::log(2 * (double)N / std::log((double)N));
-        if (lim < maxp) maxp = lim;
+        if (!bdeu) {
+            const int lim = (int)std::log(2 * (double)N / std::log((double)N));
+            if (lim < maxp) maxp = lim;
+        }
     }
     // -c: scoring::parseConstraints over the .pss names (score_main.cpp:314-317)
     const std::string cons_file = args.get("constraints");
@@ -175,8 +198,9 @@ int main(int argc, char **argv) {
         rc = ulg_cbic_set_constraints(ctx, (int)cons.vars.size(), cons.vars.data(), cons.required.data(),
                                       cons.forbidden.data());
     if (rc == ULG_OK && prune) rc = ulg_set_option(ctx, "disc_prune", 1);
+    if (rc == ULG_OK && bdeu) rc = ulg_disc_set_ess(ctx, ess);
     if (rc == ULG_OK)
-        rc = discrete ? ulg_disc_score(ctx, ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
+        rc = discrete ? ulg_disc_score(ctx, bdeu ? ULG_SCORE_BDEU : ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
                       : ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
     int64_t oot = 0, done_layer = 0, pruned = 0;
     if (rc == ULG_OK && prune) {
@@ -203,7 +227,7 @@ int main(int argc, char **argv) {
     {
         // boost::lexical_cast<std::string>(float)
         char buf[64];
-        std::snprintf(buf, sizeof buf, "%.9g", (double)std::strtof(args.get("ess").c_str(), nullptr));
+        std::snprintf(buf, sizeof buf, "%.9g", ess);
         h.ess = buf;
     }
     const std::string header = ulgio::pss_header_text(h);
@@ -233,11 +257,13 @@ int main(int argc, char **argv) {
                 (long long)len);
     char pruned_field[48] = "";
     if (prune) std::snprintf(pruned_field, sizeof pruned_field, ", \"pruned\": %lld", (long long)pruned);
+    char ess_field[48] = "";
+    if (bdeu) std::snprintf(ess_field, sizeof ess_field, ", \"ess\": %.9g", ess);
     std::fprintf(stderr,
                  "ulg_metrics {\"tool\": \"score\", \"function\": \"%s\", \"n\": %d, \"N\": %lld, \"k\": %d, \"lambda\": %g, "
                  "\"scored\": %lld, \"stored\": %lld, \"score_s\": %.6f, \"sets_per_s\": %.6g, \"format_s\": %.6f, "
-                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d%s}\n",
+                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d%s%s}\n",
                  sf.c_str(), n, (long long)N, maxp, lambda, (long long)scored, (long long)stored, t1 - t0,
-                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot, pruned_field);
+                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot, pruned_field, ess_field);
     return 0;
 }

@@ -48,6 +48,7 @@ def lib():
         L.ulg_disc_load.argtypes = [P, P, I64, I, P]
         L.ulg_disc_score.argtypes = [P, I, P, I, P, I, C.POINTER(I64), C.POINTER(I64)]
         L.ulg_disc_score_sets.argtypes = [P, I, I64, P, P, P]
+        L.ulg_disc_set_ess.argtypes = [P, D]
         L.ulg_disc_counts.argtypes = [P, I, C.c_uint64, P, I64, C.POINTER(I64)]
         L.ulg_chi2_log_sf.argtypes = [D, D]
         L.ulg_chi2_log_sf.restype = D
@@ -242,8 +243,14 @@ class Context:
     def clear_constraints(self):
         self._check(lib().ulg_cbic_set_constraints(self._h, 0, None, None, None), "ulg_cbic_set_constraints")
 
-    # ---- discrete BIC -------------------------------------------------------
+    # ---- discrete BIC and BDeu ----------------------------------------------
     SCORE_BIC = 1
+    SCORE_BDEU = 3
+
+    def set_ess(self, ess: float):
+        """ulg_disc_set_ess: the equivalent sample size of SCORE_BDEU (sticky, default 1.0,
+        1e-6 <= ess <= 1e6; a refused value leaves the previous one)."""
+        self._check(lib().ulg_disc_set_ess(self._h, float(ess)), "ulg_disc_set_ess")
 
     def load_discrete(self, codes: np.ndarray, arity):
         """ulg_disc_load: codes = N x n array of value codes (rows = records),
@@ -262,14 +269,19 @@ class Context:
         self.n = n
         self.N = N
 
-    def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC, prune=None):
+    def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC, prune=None, ess=None):
         """ulg_disc_score -> (total_stored, total_scored); fetch() reads the lists.
+        kind: SCORE_BIC or SCORE_BDEU.
         prune: True / False sets option "disc_prune" (sticky) before the call -- the
         reference's prune(): a set goes when a kept proper subset scores at least as
         well; total_stored then counts the kept sets and info("disc_pruned") the
-        removed ones.  None leaves the option as it is."""
+        removed ones.  None leaves the option as it is.
+        ess: set_ess(ess) before the call (sticky; only SCORE_BDEU reads it).  None
+        leaves it as it is."""
         if prune is not None:
             self.set_option("disc_prune", 1 if prune else 0)
+        if ess is not None:
+            self.set_ess(ess)
         v = np.ascontiguousarray(variables, dtype=np.int32)
         c = np.ascontiguousarray(candidates, dtype=np.uint64)
         st, sc = C.c_int64(), C.c_int64()
@@ -278,8 +290,11 @@ class Context:
         self._nv = len(v)
         return st.value, sc.value
 
-    def score_sets_discrete(self, variables, parents, kind: int = SCORE_BIC) -> np.ndarray:
-        """BICScoringFunction::calculateScore's value per (variable, parent mask) pair (ulg_disc_score_sets)."""
+    def score_sets_discrete(self, variables, parents, kind: int = SCORE_BIC, ess=None) -> np.ndarray:
+        """calculateScore's value (BIC or BDeu, by kind) per (variable, parent mask) pair
+        (ulg_disc_score_sets).  ess: as in score_discrete."""
+        if ess is not None:
+            self.set_ess(ess)
         v = np.ascontiguousarray(variables, dtype=np.int32)
         p = np.ascontiguousarray(parents, dtype=np.uint64)
         if v.shape != p.shape:

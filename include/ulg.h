@@ -517,6 +517,12 @@ int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_co
  * and 241 only, and not under time_limit_ms, whose budget is checked after every
  * layer; lists identical either way; C3 layers 1-3: 40 us against 54 us
  * for six launches, layer 4 in it 340 us: too many sets for one workgroup).
+ * "score_unrank_lut" (0..2^31-1, default 2^20): the layer launches of 4 to 8
+ * parents read each set's members from a table rank -> set of C(U, l) 32-bit
+ * masks per (candidates U <= 32, members l), filled once per context the
+ * first time a call needs it and shared by every variable, layer and call;
+ * the value is the largest such table in entries, 0 = every lane computes
+ * the mapping as before.  Lists and scores are bit-identical either way.
  * "disc_dense_cells" (1..32768, default 16384): a discrete set whose
  * contingency table has at most this many cells is counted in an int32 LDS
  * histogram; larger tables are counted in a hash table of their non-empty

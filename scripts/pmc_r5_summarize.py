@@ -12,7 +12,12 @@ walk_sliced_kernel<6, 1, K>).
   a divergent 4-byte gather costs one per distinct 128-byte line per lane);
 * ta_busy_frac = (TA_TA_BUSY_sum / 256 CUs) / (GRBM_GUI_ACTIVE / 8 XCDs):
   the fraction of the kernel's cycles the average CU's texture-address unit
-  is busy.
+  is busy;
+* valu_busy_frac = SQ_ACTIVE_INST_VALU x 4 / (1,024 SIMDs x kernel cycles):
+  the SQ ACTIVE / WAIT / WAVE_CYCLES counters count quad-cycles, so x 4 gives
+  the cycles some wave's VALU instruction was issuing, summed over all SIMDs
+  (round 6's counters: 83.56 M x 4 / 1,024 = 326 K of 398 K cycles = 0.82;
+  DESIGN.md §3.1n).
 
     python scripts/pmc_r5_summarize.py gpurun_out/<tag> > profiles/r6/pmc_scorer.json
 """
@@ -27,8 +32,11 @@ import sys
 # grid, i.e. the full-layer launches of one stream per context)
 # round 6: variant 241 (V = 209) and the key-sorted walk (walk_bucket_kernel;
 # its count / scatter kernels are summed in as "sort" when present)
-KERNELS = {"score": "score_layer_kernel<6, 1, 209>", "walk": "walk_bucket_kernel<6, 1, "}
-N_CU, N_XCD = 256, 8
+# round 15: the phase-0 launch (sets with variable 0) beside them, counters only
+KERNELS = {"score": "score_layer_kernel<6, 1, 209>", "walk": "walk_bucket_kernel<6, 1, ",
+           "score_var0": "score_layer_kernel<6, 0, 209>"}
+PAIR = ("score", "walk")  # the launch pair the traffic and L1 totals are summed over
+N_CU, N_XCD, N_SIMD = 256, 8, 1024
 
 
 def per_dispatch(outdir):
@@ -74,8 +82,8 @@ def main():
         e = {}
         if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
             e["traffic_bytes"] = (2 * c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024
-            tr += e["traffic_bytes"]
-        if "TCP_TOTAL_CACHE_ACCESSES_sum" in c:
+            tr += e["traffic_bytes"] if k in PAIR else 0.0
+        if "TCP_TOTAL_CACHE_ACCESSES_sum" in c and k in PAIR:  # `sets` is the pair's launch
             e["l1_lines_per_set"] = c["TCP_TOTAL_CACHE_ACCESSES_sum"] / sets
             l1 += e["l1_lines_per_set"]
         if "TA_TA_BUSY_sum" in c and c.get("GRBM_GUI_ACTIVE"):
@@ -88,6 +96,8 @@ def main():
             e["salu_per_wave"] = c.get("SQ_INSTS_SALU", 0.0) / c["SQ_WAVES"]
         if "SQ_WAVE_CYCLES" in c and e.get("kernel_cycles_per_xcd"):
             e["resident_waves_per_simd"] = c["SQ_WAVE_CYCLES"] / (e["kernel_cycles_per_xcd"] * N_CU)
+        if "SQ_ACTIVE_INST_VALU" in c and e.get("kernel_cycles_per_xcd"):
+            e["valu_busy_frac"] = c["SQ_ACTIVE_INST_VALU"] * 4 / (N_SIMD * e["kernel_cycles_per_xcd"])
         if "TCP_TCC_READ_REQ_sum" in c and c["TCP_TCC_READ_REQ_sum"]:
             e["l1_to_l2_latency_cycles"] = c["TCP_TCC_READ_REQ_LATENCY_sum"] / c["TCP_TCC_READ_REQ_sum"]
         e["counters_per_dispatch"] = {kk: round(vv, 1) for kk, vv in c.items()

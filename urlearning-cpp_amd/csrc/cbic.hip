@@ -145,6 +145,7 @@ struct ScoreArgs {
     const int *meta;         // [nv][4]: variable, m, var0in, -
     const uint64_t *tbl_off; // [nv*S + 1] start of (vi, layer) slab
     const uint64_t *work;    // [nv + 1] prefix of this launch's sets
+    uint64_t total;          // work[nv], for the layer kernels' scalar search (wave_variable)
     float *table;
     float *hsub;                // variant bit 6: per slot, the maximum stored value over the set's
                                 // nonempty subsets (the set included; NaN = none), table layout
@@ -153,10 +154,16 @@ struct ScoreArgs {
     unsigned long long *err;    // the call's error word (kErrQueue: a walk-queue segment overflowed)
     uint8_t *qkey;              // bucketed walk launches: per queue entry, its walk key
     double N;
-    double lambda;
+    double pen;                 // lambda ln(N), the device's product (ulg_ctx::pen, penalty_kernel)
     int n, nv, S;
     int xcd;                    // remap blocks so each XCD takes a contiguous run of sets
     int hsub_out;               // write the subset maxima (0: the top layer's phase 1, never read)
+    // Unrank tables (option score_unrank_lut; CbicPlan::build_luts): lut[off + r]
+    // = unrank_colex(r, l, U) as 32 bits, for the (U, l) this launch unranks
+    // variable vi's sets with; lut_off[vi] = its offset, -1 = none (the lane
+    // computes).  Both null: no table in this launch.
+    const uint32_t *lut;
+    const int32_t *lut_off;     // [nv], this launch's (layer, phase)
 };
 
 // Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8),
@@ -202,14 +209,14 @@ __device__ __forceinline__ const uint64_t *cons_stage(unsigned char *smem, int l
 }
 
 
-// LDS carve: gram | binom | work | tbl_off | meta | candidate lists |
+// LDS carve: gram | binom | work, this launch's unrank-table offsets | tbl_off | meta | candidate lists |
 // recursion stack (variant bit 1)
 // | LDS bitsets (3 per lane when they have >= 4 words) | the block's
 // undecided sets after the subset-maxima test (variant bits 4 + 6: a count,
 // then per entry compact mask, slot, ts, children maximum, variable) (16-B
 // aligned)
 struct LdsLayout {
-    int gram, binom, work, toff, meta, cand, stack, bits, cmp, cmp2, total;
+    int gram, binom, work, lutoff, toff, meta, cand, stack, bits, cmp, cmp2, total;
 };
 constexpr int kCmpEntryBytes = 8 + 4 + 4 + 4 + 4;
 __host__ __device__ inline int align16(int x) { return (x + 15) & ~15; }
@@ -235,7 +242,8 @@ __host__ __device__ inline LdsLayout lds_layout(int n, int nv, int S, int L, int
         const int ra = l.cmp + 16;             // the shared region
         l.gram = ra;
         l.work = align16(l.gram + n * n * 8);
-        l.cand = align16(l.work + (nv + 1) * 8);
+        l.lutoff = l.work + (nv + 1) * 8;  // [nv] int32, read where work[] is: a straddling wave's lanes
+        l.cand = align16(l.lutoff + nv * 4);
         l.stack = l.bits = align16(l.cand + nv * 64);
         l.cmp2 = align16(ra + kBlock * kCmpEntryBytes);
         const int endc = l.cmp2 + 2 * W * kBlock * 8;
@@ -245,7 +253,8 @@ __host__ __device__ inline LdsLayout lds_layout(int n, int nv, int S, int L, int
     l.gram = 0;
     l.binom = align16(l.gram + n * n * 8);
     l.work = align16(l.binom + 64 * kBinomK * 4);
-    l.toff = align16(l.work + (nv + 1) * 8);
+    l.lutoff = l.work + (nv + 1) * 8;
+    l.toff = align16(l.lutoff + nv * 4);
     l.meta = align16(l.toff + (nv * S + 1) * 8);
     l.cand = align16(l.meta + nv * 4 * 4);
     l.stack = align16(l.cand + nv * 64);
@@ -429,17 +438,87 @@ struct SetHead {
     uint64_t cm, rankP;
     int gv[L];
 };
-template <int L, int PHASE>
+// out[r] = unrank_colex(r, l, U) for r < count = C(U, l): a context's unrank
+// table (score_plan.h LutCache), equal to the computed mapping by construction.
+__global__ void __launch_bounds__(kBlock) unrank_lut_fill_kernel(uint32_t *out, uint32_t count, int l, int U,
+                                                                 const uint32_t *binom) {
+    const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r < count) out[r] = (uint32_t)unrank_colex(r, l, U, binom);
+}
+
+// *out = lambda ln(N) with the device's logarithm and one rounded product:
+// the value every lane used to compute inside the score's last expression.
+__global__ void penalty_kernel(double N, double lambda, double *out) { *out = lambda * log(N); }
+
+// The variable of a whole wave of a layer launch, found on the scalar unit
+// before the block fills its LDS: the wave's first and last set (lane 0's gid
+// and 63 further, clamped to the launch's last set like the lanes' own) are
+// wave-uniform, so the search of the launch's prefixes runs in SGPRs on scalar
+// loads of a.work.  vi >= 0: every lane's set belongs to variable vi, whose
+// sets start at `base`; -1: the wave straddles a boundary and each lane
+// searches the LDS copy as before.  With vi known this early the lane's read
+// of the unrank table is in flight while the block fills its LDS, instead of a
+// dependent round trip behind the barrier.
+struct WaveVar {
+    int vi;
+    int32_t loff;  // the variable's unrank table in this launch, -1 = none
+    uint64_t base, total;
+};
+__device__ __forceinline__ uint64_t uniform64(uint64_t x) {
+    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)x) |
+           ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32);
+}
+// total = work[nv], the launch's sets (ScoreArgs::total): every scalar load
+// here is a dependent round trip at the start of the wave, so the search keeps
+// the prefixes it has read -- work[0] = 0 and work[nv] = total bound it, and
+// when it ends the last two probes are work[lo] and work[lo + 1].
+// The same for the variable's unrank-table offset (lut_off, may be null): each
+// probe reads it beside the prefix, in the same round trip, so loff is
+// lut_off[lo] when the search ends.
+__device__ __forceinline__ WaveVar wave_variable(const uint64_t *work, const int32_t *lut_off, int nv, uint64_t total,
+                                                 uint64_t gid_lane0) {
+    WaveVar w;
+    w.total = total;
+    const uint64_t first = uniform64(gid_lane0), last = total - 1;
+    const uint64_t gl = first < last ? first : last, gh = first + 63 < last ? first + 63 : last;
+    int lo = 0, hi = nv;
+    uint64_t wlo = 0, whi = total;
+    int32_t llo = lut_off ? lut_off[0] : -1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        const uint64_t wm = work[mid];
+        const int32_t lm = lut_off ? lut_off[mid] : -1;
+        if (wm <= gl) {
+            lo = mid;
+            wlo = wm;
+            llo = lm;
+        } else {
+            hi = mid;
+            whi = wm;
+        }
+    }
+    w.base = wlo;
+    w.vi = gh < whi ? lo : -1;
+    w.loff = llo;
+    return w;
+}
+
+// have_um: um is the set's unranked mask read from the launch's unrank table
+// (UnrankPick below); otherwise the lane computes it.  RANK false: the caller
+// takes the set's rank from child_ranks and rankP stays 0.
+template <int L, int PHASE, bool RANK = true>
 __device__ __forceinline__ SetHead<L> set_head(const int *smeta, const uint8_t *scand, const uint32_t *binom, int vi,
-                                               uint64_t r) {
+                                               uint64_t r, bool have_um = false, uint32_t um32 = 0u) {
     SetHead<L> h;
     h.v = smeta[vi * 4 + 0];
     const int m = smeta[vi * 4 + 1];
     h.z = smeta[vi * 4 + 2] != 0;
-    if (PHASE == 0) h.cm = (unrank_colex(r, L - 1, m - 1, binom) << 1) | 1ull;
-    else if (h.z) h.cm = unrank_colex(r, L, m - 1, binom) << 1;
-    else h.cm = unrank_colex(r, L, m, binom);
-    h.rankP = rank_colex(h.cm, binom);
+    uint64_t um = um32;
+    if (!have_um) um = unrank_colex(r, (PHASE == 0) ? L - 1 : L, (PHASE == 0 || h.z) ? m - 1 : m, binom);
+    if (PHASE == 0) h.cm = (um << 1) | 1ull;
+    else if (h.z) h.cm = um << 1;
+    else h.cm = um;
+    h.rankP = RANK ? rank_colex(h.cm, binom) : 0ull;
     const uint8_t *cl = scand + vi * 64;
     uint64_t rem = h.cm;
 #pragma unroll
@@ -1099,7 +1178,7 @@ struct WideArgs {
     const uint64_t *hoff;     // [nv] offset of a variable's tables in hmax / pval, ~0 = none
     int reduced;              // walk_wide_kernel: skip the reference's no-op re-tests
     double N;
-    double lambda;
+    double pen;               // lambda ln(N), the device's product (ulg_ctx::pen)
     int n, nv, S, L;
 };
 
@@ -2326,7 +2405,7 @@ int wide_score(const ScoreCall &k, int L, int ph, WideGroup &G, unsigned long lo
     wa.hoff = nullptr;
     wa.reduced = c->wide_reduced;
     wa.N = (double)c->N;
-    wa.lambda = c->lambda;
+    wa.pen = c->pen;
     wa.n = c->n;
     wa.nv = k.ls.nv;
     wa.S = k.ls.S;
@@ -2729,6 +2808,8 @@ int launch_small(const ScoreCall &k, int L, int ph) {
     const uint64_t cnt = p.work[wo + nv];
     if (cnt == 0) return ULG_OK;
     ss.work = c->d_work.p + wo;
+    ss.total = cnt;
+    ss.lut_off = p.lut_any ? c->d_lutoff.p + p.lut_offset(L, ph) : nullptr;
     ss.hsub_out = !(L == p.kmax && ph == 1);
     return launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.vsmall), layer_kernel<true>(L, ph, p.vsmall),
                        dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock),
@@ -2800,6 +2881,8 @@ int launch_unrolled(const ScoreCall &k, int g, int L, int ph) {
     const bool bk = p.bucket && (L == 5 || L == 6);
     ScoreArgs sa = k.sa;
     sa.work = k.d_wk + p.work_offset(g, L, ph);
+    sa.total = cnt;
+    sa.lut_off = p.lut_any ? c->d_lutoff.p + p.lut_offset(L, ph) : nullptr;
     sa.queue = two_pass ? c->d_queue.p + (size_t)g * p.qwords : nullptr;
     sa.qcount = two_pass ? c->d_qseg.p + p.segoff[p.seg_slot(g, L, ph)] : nullptr;
     sa.qkey = bk ? c->d_qkey.p + (size_t)g * p.qcap : nullptr;
@@ -2921,7 +3004,12 @@ int ulg_cbic_load(ulg_ctx *c, const double *data, int64_t N, int n, double lambd
     gram_reduce_kernel<<<(n * n + kBlock - 1) / kBlock, kBlock, 0, c->stream>>>(c->partials.p, chunks, tiles, n,
                                                                                c->gram.p);
     prof_end(c);
+    // the BIC penalty per parent, once per load and from the device's own
+    // log: the host's libm may round ln(N) differently
+    if ((rc = ensure(c, c->d_pen, 1))) return rc;
+    penalty_kernel<<<1, 1, 0, c->stream>>>((double)N, lambda, c->d_pen.p);
     ULG_HIP(c, hipGetLastError());
+    ULG_HIP(c, hipMemcpyAsync(&c->pen, c->d_pen.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     c->loaded = true;
@@ -2957,6 +3045,43 @@ int ulg_cbic_score_finish(ulg_ctx *c, int64_t *total_stored, int64_t *total_scor
 }
 
 namespace {
+
+// The unrank tables the plan added to `staged`, a copy of the context's cache
+// (p.lut_new): room for them behind the tables already there, whose entries
+// move along when the buffer grows, and one fill launch each -- on the context
+// stream, before the call's launches and outside their capture.  Then the
+// call's offsets.  Only when all of that is enqueued does `staged` become the
+// context's cache: after any earlier return (here, or in reserve_buffers
+// before it) the context's cache still names exactly the tables d_lut holds
+// filled, and the next call plans the missing ones again.
+int reserve_luts(ulg_ctx *c, const CbicPlan &p, LutCache &staged) {
+    if (!p.lut_new.empty()) {
+        const uint64_t old_total = c->lut_cache.total, total = staged.total;
+        if (c->d_lut.cap < total) {
+            DevBuf<uint32_t> grown;
+            if (int rc = ensure(c, grown, (size_t)std::max<uint64_t>(total, 2 * c->d_lut.cap))) return rc;
+            if (old_total) {
+                hipError_t e = hipMemcpyAsync(grown.p, c->d_lut.p, old_total * sizeof(uint32_t),
+                                              hipMemcpyDeviceToDevice, c->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+                if (e != hipSuccess) {
+                    release(grown);  // d_lut and the context's cache stay as they were
+                    return set_err(c, ULG_ERR_HIP, std::string("unrank table copy failed: ") + hipGetErrorString(e));
+                }
+            }
+            release(c->d_lut);
+            c->d_lut = grown;
+        }
+        for (const LutTable &t : p.lut_new)
+            unrank_lut_fill_kernel<<<(unsigned)((t.count + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
+                c->d_lut.p + t.off, (uint32_t)t.count, t.l, t.U, c->d_binom.p);
+        ULG_HIP(c, hipGetLastError());
+    }
+    if (p.lut_any)
+        if (int rc = upload(c, c->d_lutoff, c->mir_lutoff, p.lutoff)) return rc;
+    c->lut_cache = std::move(staged);
+    return ULG_OK;
+}
 
 // Every device buffer the plan sizes, the uploads of its tables (skipped when
 // the device already holds the same bytes) and the groups' streams and events.
@@ -3030,7 +3155,9 @@ void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const 
                  ptr(c->d_meta.p), ptr(c->d_tbl_off.p), ptr(c->out_sets.p), ptr(c->out_scores.p),
                  ptr(c->out_offsets.p), ptr(c->d_blk.p), ptr(c->gram.p), ptr(c->d_binom.p), ptr(c->d_binom64.p),
                  ptr(c->d_hsub.p), (uint64_t)ls.total_slots, (uint64_t)c->score_small_layers, (uint64_t)c->score_fused,
-                 (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr)});
+                 (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr), dbits(c->pen),
+                 (uint64_t)c->score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
+                 ptr(p.lut_any ? c->d_lutoff.p : nullptr)});
     for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
     for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
     for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
@@ -3169,8 +3296,14 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     o.time_limit_ms = c->time_limit_ms;
     const char *wck = std::getenv("ULG_WALK_CLOCK");
     o.wck = wck != nullptr;
+    o.score_unrank_lut = c->score_unrank_lut;
     p.build(ls, c->cons_var, c->cons_req, c->cons_forb, o);
+    // the tables are planned on a copy of the context's cache, which takes
+    // the copy's place only once they are allocated and their fills enqueued
+    LutCache staged = c->lut_cache;
+    p.build_luts(ls, o.score_unrank_lut, staged);
     if (int rc = reserve_buffers(c, ls, p)) return rc;
+    if (int rc = reserve_luts(c, p, staged)) return rc;
 
     ScoreCall k{c, ls, p, ConsTable{p.cons_words ? c->d_cons.p : nullptr, p.cons_words, p.cons_lds}, ScoreArgs{},
                 p.G > 1 ? c->d_workg.p : c->d_work.p, std::vector<hipStream_t>(p.G), wck};
@@ -3187,7 +3320,8 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     sa.hsub = (p.variant & 64) ? c->d_hsub.p : nullptr;
     sa.err = k.errf();
     sa.N = (double)c->N;
-    sa.lambda = c->lambda;
+    sa.pen = c->pen;
+    sa.lut = p.lut_any ? c->d_lut.p : nullptr;
     sa.n = ls.n;
     sa.nv = ls.nv;
     sa.S = ls.S;
@@ -3300,9 +3434,9 @@ int ulg_cbic_score_sets(ulg_ctx *c, int64_t count, const int *vars, const uint64
     const dim3 grid((unsigned)((count + kBlock - 1) / kBlock)), block(kBlock);
     if ((rc = c->cons_var.empty()
                   ? launch_kernel(c, score_sets_kernel, grid, block, n * n * 8, c->stream, "score_sets", c->gram.p,
-                                  c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p)
+                                  c->d_sets_in.p, count, n, c->N, c->pen, c->qbuf_out.p)
                   : launch_kernel(c, score_sets_cons_kernel, grid, block, n * n * 8, c->stream, "score_sets",
-                                  c->gram.p, c->d_sets_in.p, count, n, c->N, c->lambda, c->qbuf_out.p,
+                                  c->gram.p, c->d_sets_in.p, count, n, c->N, c->pen, c->qbuf_out.p,
                                   c->d_cons_var.p)))
         return rc;
     ULG_HIP(c, hipMemcpyAsync(neg_scores, c->qbuf_out.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));

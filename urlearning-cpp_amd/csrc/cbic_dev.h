@@ -502,35 +502,12 @@ __device__ __forceinline__ bool settle_rules(const BS &present, const BS &hi, co
 //   max over U(P) = max_a hsub[P\a]                    (P with var 0, or no var 0 candidate)
 //                 = max_a max(hsub[P\a], hsub[P\a+{0}]) (P without var 0, phase 1)
 // and a set whose U(P) holds no key >= -ts is stored without its 2^(L+1)
-// presence gathers.  Children ranks: for P = {a_1 < ... < a_L} (compact),
-//   rank(P\a_i)       = sum_{j<i} C(a_j, j)   + sum_{j>i} C(a_j, j-1)
-//   rank(P\a_i + {0}) = sum_{j<i} C(a_j, j+1) + sum_{j>i} C(a_j, j)   (a_1 >= 1)
+// presence gathers.  The children's ranks, and P's own: child_ranks_t,
+// score_plan.h (host-checked there).
 template <int L, bool WITH0>
-__device__ __forceinline__ void child_ranks(uint64_t cm, const uint32_t *binom, uint64_t (&rc)[L], uint64_t (&rz)[L]) {
-    uint32_t e[L], d[L], f[L];
-    uint64_t rem = cm;
-#pragma unroll
-    for (int j = 0; j < L; ++j) {
-        const int aj = __builtin_ctzll(rem);
-        rem &= rem - 1;
-        e[j] = B(binom, aj, j + 1);
-        d[j] = B(binom, aj, j);
-        f[j] = WITH0 ? B(binom, aj, j + 2) : 0u;
-    }
-    uint32_t pe = 0, pf = 0;  // ranks of the unrolled layers fit 32 bits
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-        uint32_t sd = 0, se = 0;
-#pragma unroll
-        for (int j = i + 1; j < L; ++j) {
-            sd += d[j];
-            se += e[j];
-        }
-        rc[i] = pe + sd;
-        rz[i] = pf + se;
-        pe += e[i];
-        pf += f[i];
-    }
+__device__ __forceinline__ uint32_t child_ranks(uint64_t cm, const uint32_t *binom, uint64_t (&rc)[L],
+                                                uint64_t (&rz)[L]) {
+    return child_ranks_t<L, WITH0, kBinomK>(cm, binom, rc, rz);
 }
 
 // May find_best_subset_score's walk of P reach a key >= -ts?  A superset of
@@ -781,10 +758,13 @@ __device__ __forceinline__ void walk_sliced(uint32_t T, uint32_t pv, uint32_t ac
 // Gram matrix g = Z'Z (n x n, row-major, in LDS): Cholesky of G[P,P],
 // y = L^-1 G[P,v], RSS = G[v,v] - |y|^2, score = N ln(RSS / N) + lambda ln(N) L
 // (BIC_OLS.cpp:366), returned as float like the reference.  Every layer kernel
-// uses this one operation order.
+// uses this one operation order.  pen = lambda ln(N), the device's own rounded
+// product, computed once at ulg_cbic_load (penalty_kernel, cbic.hip): it is a
+// constant of the context, and its logarithm was ~74 VALU instructions of
+// every lane of every launch.
 template <int L>
 __device__ __forceinline__ float cbic_set_score(const double *g, int n, int v, const int (&gv)[L], double N,
-                                                double lambda) {
+                                                double pen) {
     double Lm[L][L];
     double y[L];
     int ro[L];  // row offsets gv[i] * n (< 2^24: a full-rate 24-bit multiply)
@@ -825,7 +805,7 @@ __device__ __forceinline__ float cbic_set_score(const double *g, int n, int v, c
     }
     const double rss = cvv - yy;
     // BIC_OLS.cpp:366  num_err*log(error_L2) + lambda*log(num_err)*k - 0
-    const double the_score = N * log(rss / N) + lambda * log(N) * (double)L - 0.0;
+    const double the_score = N * log(rss / N) + pen * (double)L - 0.0;
     return (float)the_score;
 }
 

@@ -27,40 +27,66 @@ score_layer_kernel(ScoreArgs a) {
     // would be two more dependent round trips per lane
     int *smeta = reinterpret_cast<int *>(smem + lay.meta);
     uint8_t *scand = reinterpret_cast<uint8_t *>(smem + lay.cand);
+    constexpr bool HM = (V & 64) != 0;           // subset maxima kept up to date
+    constexpr bool CMP = HM && (V & 16) != 0;     // ... and the sets settled by them first
+    // the wave's variable on the scalar unit, and with it the lane's unrank
+    // table entry, before the fill (wave_variable, cbic.hip)
+    const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
+    const WaveVar wv = wave_variable(a.work, a.lut_off, a.nv, a.total, gid0 - (threadIdx.x & 63u));
+    const bool valid = gid0 < wv.total;
+    // CMP: every lane reaches the block's barrier; a lane past the launch's
+    // sets scores the last one again and writes nothing
+    const uint64_t gid = valid ? gid0 : wv.total - 1;
+    bool have_um = false;
+    uint32_t um = 0u;
+    if (wv.vi >= 0 && wv.loff >= 0) {
+        um = a.lut[(uint32_t)wv.loff + (uint32_t)(gid - wv.base)];
+        have_um = true;
+    }
     for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
     for (int i = threadIdx.x; i < 64 * kBinomK; i += kBlock) binom[i] = a.binom[i];
     for (int i = threadIdx.x; i <= a.nv; i += kBlock) work[i] = a.work[i];
+    // the table offsets beside them: a straddling wave's lanes read theirs
+    // from LDS, not in a round trip of its own in front of the table read
+    int32_t *slut = reinterpret_cast<int32_t *>(smem + lay.lutoff);
+    if (a.lut_off)
+        for (int i = threadIdx.x; i < a.nv; i += kBlock) slut[i] = a.lut_off[i];
     for (int i = threadIdx.x; i <= a.nv * a.S; i += kBlock) toff[i] = a.tbl_off[i];
     for (int i = threadIdx.x; i < a.nv * 4; i += kBlock) smeta[i] = a.meta[i];
     for (int i = threadIdx.x; i < a.nv * 16; i += kBlock)
         reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
     __syncthreads();
 
-    constexpr bool HM = (V & 64) != 0;           // subset maxima kept up to date
-    constexpr bool CMP = HM && (V & 16) != 0;     // ... and the sets settled by them first
-    const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
-    const bool valid = gid0 < work[a.nv];
     if (!CMP && !valid) return;
-    // CMP: every lane reaches the block's barrier; a lane past the launch's
-    // sets scores the last one again and writes nothing
-    const uint64_t gid = valid ? gid0 : work[a.nv] - 1;
-    int lo = 0, hi = a.nv;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (work[mid] <= gid) lo = mid; else hi = mid;
+    int vi = wv.vi;
+    uint64_t r = gid - wv.base;
+    if (wv.vi < 0) {  // the wave straddles variables: each lane finds its own
+        int lo = 0, hi = a.nv;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (work[mid] <= gid) lo = mid; else hi = mid;
+        }
+        vi = lo;
+        r = gid - work[vi];
+        if (a.lut_off) {
+            const int32_t lo2 = slut[vi];
+            if (lo2 >= 0) {
+                um = a.lut[(uint32_t)lo2 + (uint32_t)r];
+                have_um = true;
+            }
+        }
     }
-    const int vi = lo;
-    const uint64_t r = gid - work[vi];
-    const SetHead<L> hd = set_head<L, PHASE>(smeta, scand, binom, vi, r);
+    // CMP: the set's rank comes out of child_ranks below
+    const SetHead<L> hd = set_head<L, PHASE, !CMP>(smeta, scand, binom, vi, r, have_um, um);
     const bool z = hd.z;
-    const uint64_t cm = hd.cm, rankP = hd.rankP;
+    const uint64_t cm = hd.cm;
 
 #ifndef ULG_PROBE_NOSCORE  // ULG_PROBE_*: timing-only builds, see the two-pass section below
 #if ULG_CONS
     float ts = (float)a.n;
-    if (!cons_violates(ct, a.nv, vi, cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+    if (!cons_violates(ct, a.nv, vi, cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
 #else
-    const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+    const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
 #endif
 #else
     const float ts = (float)(-a.N * g[hd.gv[0] * a.n + hd.gv[L - 1]] - (double)(r & 1023));
@@ -70,9 +96,9 @@ score_layer_kernel(ScoreArgs a) {
         // 1. settle by the subset maxima: ts >= 0, no key >= -ts in U(P), or a
         //    present direct child >= -ts (always visited at the top level)
         const uint64_t vbase = (uint64_t)vi * a.S;
-        const uint64_t slot = toff[vbase + L] + rankP;
         uint64_t rc[L], rz[L];
-        child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
+        const uint64_t rankP = child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
+        const uint64_t slot = toff[vbase + L] + rankP;
         // every load of the settle issued at once (the children's maxima and
         // values, the var-0 toggles' maxima): one memory round trip instead
         // of up to three dependent ones
@@ -266,5 +292,5 @@ score_layer_kernel(ScoreArgs a) {
         return;
     }
 
-    one_pass_set<L, PHASE, V>(a, smem, lay, binom, toff, vi, z, cm, rankP, ts);
+    one_pass_set<L, PHASE, V>(a, smem, lay, binom, toff, vi, z, cm, hd.rankP, ts);
 }

@@ -5,11 +5,11 @@
 // cons: the by-variable table in variable masks; a violator, the empty set
 // included, returns -float(n)
 __global__ void __launch_bounds__(kBlock) score_sets_cons_kernel(const double *gram, const uint64_t *pairs,
-                                                                 int64_t count, int n, double N, double lambda,
+                                                                 int64_t count, int n, double N, double pen,
                                                                  float *out, const uint64_t *cons) {
 #else
 __global__ void __launch_bounds__(kBlock) score_sets_kernel(const double *gram, const uint64_t *pairs, int64_t count,
-                                                            int n, double N, double lambda, float *out) {
+                                                            int n, double N, double pen, float *out) {
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *g = reinterpret_cast<double *>(smem);
@@ -69,6 +69,6 @@ __global__ void __launch_bounds__(kBlock) score_sets_kernel(const double *gram, 
         yy += t * t;
     }
     const double rss = cvv - yy;
-    const double the_score = N * log(rss / N) + lambda * log(N) * (double)L - 0.0;  // BIC_OLS.cpp:366
+    const double the_score = N * log(rss / N) + pen * (double)L - 0.0;  // BIC_OLS.cpp:366, pen = lambda ln(N)
     out[i] = -(float)the_score;
 }

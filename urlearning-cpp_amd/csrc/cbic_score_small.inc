@@ -23,9 +23,9 @@ __device__ __forceinline__ void ULG_FUSED_PHASE(const ScoreArgs &a, const uint64
         const SetHead<L> hd = set_head<L, PHASE>(smeta, scand, binom, vi, r);
 #if ULG_CONS
         float ts = (float)a.n;
-        if (!cons_violates(ct, a.nv, vi, hd.cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+        if (!cons_violates(ct, a.nv, vi, hd.cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
 #else
-        const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.lambda);
+        const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
 #endif
         one_pass_set<L, PHASE, V>(as, smem, lay, binom, toff, vi, hd.z, hd.cm, hd.rankP, ts);
     }

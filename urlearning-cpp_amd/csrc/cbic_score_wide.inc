@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(kBlock) score_wide_kernel(WideArgs a) {
     }
     const double rss = cvv - yy;
     // BIC_OLS.cpp:366
-    const double the_score = a.N * log(rss / a.N) + a.lambda * log(a.N) * (double)L - 0.0;
+    const double the_score = a.N * log(rss / a.N) + a.pen * (double)L - 0.0;
     const float ts = (float)the_score;
     if (ts >= 0.0f) {
         const float s = -ts;  // stored by the caller iff < 0 (score_calculator.cpp:111)

@@ -143,6 +143,84 @@ struct ScoreLists {
     }
 };
 
+#if defined(__HIPCC__)
+#define ULG_UNROLL _Pragma("unroll")
+#else
+#define ULG_UNROLL
+#endif
+
+// Children ranks of a layer-L set P = {a_1 < ... < a_L} (compact mask cm) from
+// a clamped 32-bit binomial table C(a, b) at binom[a * STRIDE + b]:
+//   rank(P\a_i)       = sum_{j<i} C(a_j, j)   + sum_{j>i} C(a_j, j-1)
+//   rank(P\a_i + {0}) = sum_{j<i} C(a_j, j+1) + sum_{j>i} C(a_j, j)   (a_1 >= 1)
+// Returns P's own colex rank, sum_j C(a_j, j): the binomials are the e[] the
+// children's ranks already fetch, so the two-pass kernels take the set's slot
+// from here instead of adding the same table reads up again (rank_colex).
+// Ranks of the unrolled layers fit 32 bits.  Host and device: the layer
+// kernels' child_ranks (cbic_dev.h) is this function, and
+// host/unrank_lut_check.cpp runs it against the enumeration order.
+template <int L, bool WITH0, int STRIDE>
+ULG_HD inline __attribute__((always_inline)) uint32_t child_ranks_t(uint64_t cm, const uint32_t *binom, uint64_t (&rc)[L], uint64_t (&rz)[L]) {
+    uint32_t e[L], d[L], f[L];
+    uint64_t rem = cm;
+    ULG_UNROLL
+    for (int j = 0; j < L; ++j) {
+        const int aj = __builtin_ctzll(rem);
+        rem &= rem - 1;
+        e[j] = binom[aj * STRIDE + j + 1];
+        d[j] = binom[aj * STRIDE + j];
+        f[j] = WITH0 ? binom[aj * STRIDE + j + 2] : 0u;
+    }
+    uint32_t pe = 0, pf = 0;
+    ULG_UNROLL
+    for (int i = 0; i < L; ++i) {
+        uint32_t sd = 0, se = 0;
+        ULG_UNROLL
+        for (int j = i + 1; j < L; ++j) {
+            sd += d[j];
+            se += e[j];
+        }
+        rc[i] = pe + sd;
+        rz[i] = pf + se;
+        pe += e[i];
+        pf += f[i];
+    }
+    return pe;
+}
+
+// Unrank tables (option score_unrank_lut).  The mapping rank -> set of
+// unrank_colex(r, l, U) depends only on (U, l), not on the data, the variable
+// or the call, so the layer kernels L = kLutMinL .. kMaxL read it from a table
+// of C(U, l) 32-bit masks filled once per context (unrank_lut_fill_kernel,
+// cbic.hip) instead of computing it in every lane.  The cache only grows: a
+// table keeps its offset for the life of the context, and every variable,
+// phase, layer and call with the same (U, l) shares it.
+constexpr int kLutMinL = 4;     // layers below run in the fused small kernel
+constexpr int kLutMaxU = 32;    // a table entry is a 32-bit mask
+constexpr int64_t kLutDefaultCap = 1 << 20;  // entries of the largest table (profiles/r15/README.md)
+constexpr uint64_t kLutMaxTotal = 0x7fffffffull;  // offsets are int32, -1 = none
+struct LutTable {
+    int U, l;
+    uint64_t off, count;  // entries
+};
+struct LutCache {
+    std::vector<LutTable> tables;  // in the order they were added
+    uint64_t total = 0;            // entries of all of them
+    const LutTable *find(int U, int l) const {
+        for (const LutTable &t : tables)
+            if (t.U == U && t.l == l) return &t;
+        return nullptr;
+    }
+};
+// the (U, l) a launch (L, ph) unranks variable (m candidates, z: variable 0
+// among them) with; false: the variable has no set in that launch
+inline bool lut_pair(int m, bool z, int L, int ph, int &U, int &l) {
+    if (ph == 0 && !z) return false;
+    U = (ph == 0 || z) ? m - 1 : m;
+    l = ph == 0 ? L - 1 : L;
+    return l >= 0 && l <= U;
+}
+
 // the context options a cBIC scoring call's plan depends on
 struct CbicOptions {
     int score_variant = 241;
@@ -154,6 +232,7 @@ struct CbicOptions {
     int wide_pool = 2;
     int64_t time_limit_ms = 0;
     bool wck = false;  // ULG_WALK_CLOCK diagnostics (synchronising, one stream)
+    int64_t score_unrank_lut = kLutDefaultCap;  // largest unrank table in entries, 0: none
 };
 
 // Everything ulg_cbic_score derives from the lists before its first launch.
@@ -220,6 +299,46 @@ struct CbicPlan {
     std::vector<uint64_t> ct;
     int cons_words = 0;  // 0: the call runs the unconstrained kernels
     int cons_lds = 0;    // bytes of LDS the constrained kernels add
+
+    // unrank tables: per launch (L, ph) and variable the offset of its table
+    // in the context's cache, -1 = the lanes compute; lut_new = the tables
+    // this call added to the cache, to be filled before its first launch
+    std::vector<int32_t> lutoff;  // [(L * 2 + ph) * nv + vi]; empty when no launch has a table
+    std::vector<LutTable> lut_new;
+    bool lut_any = false;
+    size_t lut_offset(int L, int ph) const { return ((size_t)L * 2 + ph) * nv; }
+
+    // After build(): which tables the call's layer launches read.  A table
+    // exists for U <= kLutMaxU and 0 < C(U, l) <= cap, while the cache stays
+    // within int32 offsets; it is added to `cache` the first time any call
+    // needs it (variables, then layers, then phases, in order).
+    void build_luts(const ScoreLists &ls, int64_t cap, LutCache &cache) {
+        lutoff.clear();
+        lut_new.clear();
+        lut_any = false;
+        const int top = std::min(kmax, kMaxL);
+        if (cap <= 0 || top < kLutMinL) return;
+        lutoff.assign((size_t)(kmax + 1) * 2 * nv, -1);
+        for (int i = 0; i < nv; ++i)
+            for (int L = kLutMinL; L <= top; ++L)
+                for (int ph = 0; ph < 2; ++ph) {
+                    int U, l;
+                    if (!lut_pair(ls.mv[i], meta[i * 4 + 2] != 0, L, ph, U, l) || U > kLutMaxU) continue;
+                    const uint64_t cnt = binom64(U, l);
+                    if (cnt == 0 || cnt > (uint64_t)cap) continue;
+                    const LutTable *t = cache.find(U, l);
+                    if (!t) {
+                        if (cache.total + cnt > kLutMaxTotal) continue;
+                        cache.tables.push_back(LutTable{U, l, cache.total, cnt});
+                        cache.total += cnt;
+                        lut_new.push_back(cache.tables.back());
+                        t = &cache.tables.back();
+                    }
+                    lutoff[lut_offset(L, ph) + i] = (int32_t)t->off;
+                    lut_any = true;
+                }
+        if (!lut_any) lutoff.clear();
+    }
 
     size_t work_offset(int g, int L, int ph) const {
         return (size_t)g * (G > 1 ? wstride : 0) + ((size_t)L * 2 + ph) * (nv + 1);

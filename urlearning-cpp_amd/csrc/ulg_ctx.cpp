@@ -162,6 +162,7 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->out_sets); release(c->out_scores); release(c->out_offsets);
     release(c->qbuf_in); release(c->qbuf_out);
     release(c->d_cons); release(c->d_cons_var);
+    release(c->d_lut); release(c->d_lutoff); release(c->d_pen);
     release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
     release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
     release(c->d_disc_table); release(c->d_disc_blk); release(c->d_disc_best);
@@ -203,6 +204,13 @@ int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
     if (std::strcmp(name, "score_fused") == 0) {
         if (value < 0 || value > 4) return set_err(c, ULG_ERR_ARG, "score_fused must be 0..4");
         c->score_fused = (int)value;
+        return ULG_OK;
+    }
+    // the largest unrank table in entries (score_plan.h); part of the graph key
+    if (std::strcmp(name, "score_unrank_lut") == 0) {
+        if (value < 0 || value > (int64_t)kLutMaxTotal)
+            return set_err(c, ULG_ERR_ARG, "score_unrank_lut must be 0..2^31-1");
+        c->score_unrank_lut = value;
         return ULG_OK;
     }
     if (std::strcmp(name, "score_variant") == 0) {
@@ -330,6 +338,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // (1), a walk-queue segment overflow (2) or a walk entry past the table (4)
     if (std::strcmp(name, "score_error_word") == 0) {
         *value = (int64_t)c->last_err_word;
+        return ULG_OK;
+    }
+    // option score_unrank_lut as it stands, and the entries of the unrank tables the context holds
+    if (std::strcmp(name, "score_unrank_lut") == 0 || std::strcmp(name, "unrank_lut_entries") == 0) {
+        *value = name[0] == 's' ? c->score_unrank_lut : (int64_t)c->lut_cache.total;
         return ULG_OK;
     }
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table

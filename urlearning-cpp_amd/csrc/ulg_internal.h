@@ -100,6 +100,17 @@ struct ulg_ctx {
     int sweep_xcd = 1;             // GPU sweep launches: contiguous runs of nodes per XCD           // GPU search: successor costs in the sweep's (layer, colex) order
     ulg::DevBuf<float> table;
     ulg::DevBuf<float> d_hsub;    // score_variant bit 6: subset maxima, table layout
+    // lambda ln(N) as the device computes it (penalty_kernel at ulg_cbic_load):
+    // the BIC penalty per parent, passed to every scoring kernel
+    double pen = 0.0;
+    ulg::DevBuf<double> d_pen;
+    // unrank tables (score_plan.h LutCache): the tables, the cache's index of
+    // them, and the call's per-launch offsets
+    int64_t score_unrank_lut = ulg::kLutDefaultCap;
+    ulg::LutCache lut_cache;
+    ulg::DevBuf<uint32_t> d_lut;
+    ulg::DevBuf<int32_t> d_lutoff;
+    ulg::Mirror mir_lutoff;
     ulg::DevBuf<uint64_t> d_tbl_off, d_work, d_blk;
     ulg::DevBuf<uint8_t> d_cand;  // [nv][64] compact index -> variable
     ulg::DevBuf<int> d_meta;      // [nv][4]: var, m, var0in, pad

@@ -523,6 +523,16 @@ int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_co
  * first time a call needs it and shared by every variable, layer and call;
  * the value is the largest such table in entries, 0 = every lane computes
  * the mapping as before.  Lists and scores are bit-identical either way.
+ * "score_lds_image" (0/1, default 1): every block of a layer launch (the
+ * unfused layers up to 8 parents) fills its LDS constants -- Gram matrix,
+ * binomials, work prefixes, unrank offsets, slab offsets, metadata, candidate
+ * lists -- from one image per launch that the host packs in the LDS layout
+ * (the Gram matrix from a host copy taken at ulg_cbic_load), in 16-byte
+ * pieces whose loads are all in flight at once; 0 = from the separate arrays,
+ * one loop each, as before.  The images are uploaded only when their bytes
+ * change.  Lists and scores are bit-identical either way; ulg_get_info
+ * "score_lds_image" / "lds_image_bytes" read the option and the bytes of the
+ * last call's images.
  * "disc_dense_cells" (1..32768, default 16384): a discrete set whose
  * contingency table has at most this many cells is counted in an int32 LDS
  * histogram; larger tables are counted in a hash table of their non-empty

@@ -164,6 +164,11 @@ struct ScoreArgs {
     // computes).  Both null: no table in this launch.
     const uint32_t *lut;
     const int32_t *lut_off;     // [nv], this launch's (layer, phase)
+    // The launch image (option score_lds_image; CbicPlan::build_images): the
+    // bytes of LDS [0, lay.stack) as 16-byte pieces, image16 of them.  Null:
+    // the layer kernels fill LDS from the arrays above.
+    const uint4 *image;
+    int image16;
 };
 
 // Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8),
@@ -209,66 +214,7 @@ __device__ __forceinline__ const uint64_t *cons_stage(unsigned char *smem, int l
 }
 
 
-// LDS carve: gram | binom | work, this launch's unrank-table offsets | tbl_off | meta | candidate lists |
-// recursion stack (variant bit 1)
-// | LDS bitsets (3 per lane when they have >= 4 words) | the block's
-// undecided sets after the subset-maxima test (variant bits 4 + 6: a count,
-// then per entry compact mask, slot, ts, children maximum, variable) (16-B
-// aligned)
-struct LdsLayout {
-    int gram, binom, work, lutoff, toff, meta, cand, stack, bits, cmp, cmp2, total;
-};
-constexpr int kCmpEntryBytes = 8 + 4 + 4 + 4 + 4;
-__host__ __device__ inline int align16(int x) { return (x + 15) & ~15; }
-#ifndef ULG_LDS_ALIAS
-#define ULG_LDS_ALIAS 1
-#endif
-__host__ __device__ inline LdsLayout lds_layout(int n, int nv, int S, int L, int V) {
-    LdsLayout l;
-    if (ULG_LDS_ALIAS && (V & 208) == 208 && bits_words(L) < 4) {
-        // the two-pass kernels with the second compaction (variant bit 7):
-        // the Gram matrix, the work prefixes and the candidate lists are
-        // read only before the block's first barrier (the scores and the
-        // subset-maxima settle), and the compaction entries and their words
-        // are written only after it -- so they share one region.  The
-        // counters, the binomials, the slab offsets and the metadata, read
-        // throughout, sit in front of it.  C3 layer 6: 26.7 -> 19 KB per
-        // block, 6 -> 8 blocks per CU (C5: 5 -> 8).
-        const int W = bits_words(L);
-        l.binom = 0;
-        l.toff = align16(l.binom + 64 * kBinomK * 4);
-        l.meta = align16(l.toff + (nv * S + 1) * 8);
-        l.cmp = align16(l.meta + nv * 4 * 4);  // 16 bytes of counters, then the entries
-        const int ra = l.cmp + 16;             // the shared region
-        l.gram = ra;
-        l.work = align16(l.gram + n * n * 8);
-        l.lutoff = l.work + (nv + 1) * 8;  // [nv] int32, read where work[] is: a straddling wave's lanes
-        l.cand = align16(l.lutoff + nv * 4);
-        l.stack = l.bits = align16(l.cand + nv * 64);
-        l.cmp2 = align16(ra + kBlock * kCmpEntryBytes);
-        const int endc = l.cmp2 + 2 * W * kBlock * 8;
-        l.total = l.stack > endc ? l.stack : endc;
-        return l;
-    }
-    l.gram = 0;
-    l.binom = align16(l.gram + n * n * 8);
-    l.work = align16(l.binom + 64 * kBinomK * 4);
-    l.lutoff = l.work + (nv + 1) * 8;
-    l.toff = align16(l.lutoff + nv * 4);
-    l.meta = align16(l.toff + (nv * S + 1) * 8);
-    l.cand = align16(l.meta + nv * 4 * 4);
-    l.stack = align16(l.cand + nv * 64);
-    l.bits = l.stack;
-    const int W = bits_words(L);
-    l.cmp = align16(l.bits + (W >= 4 ? 3 * W * kBlock * 8 : 0));
-    // variant bit 7: the second compaction carries each set's gathered
-    // present / hi words (register bitsets only, W < 4)
-    l.cmp2 = align16(l.cmp + ((V & 80) == 80 ? 16 + kBlock * kCmpEntryBytes : 0));
-    l.total = l.cmp2 + ((V & 208) == 208 && W < 4 ? 2 * W * kBlock * 8 : 0);
-    return l;
-}
-
-
+// The blocks' LDS carve (LdsLayout, lds_layout): score_plan.h.
 
 // The walk queue's segments and their counters (kSegBlocks, kSegEntries,
 // kSegStride, kBucketHdrWords, seg_count): score_plan.h.
@@ -2790,6 +2736,13 @@ int launch_prologue(const ScoreCall &k) {
                          k.ls.S, c->table.p, qcount, nqc, qseg, p.nqseg);
 }
 
+// The launch image of layer launch (g, L, ph), when the call built one.
+void set_image(const ScoreCall &k, ScoreArgs &sa, int g, int L, int ph) {
+    const int64_t at = k.p.image_offset(g, L, ph);
+    sa.image = at < 0 ? nullptr : reinterpret_cast<const uint4 *>(k.c->d_image.p + at);
+    sa.image16 = at < 0 ? 0 : k.p.image_bytes(k.ls, L) / 16;
+}
+
 // A small layer phase (L <= p.Ls) on the context stream, one-pass over all
 // variables; layers <= p.Lf run together in one fused launch, sent at (1, 0).
 int launch_small(const ScoreCall &k, int L, int ph) {
@@ -2810,6 +2763,7 @@ int launch_small(const ScoreCall &k, int L, int ph) {
     ss.work = c->d_work.p + wo;
     ss.total = cnt;
     ss.lut_off = p.lut_any ? c->d_lutoff.p + p.lut_offset(L, ph) : nullptr;
+    set_image(k, ss, 0, L, ph);
     ss.hsub_out = !(L == p.kmax && ph == 1);
     return launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.vsmall), layer_kernel<true>(L, ph, p.vsmall),
                        dim3((unsigned)((cnt + kBlock - 1) / kBlock)), dim3(kBlock),
@@ -2883,6 +2837,7 @@ int launch_unrolled(const ScoreCall &k, int g, int L, int ph) {
     sa.work = k.d_wk + p.work_offset(g, L, ph);
     sa.total = cnt;
     sa.lut_off = p.lut_any ? c->d_lutoff.p + p.lut_offset(L, ph) : nullptr;
+    set_image(k, sa, g, L, ph);
     sa.queue = two_pass ? c->d_queue.p + (size_t)g * p.qwords : nullptr;
     sa.qcount = two_pass ? c->d_qseg.p + p.segoff[p.seg_slot(g, L, ph)] : nullptr;
     sa.qkey = bk ? c->d_qkey.p + (size_t)g * p.qcap : nullptr;
@@ -3010,6 +2965,10 @@ int ulg_cbic_load(ulg_ctx *c, const double *data, int64_t N, int n, double lambd
     penalty_kernel<<<1, 1, 0, c->stream>>>((double)N, lambda, c->d_pen.p);
     ULG_HIP(c, hipGetLastError());
     ULG_HIP(c, hipMemcpyAsync(&c->pen, c->d_pen.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    // the host copy of the Gram matrix the launch images are built from
+    c->h_gram.resize((size_t)n * n);
+    ULG_HIP(c, hipMemcpyAsync(c->h_gram.data(), c->gram.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost,
+                              c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     c->loaded = true;
@@ -3157,7 +3116,8 @@ void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const 
                  ptr(c->d_hsub.p), (uint64_t)ls.total_slots, (uint64_t)c->score_small_layers, (uint64_t)c->score_fused,
                  (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr), dbits(c->pen),
                  (uint64_t)c->score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
-                 ptr(p.lut_any ? c->d_lutoff.p : nullptr)});
+                 ptr(p.lut_any ? c->d_lutoff.p : nullptr), (uint64_t)c->score_lds_image,
+                 ptr(p.image_any ? c->d_image.p : nullptr)});
     for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
     for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
     for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
@@ -3297,6 +3257,7 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     const char *wck = std::getenv("ULG_WALK_CLOCK");
     o.wck = wck != nullptr;
     o.score_unrank_lut = c->score_unrank_lut;
+    o.score_lds_image = c->score_lds_image;
     p.build(ls, c->cons_var, c->cons_req, c->cons_forb, o);
     // the tables are planned on a copy of the context's cache, which takes
     // the copy's place only once they are allocated and their fills enqueued
@@ -3304,6 +3265,11 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     p.build_luts(ls, o.score_unrank_lut, staged);
     if (int rc = reserve_buffers(c, ls, p)) return rc;
     if (int rc = reserve_luts(c, p, staged)) return rc;
+    // the launch images last: they hold the tables' offsets, and a call that
+    // failed above has changed neither d_image nor its mirror
+    p.build_images(ls, c->h_gram.data(), host_binom().data(), c->score_lds_image != 0);
+    if (p.image_any)
+        if (int rc = upload(c, c->d_image, c->mir_image, p.image)) return rc;
 
     ScoreCall k{c, ls, p, ConsTable{p.cons_words ? c->d_cons.p : nullptr, p.cons_words, p.cons_lds}, ScoreArgs{},
                 p.G > 1 ? c->d_workg.p : c->d_work.p, std::vector<hipStream_t>(p.G), wck};

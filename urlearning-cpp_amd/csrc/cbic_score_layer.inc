@@ -29,6 +29,21 @@ score_layer_kernel(ScoreArgs a) {
     uint8_t *scand = reinterpret_cast<uint8_t *>(smem + lay.cand);
     constexpr bool HM = (V & 64) != 0;           // subset maxima kept up to date
     constexpr bool CMP = HM && (V & 16) != 0;     // ... and the sets settled by them first
+    // The launch image (a.image, wave-uniform): the block's constants as one
+    // flat run of 16-byte pieces, thread t taking pieces t, t + kBlock, ...
+    // The loads of up to four passes (every n <= 32) are issued here, ahead
+    // of the variable search's scalar round trips and the table read, and
+    // written to LDS in front of the barrier; an index past the image reads
+    // its last piece again and writes nothing.
+    const uint32_t n16 = (uint32_t)a.image16;
+    const auto piece = [&](uint32_t j) {  // pass j's piece of this thread, when the image reaches that pass
+        // a 32-bit byte offset off the image's base in SGPRs, not a 64-bit pointer per lane
+        const uint32_t i = threadIdx.x + j * kBlock, at = (i < n16 ? i : n16 - 1u) << 4;
+        return (a.image && j * kBlock < n16)
+                   ? *reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned char *>(a.image) + at)
+                   : uint4{0u, 0u, 0u, 0u};
+    };
+    const uint4 im0 = piece(0), im1 = piece(1), im2 = piece(2), im3 = piece(3);
     // the wave's variable on the scalar unit, and with it the lane's unrank
     // table entry, before the fill (wave_variable, cbic.hip)
     const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
@@ -43,18 +58,28 @@ score_layer_kernel(ScoreArgs a) {
         um = a.lut[(uint32_t)wv.loff + (uint32_t)(gid - wv.base)];
         have_um = true;
     }
-    for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
-    for (int i = threadIdx.x; i < 64 * kBinomK; i += kBlock) binom[i] = a.binom[i];
-    for (int i = threadIdx.x; i <= a.nv; i += kBlock) work[i] = a.work[i];
-    // the table offsets beside them: a straddling wave's lanes read theirs
-    // from LDS, not in a round trip of its own in front of the table read
     int32_t *slut = reinterpret_cast<int32_t *>(smem + lay.lutoff);
-    if (a.lut_off)
-        for (int i = threadIdx.x; i < a.nv; i += kBlock) slut[i] = a.lut_off[i];
-    for (int i = threadIdx.x; i <= a.nv * a.S; i += kBlock) toff[i] = a.tbl_off[i];
-    for (int i = threadIdx.x; i < a.nv * 4; i += kBlock) smeta[i] = a.meta[i];
-    for (int i = threadIdx.x; i < a.nv * 16; i += kBlock)
-        reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
+    if (a.image) {
+        uint4 *simg = reinterpret_cast<uint4 *>(smem);
+        const uint32_t t = threadIdx.x;
+        if (t < n16) simg[t] = im0;
+        if (t + kBlock < n16) simg[t + kBlock] = im1;
+        if (t + 2u * kBlock < n16) simg[t + 2u * kBlock] = im2;
+        if (t + 3u * kBlock < n16) simg[t + 3u * kBlock] = im3;
+        for (uint32_t i = threadIdx.x + 4u * kBlock; i < n16; i += kBlock) simg[i] = a.image[i];
+    } else {
+        for (int i = threadIdx.x; i < a.n * a.n; i += kBlock) g[i] = a.gram[i];
+        for (int i = threadIdx.x; i < 64 * kBinomK; i += kBlock) binom[i] = a.binom[i];
+        for (int i = threadIdx.x; i <= a.nv; i += kBlock) work[i] = a.work[i];
+        // the table offsets beside them: a straddling wave's lanes read theirs
+        // from LDS, not in a round trip of its own in front of the table read
+        if (a.lut_off)
+            for (int i = threadIdx.x; i < a.nv; i += kBlock) slut[i] = a.lut_off[i];
+        for (int i = threadIdx.x; i <= a.nv * a.S; i += kBlock) toff[i] = a.tbl_off[i];
+        for (int i = threadIdx.x; i < a.nv * 4; i += kBlock) smeta[i] = a.meta[i];
+        for (int i = threadIdx.x; i < a.nv * 16; i += kBlock)
+            reinterpret_cast<uint32_t *>(scand)[i] = reinterpret_cast<const uint32_t *>(a.cand)[i];
+    }
     __syncthreads();
 
     if (!CMP && !valid) return;

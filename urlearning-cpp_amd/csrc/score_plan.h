@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/ulg.h"
@@ -55,6 +56,69 @@ constexpr int kSlotsPerBlock = kBlock * kSlotsPerThread;
 ULG_HD inline uint64_t seg_count(uint64_t blocks) { return (blocks + kSegBlocks - 1) / kSegBlocks; }
 // 64-bit words of a layer-L set's local bitset (2^(L+1) bits)
 ULG_HD constexpr int bits_words(int L) { return (L + 1) <= 6 ? 1 : (1 << ((L + 1) - 6)); }
+
+constexpr int kBinomK = kMaxL + 2;  // binomial table columns C(a, 0..kBinomK-1)
+
+// LDS carve: gram | binom | work, this launch's unrank-table offsets | tbl_off | meta | candidate lists |
+// recursion stack (variant bit 1)
+// | LDS bitsets (3 per lane when they have >= 4 words) | the block's
+// undecided sets after the subset-maxima test (variant bits 4 + 6: a count,
+// then per entry compact mask, slot, ts, children maximum, variable) (16-B
+// aligned).  Host and device: the layer kernels carve their LDS with it, and
+// CbicPlan::build_images lays the launch images out with it
+// (host/lds_image_check.cpp).
+struct LdsLayout {
+    int gram, binom, work, lutoff, toff, meta, cand, stack, bits, cmp, cmp2, total;
+};
+constexpr int kCmpEntryBytes = 8 + 4 + 4 + 4 + 4;
+ULG_HD inline int align16(int x) { return (x + 15) & ~15; }
+#ifndef ULG_LDS_ALIAS
+#define ULG_LDS_ALIAS 1
+#endif
+ULG_HD inline LdsLayout lds_layout(int n, int nv, int S, int L, int V) {
+    LdsLayout l;
+    if (ULG_LDS_ALIAS && (V & 208) == 208 && bits_words(L) < 4) {
+        // the two-pass kernels with the second compaction (variant bit 7):
+        // the Gram matrix, the work prefixes and the candidate lists are
+        // read only before the block's first barrier (the scores and the
+        // subset-maxima settle), and the compaction entries and their words
+        // are written only after it -- so they share one region.  The
+        // counters, the binomials, the slab offsets and the metadata, read
+        // throughout, sit in front of it.  C3 layer 6: 26.7 -> 19 KB per
+        // block, 6 -> 8 blocks per CU (C5: 5 -> 8).
+        const int W = bits_words(L);
+        l.binom = 0;
+        l.toff = align16(l.binom + 64 * kBinomK * 4);
+        l.meta = align16(l.toff + (nv * S + 1) * 8);
+        l.cmp = align16(l.meta + nv * 4 * 4);  // 16 bytes of counters, then the entries
+        const int ra = l.cmp + 16;             // the shared region
+        l.gram = ra;
+        l.work = align16(l.gram + n * n * 8);
+        l.lutoff = l.work + (nv + 1) * 8;  // [nv] int32, read where work[] is: a straddling wave's lanes
+        l.cand = align16(l.lutoff + nv * 4);
+        l.stack = l.bits = align16(l.cand + nv * 64);
+        l.cmp2 = align16(ra + kBlock * kCmpEntryBytes);
+        const int endc = l.cmp2 + 2 * W * kBlock * 8;
+        l.total = l.stack > endc ? l.stack : endc;
+        return l;
+    }
+    l.gram = 0;
+    l.binom = align16(l.gram + n * n * 8);
+    l.work = align16(l.binom + 64 * kBinomK * 4);
+    l.lutoff = l.work + (nv + 1) * 8;
+    l.toff = align16(l.lutoff + nv * 4);
+    l.meta = align16(l.toff + (nv * S + 1) * 8);
+    l.cand = align16(l.meta + nv * 4 * 4);
+    l.stack = align16(l.cand + nv * 64);
+    l.bits = l.stack;
+    const int W = bits_words(L);
+    l.cmp = align16(l.bits + (W >= 4 ? 3 * W * kBlock * 8 : 0));
+    // variant bit 7: the second compaction carries each set's gathered
+    // present / hi words (register bitsets only, W < 4)
+    l.cmp2 = align16(l.cmp + ((V & 80) == 80 ? 16 + kBlock * kCmpEntryBytes : 0));
+    l.total = l.cmp2 + ((V & 208) == 208 && W < 4 ? 2 * W * kBlock * 8 : 0);
+    return l;
+}
 
 // C(a, b), saturating at 2^64 - 1
 inline uint64_t binom64(int a, int b) {
@@ -233,6 +297,7 @@ struct CbicOptions {
     int64_t time_limit_ms = 0;
     bool wck = false;  // ULG_WALK_CLOCK diagnostics (synchronising, one stream)
     int64_t score_unrank_lut = kLutDefaultCap;  // largest unrank table in entries, 0: none
+    int score_lds_image = 1;  // the layer launches fill LDS from a packed image (build_images)
 };
 
 // Everything ulg_cbic_score derives from the lists before its first launch.
@@ -338,6 +403,58 @@ struct CbicPlan {
                     lut_any = true;
                 }
         if (!lut_any) lutoff.clear();
+    }
+
+    // Launch images (option score_lds_image).  Every block of a layer launch
+    // (score_layer_kernel and its constrained twin) fills the same constants
+    // into LDS before its first barrier; the image of launch (g, L, ph) is
+    // those bytes, LDS [0, lay.stack) exactly as lds_layout places them --
+    // the Gram matrix, the binomials, the launch's work prefixes and unrank
+    // offsets, the slab offsets, the metadata and the candidate lists, the
+    // alignment gaps and the aliased carve's counters zero -- so the block
+    // copies one flat run of 16-byte pieces.  lay.stack is a multiple of 16.
+    // Images lie back to back in `image`; imgoff holds their byte offsets.
+    std::vector<unsigned char> image;
+    std::vector<int64_t> imgoff;  // [seg_slot(g, L, ph)] -1: the launch has no image
+    bool image_any = false;
+    int64_t image_offset(int g, int L, int ph) const { return image_any ? imgoff[seg_slot(g, L, ph)] : -1; }
+    // the variant a layer launch runs with, and its work prefixes
+    int launch_variant(int L) const { return L <= Ls ? vsmall : variant; }
+    const uint64_t *launch_work(int g, int L, int ph) const {
+        return L <= Ls ? &work[work_offset(0, L, ph)] : &group_work()[work_offset(g, L, ph)];
+    }
+    int image_bytes(const ScoreLists &ls, int L) const { return lds_layout(ls.n, nv, ls.S, L, launch_variant(L)).stack; }
+
+    // After build() and build_luts(): gram = the n x n Gram matrix of the
+    // loaded data, binom = the clamped [64][kBinomK] table.  A small layer
+    // (Lf < L <= Ls) is one launch of all variables, group 0's.
+    void build_images(const ScoreLists &ls, const double *gram, const uint32_t *binom, bool on) {
+        image.clear();
+        imgoff.clear();
+        image_any = false;
+        const int top = std::min(kmax, kMaxL);
+        if (!on || !gram || !binom || top <= Lf) return;
+        imgoff.assign((size_t)G * 2 * (kmax + 1), -1);
+        const int n = ls.n, S = ls.S;
+        for (int L = Lf + 1; L <= top; ++L)
+            for (int ph = 0; ph < 2; ++ph)
+                for (int g = 0; g < (L <= Ls ? 1 : G); ++g) {
+                    const uint64_t *w = launch_work(g, L, ph);
+                    if (w[nv] == 0) continue;
+                    const LdsLayout lay = lds_layout(n, nv, S, L, launch_variant(L));
+                    const size_t at = image.size();
+                    image.resize(at + (size_t)lay.stack, 0);
+                    unsigned char *im = image.data() + at;
+                    std::memcpy(im + lay.gram, gram, (size_t)n * n * 8);
+                    std::memcpy(im + lay.binom, binom, (size_t)64 * kBinomK * 4);
+                    std::memcpy(im + lay.work, w, (size_t)(nv + 1) * 8);
+                    if (lut_any) std::memcpy(im + lay.lutoff, &lutoff[lut_offset(L, ph)], (size_t)nv * 4);
+                    std::memcpy(im + lay.toff, ls.toff.data(), ((size_t)nv * S + 1) * 8);
+                    std::memcpy(im + lay.meta, meta.data(), (size_t)nv * 16);
+                    std::memcpy(im + lay.cand, ls.cand.data(), (size_t)nv * 64);
+                    imgoff[seg_slot(g, L, ph)] = (int64_t)at;
+                    image_any = true;
+                }
     }
 
     size_t work_offset(int g, int L, int ph) const {

@@ -162,7 +162,7 @@ void ulg_destroy(ulg_ctx *c) {
     release(c->out_sets); release(c->out_scores); release(c->out_offsets);
     release(c->qbuf_in); release(c->qbuf_out);
     release(c->d_cons); release(c->d_cons_var);
-    release(c->d_lut); release(c->d_lutoff); release(c->d_pen);
+    release(c->d_lut); release(c->d_lutoff); release(c->d_image); release(c->d_pen);
     release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
     release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
     release(c->d_disc_table); release(c->d_disc_blk); release(c->d_disc_best);
@@ -211,6 +211,13 @@ int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
         if (value < 0 || value > (int64_t)kLutMaxTotal)
             return set_err(c, ULG_ERR_ARG, "score_unrank_lut must be 0..2^31-1");
         c->score_unrank_lut = value;
+        return ULG_OK;
+    }
+    // the layer launches fill LDS from one packed image per launch
+    // (score_plan.h build_images), 0: from the separate arrays; part of the graph key
+    if (std::strcmp(name, "score_lds_image") == 0) {
+        if (value != 0 && value != 1) return set_err(c, ULG_ERR_ARG, "score_lds_image must be 0 or 1");
+        c->score_lds_image = (int)value;
         return ULG_OK;
     }
     if (std::strcmp(name, "score_variant") == 0) {
@@ -343,6 +350,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // option score_unrank_lut as it stands, and the entries of the unrank tables the context holds
     if (std::strcmp(name, "score_unrank_lut") == 0 || std::strcmp(name, "unrank_lut_entries") == 0) {
         *value = name[0] == 's' ? c->score_unrank_lut : (int64_t)c->lut_cache.total;
+        return ULG_OK;
+    }
+    // option score_lds_image as it stands, and the bytes of the launch images the last call built
+    if (std::strcmp(name, "score_lds_image") == 0 || std::strcmp(name, "lds_image_bytes") == 0) {
+        *value = name[0] == 's' ? c->score_lds_image : (int64_t)c->plan.image.size();
         return ULG_OK;
     }
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table

@@ -12,11 +12,10 @@
 #include <vector>
 
 #include "../../include/ulg.h"
-#include "score_plan.h"  // kMaxVars, kMaxL, kWideMax, binom64, ScoreLists, CbicPlan
+#include "score_plan.h"  // kMaxVars, kMaxL, kWideMax, kBinomK, binom64, ScoreLists, CbicPlan
 
 namespace ulg {
 
-constexpr int kBinomK = kMaxL + 2;          // binomial table columns C(a, 0..kBinomK-1)
 constexpr uint32_t kAbsentBits = 0xFFFFFFFFu;  // "not in the FloatMap" sentinel (a NaN payload)
 
 // Device buffer that only grows.
@@ -111,6 +110,13 @@ struct ulg_ctx {
     ulg::DevBuf<uint32_t> d_lut;
     ulg::DevBuf<int32_t> d_lutoff;
     ulg::Mirror mir_lutoff;
+    // launch images (score_plan.h CbicPlan::build_images): the layer launches'
+    // LDS constants packed per launch, and the host copy of the Gram matrix
+    // they are built from (taken at ulg_cbic_load, replaced by every load)
+    int score_lds_image = 1;
+    std::vector<double> h_gram;
+    ulg::DevBuf<unsigned char> d_image;
+    ulg::Mirror mir_image;
     ulg::DevBuf<uint64_t> d_tbl_off, d_work, d_blk;
     ulg::DevBuf<uint8_t> d_cand;  // [nv][64] compact index -> variable
     ulg::DevBuf<int> d_meta;      // [nv][4]: var, m, var0in, pad

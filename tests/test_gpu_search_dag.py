@@ -26,10 +26,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _report(name, data):
+def _report(name, data, filename=None):
     d = os.path.join(ROOT, "gpurun_out")
     os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, f"dag_agreement_{name}.json"), "w") as f:
+    with open(os.path.join(d, filename or f"dag_agreement_{name}.json"), "w") as f:
         json.dump(data, f, indent=1)
 
 

@@ -7,6 +7,7 @@
 //   store / prune rule                        BIC_OLS.cpp:174-276, score_calculator.cpp:111-115
 //   two-phase layer order         score_calculator.cpp:78-123
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <type_traits>
 
@@ -753,6 +754,28 @@ __device__ __forceinline__ void walk_sliced(uint32_t T, uint32_t pv, uint32_t ac
 }
 
 
+// The rank rule of the three Cholesky forms (cbic_set_score below,
+// score_wide_kernel, score_sets_kernel).  A pivot
+// s = G[j,j] - sum_k L[j,k]^2 at or below tau G[j,j], tau = 32 (L + 1) 2^-53,
+// is rounding noise of either sign: column j lies in the span of the columns
+// before it (a duplicated column, an affine copy, a sum of two others).  The
+// forms then take s = +inf, so d, 1 / d, column j of L and y_j come out as
+// inf, 0, 0, 0 and the set scores as the set without that column does, with
+// |P| in the penalty.  Above tau the arithmetic is what it was: sqrt, 1.0 / d,
+// the divisions.  A NaN pivot (a constant column normalises to 0 / 0)
+// compares false and stays NaN.  Every diagonal entry of G is N - 1 up to
+// rounding (normalised columns), so the threshold is one value per set,
+// tau (N - 1): a compare and two selects per pivot.  (Measured dearer: the
+// threshold per column from G[j,j]; selects against zero on 1 / d and y_j;
+// one integer minimum per pivot with a guarded second factorisation behind a
+// branch, which cost the layer-6 kernels a third of their speed in spills.)
+__device__ __forceinline__ double pivot_threshold(double N, int L) {
+    return (32.0 * 0x1p-53) * (double)(L + 1) * (N - 1.0);
+}
+// A perfect fit's rss is rounding noise of either sign; a negative one scores
+// as 0 does (the score +inf).  NaN stays NaN.
+__device__ __forceinline__ double clamp_rss(double rss) { return rss < 0.0 ? 0.0 : rss; }
+
 // calculateScoreAndBeta's value (BIC_OLS.cpp:277-389) for one parent set of
 // L variables gv[] (ascending == parent_vec order) of variable v, from the
 // Gram matrix g = Z'Z (n x n, row-major, in LDS): Cholesky of G[P,P],
@@ -777,11 +800,13 @@ __device__ __forceinline__ float cbic_set_score(const double *g, int n, int v, c
 #pragma unroll
     for (int i = 0; i < L; ++i) y[i] = g[ro[i] + v];
     const double cvv = g[v * n + v];
+    const double piv = pivot_threshold(N, L);
 #pragma unroll
     for (int j = 0; j < L; ++j) {
         double s = Lm[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) s -= Lm[j][k] * Lm[j][k];
+        s = s <= piv ? (double)INFINITY : s;
         const double d = sqrt(s);
         Lm[j][j] = d;
         const double inv = 1.0 / d;
@@ -803,7 +828,7 @@ __device__ __forceinline__ float cbic_set_score(const double *g, int n, int v, c
         y[i] = t;
         yy += t * t;
     }
-    const double rss = cvv - yy;
+    const double rss = clamp_rss(cvv - yy);
     // BIC_OLS.cpp:366  num_err*log(error_L2) + lambda*log(num_err)*k - 0
     const double the_score = N * log(rss / N) + pen * (double)L - 0.0;
     return (float)the_score;

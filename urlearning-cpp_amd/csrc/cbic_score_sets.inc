@@ -45,10 +45,12 @@ __global__ void __launch_bounds__(kBlock) score_sets_kernel(const double *gram, 
         y[r] = g[gv[r] * n + v];
     }
     const double cvv = g[v * n + v];
+    const double piv = pivot_threshold(N, L);
     for (int j = 0; j < L; ++j) {
         const int rj = j * (j + 1) / 2;
         double s = Lm[rj + j];
         for (int k = 0; k < j; ++k) s -= Lm[rj + k] * Lm[rj + k];
+        s = s <= piv ? (double)INFINITY : s;
         const double d = sqrt(s);
         Lm[rj + j] = d;
         const double inv = 1.0 / d;
@@ -68,7 +70,7 @@ __global__ void __launch_bounds__(kBlock) score_sets_kernel(const double *gram, 
         y[r] = t;
         yy += t * t;
     }
-    const double rss = cvv - yy;
+    const double rss = clamp_rss(cvv - yy);
     const double the_score = N * log(rss / N) + pen * (double)L - 0.0;  // BIC_OLS.cpp:366, pen = lambda ln(N)
     out[i] = -(float)the_score;
 }

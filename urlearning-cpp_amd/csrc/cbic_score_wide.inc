@@ -59,10 +59,12 @@ __global__ void __launch_bounds__(kBlock) score_wide_kernel(WideArgs a) {
         y[i] = g[gv[i] * n + v];
     }
     const double cvv = g[v * n + v];
+    const double piv = pivot_threshold(a.N, L);
     for (int j = 0; j < L; ++j) {
         const int rj = j * (j + 1) / 2;
         double s = Lm[rj + j];
         for (int k = 0; k < j; ++k) s -= Lm[rj + k] * Lm[rj + k];
+        s = s <= piv ? (double)INFINITY : s;
         const double d = sqrt(s);
         Lm[rj + j] = d;
         const double inv = 1.0 / d;
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(kBlock) score_wide_kernel(WideArgs a) {
         y[i] = t;
         yy += t * t;
     }
-    const double rss = cvv - yy;
+    const double rss = clamp_rss(cvv - yy);
     // BIC_OLS.cpp:366
     const double the_score = a.N * log(rss / a.N) + a.pen * (double)L - 0.0;
     const float ts = (float)the_score;

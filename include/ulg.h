@@ -475,6 +475,19 @@ int ulg_sweep_shard_layer(ulg_ctx *ctx, int layer, uint64_t *keys_dev);
 int ulg_sweep_shard_commit(ulg_ctx *ctx, int layer, const uint64_t *keys_dev);
 int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_cost,
                         int64_t *expanded);
+/* Read-only view of a finished sweep: the leaf bytes of the last component
+ * ulg_astar(..., ULG_ASTAR_GPU, ...) searched on this context, or of the
+ * last ulg_sweep_shard_end, whichever ran later -- one byte per node of the
+ * component's 2^m lattice, layers 0..m in order and colex rank (over the
+ * component's variables in ascending order) within a layer.  The byte is the
+ * position j, among the node's elements in ascending order, of the leaf its
+ * cost came through (the first strict minimum), 255 for a node no admissible
+ * predecessor reaches; the layer-0 byte is not written by the sweep.
+ * *count = 2^m; cap = 0 only asks for it, a smaller nonzero cap is
+ * ULG_ERR_ARG.  ULG_ERR_STATE if no sweep has finished (the buffers are
+ * rewritten by the next GPU search or ulg_sweep_shard_begin).  No kernel
+ * runs: one device-to-host copy. */
+int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
 
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully

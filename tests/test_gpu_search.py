@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import fig_dag, load_fig
+import sweep_ref
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -19,6 +20,15 @@ def _oracle_pipeline(oracle, X, lam, k, cands=None):
     offs, sets, scores = ds.score_all(lam, cands, k, threads=8)
     costs = np.array([oracle.quantize(float(s)) for s in scores], dtype=np.float32)
     return offs, sets, scores, costs
+
+
+def _check_sweep_exact(gres, n, offs, sets, costs):
+    """The GPU order-graph search against tests/sweep_ref.py on a full
+    skeleton: goal cost bits, order and expansions."""
+    comps, expanded = sweep_ref.search(n, offs, sets, costs, [(1 << n) - 1] * n)
+    assert np.float32(gres["cost"]).tobytes() == comps[0]["cost"].tobytes()
+    assert [int(x) for x in gres["order"]] == comps[0]["order"]
+    assert gres["expanded"] == expanded
 
 
 def _random_subsets(rng, n, count):
@@ -169,6 +179,7 @@ def test_exact_astar_matches_oracle(ulg_ctx, oracle_built, seed, n, k):
     gres = ulg_ctx.astar(edges=full, mode=1)
     assert abs(gres["cost"] - ref["cost"]) <= 1e-6 * abs(ref["cost"])
     assert gres["expanded"] == (1 << n) - 1  # every node but the goal
+    _check_sweep_exact(gres, n, offs, sets, costs)
 
 
 def test_exact_astar_sparse_skeleton_components(ulg_ctx, oracle_built):
@@ -202,7 +213,7 @@ def test_c2_end_to_end_bit_exact(ulg_ctx, oracle_built):
     X, _ = synth.gaussian_sem(n, N, 9200)
     full = [(1 << n) - 1] * n
     ulg_ctx.load(X, 2.0)
-    ulg_ctx.score(list(range(n)), full, k)
+    goffs, gsets, gscores = ulg_ctx.score_all(list(range(n)), full, k)
     ulg_ctx.search_from_scores()
     res = ulg_ctx.astar(edges=full, mode=0)
     offs, sets, scores, costs = _oracle_pipeline(o, X, 2.0, k)
@@ -212,6 +223,8 @@ def test_c2_end_to_end_bit_exact(ulg_ctx, oracle_built):
     assert res["expanded"] == ref["expanded"]
     gres = ulg_ctx.astar(edges=full, mode=1)
     assert abs(gres["cost"] - ref["cost"]) <= 1e-6 * abs(ref["cost"])
+    # the lists this context searched: its own, costs through the same "%f" round trip
+    _check_sweep_exact(gres, n, goffs, gsets, ulg_ctx.quantize(gscores))
 
 
 @pytest.mark.parametrize("anc,scc", [(0b111, 0b111111111000), (0, 0b111111000000), (0b1, 0b110),

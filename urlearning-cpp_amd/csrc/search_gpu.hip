@@ -565,6 +565,7 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
     DevBuf<unsigned long long> &d_acc = s.gs_acc;
     auto cleanup = [&]() {};
     int rc;
+    if (s.leaf_src == 1) s.leaf_src = 0;  // gs_leaf is rewritten (and may move) below
     if ((rc = ensure(c, d_bn, bn.size())) || (rc = ensure(c, d_edges, 64)) || (rc = ensure(c, d_cv, kMaxM)) ||
         (rc = ensure(c, d_chain, kMaxM)) || (rc = ensure(c, d_acc, kCounters))) {
         cleanup();
@@ -676,6 +677,8 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
         if (e == hipSuccess) e = hipMemcpyAsync(chain.data(), d_chain.p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { cleanup(); return set_err(c, ULG_ERR_HIP, hipGetErrorString(e)); }
+        s.leaf_src = 1;  // this component's leaf bytes are complete (ulg_sweep_leaves)
+        s.leaf_m = m;
         if (!(g < FLT_MAX) || std::find(chain.begin(), chain.end(), -1) != chain.end()) { fail = true; continue; }
         // reconstruction as reconstructSolution: leaf order and getParents(remaining)
         std::vector<int> total(n, 0), qv(m);
@@ -725,6 +728,7 @@ int sweep_shard_begin(ulg_ctx *c, uint64_t own, int64_t *max_nodes) {
     if (n < 2 || n > kMaxM) return set_err(c, ULG_ERR_UNSUPPORTED, "ulg_sweep_shard_begin: 2..32 variables");
     if (own == 0 || (own & ~all)) return set_err(c, ULG_ERR_ARG, "ulg_sweep_shard_begin: bad variable mask");
     s.shard_active = false;
+    if (s.leaf_src == 2) s.leaf_src = 0;  // shard_leaf is rewritten (and may move) below
     // this rank's tables (every stored set of its variables, over every variable)
     int rc = search_build_tables(c, all, own);
     if (rc) return rc;
@@ -851,6 +855,8 @@ int sweep_shard_end(ulg_ctx *c, uint64_t *vpar, int *order, float *goal_cost, in
     ULG_HIP(c, hipMemcpyAsync(acc.data(), s.shard_acc.p, kCounters * 8, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     s.shard_active = false;
+    s.leaf_src = 2;  // every layer is committed (ulg_sweep_leaves)
+    s.leaf_m = m;
     if (!(g < FLT_MAX) || std::find(chain.begin(), chain.end(), -1) != chain.end())
         return set_err(c, ULG_ERR_STATE, "ulg_sweep_shard_end: no goal");
     std::vector<int> total(n, 0), qv(m);
@@ -906,6 +912,21 @@ int ulg_sweep_shard_end(ulg_ctx *c, uint64_t *vpar, int *order, float *goal_cost
     if (!c->search) return set_err(c, ULG_ERR_STATE, "ulg_sweep_shard_end: no search state");
     ULG_HIP(c, hipSetDevice(c->device));
     return ulg::sweep_shard_end(c, vpar, order, goal_cost, expanded);
+}
+
+int ulg_sweep_leaves(ulg_ctx *c, uint8_t *out, int64_t cap, int64_t *count) {
+    if (!c || !count || cap < 0 || (cap && !out)) return ULG_ERR_ARG;
+    if (!c->search || c->search->leaf_src == 0) return set_err(c, ULG_ERR_STATE, "ulg_sweep_leaves: no finished sweep");
+    const SearchState &s = *c->search;
+    const int64_t total = (int64_t)1 << s.leaf_m;  // sum over layers of C(m, layer)
+    *count = total;
+    if (cap == 0) return ULG_OK;
+    if (cap < total) return set_err(c, ULG_ERR_ARG, "ulg_sweep_leaves: cap below 2^m");
+    const uint8_t *src = s.leaf_src == 1 ? s.gs_leaf.p : s.shard_leaf.p;
+    ULG_HIP(c, hipSetDevice(c->device));
+    ULG_HIP(c, hipMemcpyAsync(out, src, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    return ULG_OK;
 }
 
 }  // extern "C"

@@ -251,6 +251,9 @@ struct SearchState {
     DevBuf<uint64_t> shard_bn, shard_loff;
     DevBuf<int> shard_wslot, shard_cv, shard_chain;
     DevBuf<unsigned long long> shard_acc;
+    // ulg_sweep_leaves: which leaf buffer holds the last finished sweep
+    // (0 none, 1 gs_leaf, 2 shard_leaf) and that component's size
+    int leaf_src = 0, leaf_m = 0;
     // pattern database
     int pd_count = 0;
     uint64_t ancestors = 0, scc = 0;
@@ -303,6 +306,7 @@ struct SearchState {
         release(shard_g0); release(shard_g1); release(shard_leaf); release(shard_bn); release(shard_loff);
         release(shard_wslot); release(shard_cv); release(shard_chain); release(shard_acc);
         shard_active = false;
+        leaf_src = 0;
         host_rows.release();
         rows_ready = false;
         host_cost_cap = 0;

@@ -76,6 +76,7 @@ def lib():
         L.ulg_sweep_shard_layer.argtypes = [P, I, P]
         L.ulg_sweep_shard_commit.argtypes = [P, I, P]
         L.ulg_sweep_shard_end.argtypes = [P, P, P, C.POINTER(F), C.POINTER(I64)]
+        L.ulg_sweep_leaves.argtypes = [P, P, I64, C.POINTER(I64)]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -450,6 +451,15 @@ class Context:
         self._check(lib().ulg_sweep_shard_end(self._h, _ptr(vpar), _ptr(order), C.byref(cost), C.byref(exp)),
                     "ulg_sweep_shard_end")
         return {"vpar": vpar, "order": order, "cost": cost.value, "expanded": exp.value}
+
+    def sweep_leaves(self) -> np.ndarray:
+        """ulg_sweep_leaves: the leaf bytes (uint8, 2^m, layer then colex
+        order) of the last component the GPU sweep finished."""
+        cnt = C.c_int64()
+        self._check(lib().ulg_sweep_leaves(self._h, None, 0, C.byref(cnt)), "ulg_sweep_leaves")
+        out = np.empty(cnt.value, dtype=np.uint8)
+        self._check(lib().ulg_sweep_leaves(self._h, _ptr(out), out.size, C.byref(cnt)), "ulg_sweep_leaves")
+        return out
 
     def _names_arg(self, names):
         arr = (C.c_char_p * len(names))(*[x.encode() for x in names])

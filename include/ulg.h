@@ -389,6 +389,25 @@ int ulg_pdb_build(ulg_ctx *ctx, int pd_count, uint64_t ancestors,
 /* StaticPatternDatabase::h for count subnetworks S. */
 int ulg_pdb_query(ulg_ctx *ctx, int64_t count, const uint64_t *S, float *h,
                   int *complete);
+/* Read-back of one variable's best-score table as the device holds it (for
+ * tests; the searches never call it): *support = D_var, the union of var's
+ * stored sets inside the tables' scope, *count = 2^|D_var|, and costs[i] =
+ * the table's cost for the S with pext(S, D_var) = i, FLT_MAX where no stored
+ * set fits.  costs == NULL or cap == 0 returns support and count only.
+ * *count = 0 for a variable that has no table (the sharded sweep's tables
+ * cover its own variables only).  ULG_ERR_STATE when no tables are built
+ * (no lists, or the budget refused them), ULG_ERR_ARG for a bad var or a
+ * cap below *count. */
+int ulg_bestscore_table(ulg_ctx *ctx, int var, uint64_t *support, float *costs,
+                        int64_t cap, int64_t *count);
+/* Read-back of one pattern-database group from the device array (for tests):
+ * *mask = the group's variables (0 for an empty group), *count = 2^|mask|,
+ * values[i] = pd[R] for the R inside mask with pext(R, mask) = i.  values ==
+ * NULL or cap == 0 returns mask and count only.  ULG_ERR_STATE without a
+ * pattern database, ULG_ERR_ARG for a group outside 0..pd_count-1 or a cap
+ * below *count. */
+int ulg_pdb_table(ulg_ctx *ctx, int group, uint64_t *mask, float *values,
+                  int64_t cap, int64_t *count);
 
 #define ULG_ASTAR_EXACT 0 /* the reference's pop order: bit-exact DAG */
 #define ULG_ASTAR_GPU 1   /* layer-synchronous GPU order-graph search */

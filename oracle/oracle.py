@@ -212,6 +212,10 @@ class Search:
         h = lib().ora_pdb_h(self.h, int(S), C.byref(comp))
         return h, comp.value
 
+    def pdb_value(self, g, R):
+        """ora_pdb_value: pd[R] of group g (R inside the group)."""
+        return lib().ora_pdb_value(self.h, int(g), int(R))
+
     def pdb_groups(self):
         g = np.zeros(64, dtype=np.uint64)
         k = lib().ora_pdb_groups(self.h, _p(g), 64)

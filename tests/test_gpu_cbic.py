@@ -158,6 +158,21 @@ def test_quantize_matches_oracle(ulg_ctx, oracle_built):
     assert got.tobytes() == exp.tobytes()
 
 
+def test_quantize_once_per_binade(ulg_ctx, oracle_built):
+    """ulg_quantize_costs on both ends and six random mantissas of every
+    float32 binade, both signs, and on the exact ties of the sixth decimal
+    (odd multiples of 1/128): bit for bit float(-atof('%f' % x)), where
+    Python's '%f' is the exact half-even expansion, and the oracle's value."""
+    import pct_f_values
+    vals = pct_f_values.binade_sweep()
+    got = ulg_ctx.quantize(vals)
+    exp = np.array([pct_f_values.expected_cost(x) for x in vals], dtype=np.float32)
+    bad = np.nonzero(got.view(np.uint32) != exp.view(np.uint32))[0]
+    assert bad.size == 0, [(float(vals[i]), float(got[i]), float(exp[i])) for i in bad[:5]]
+    ora = np.array([oracle_built.quantize(float(x)) for x in vals], dtype=np.float32)
+    assert got.tobytes() == ora.tobytes()
+
+
 def test_c2_properties_full_size(ulg_ctx, oracle_built):
     """BASELINE config C2 (n=20, N=10k, k=4, full skeleton) at full size:
     size-independent properties on every variable, oracle parity on two."""

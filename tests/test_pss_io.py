@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import pct_f_values
 from conftest import GOLDEN, PKG
 
 DUMP = os.path.join(PKG, "bin", "pss_dump")
@@ -136,6 +137,43 @@ def test_gpu_pss_format_matches_glibc(ulg_ctx, oracle_built, tmp_path):
     header = ref_text[: ref_text.index(b"VAR ")].decode()
     got = ulg_ctx.pss_format_lists(header, names, list(range(1, n + 2)), offs, sets, scores)
     assert got == ref_text
+
+
+def test_oracle_round_trip_once_per_binade(oracle_built):
+    """The oracle's "%f" + atof round trip is Python's exact '%f' expansion
+    on the once-per-binade sweep (what the GPU tests compare against)."""
+    vals = pct_f_values.binade_sweep()
+    got = np.array([oracle_built.quantize(float(x)) for x in vals], dtype=np.float32)
+    exp = np.array([pct_f_values.expected_cost(x) for x in vals], dtype=np.float32)
+    assert got.tobytes() == exp.tobytes()
+
+
+@pytest.mark.gpu
+def test_gpu_pss_format_once_per_binade(ulg_ctx, oracle_built, tmp_path):
+    """The formatter's score field is '%f' % x for every value of the sweep
+    (both ends and six random mantissas of every binade, both signs, and the
+    exact ties of the sixth decimal), and the whole text is the glibc
+    writer's."""
+    o = oracle_built
+    vals = pct_f_values.binade_sweep()
+    n = 6
+    names = ["alpha", "b", "Variable_2", "x3", "long_variable_name_4", "v5"]
+    per = len(vals) // n + 1
+    offs = [min(v * per, len(vals)) for v in range(n + 1)]
+    rng = np.random.default_rng(6)
+    sets = [int(rng.integers(0, 1 << n)) & ~(1 << min(i // per, n - 1)) for i in range(len(vals))]
+    got = ulg_ctx.pss_format_lists("META x=1\n\n", names, [2] * n, offs, sets, vals)
+    fields = [ln.split(b" ")[0].decode() for ln in got.split(b"\n")
+              if ln and not ln.startswith((b"META", b"VAR"))]
+    assert len(fields) == len(vals)
+    want = ['%f' % float(x) for x in vals]
+    bad = [(i, fields[i], want[i]) for i in range(len(vals)) if fields[i] != want[i]]
+    assert not bad, bad[:5]
+    ref = tmp_path / "ref.pss"
+    o.write_pss(str(ref), names, [2] * n, offs, sets, vals, num_records=5000)
+    ref_text = ref.read_bytes()
+    header = ref_text[: ref_text.index(b"VAR ")].decode()
+    assert ulg_ctx.pss_format_lists(header, names, [2] * n, offs, sets, vals) == ref_text
 
 
 @pytest.mark.gpu

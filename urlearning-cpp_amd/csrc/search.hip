@@ -421,17 +421,19 @@ int search_build_tables(ulg_ctx *c, uint64_t scope, uint64_t tvars) {
     tvars &= (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
     int rc;
     // support D_v
-    if ((rc = ensure(c, s.d_support, (size_t)n))) return rc;
-    ULG_HIP(c, hipMemsetAsync(s.d_support.p, 0, (size_t)n * 8, c->stream));
+    // (into a buffer of its own: a build the budget refuses below must leave
+    // d_support, which indexes the current tables, as it is)
+    if ((rc = ensure(c, s.d_support, (size_t)n)) || (rc = ensure(c, s.d_support_new, (size_t)n))) return rc;
+    ULG_HIP(c, hipMemsetAsync(s.d_support_new.p, 0, (size_t)n * 8, c->stream));
     int64_t maxcnt = 1;
     for (int v = 0; v < n; ++v) maxcnt = std::max<int64_t>(maxcnt, s.offsets[v + 1] - s.offsets[v]);
     const unsigned gx = (unsigned)std::min<int64_t>((maxcnt + kB - 1) / kB, 4096);
     prof_begin(c, "bs_support");
     support_kernel<<<dim3(gx, n), kB, 0, c->stream>>>(s.d_sets.p, s.d_offsets.p, n, scope,
-                                                     reinterpret_cast<unsigned long long *>(s.d_support.p));
+                                                     reinterpret_cast<unsigned long long *>(s.d_support_new.p));
     prof_end(c);
     std::vector<uint64_t> support(n, 0);
-    ULG_HIP(c, hipMemcpyAsync(support.data(), s.d_support.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipMemcpyAsync(support.data(), s.d_support_new.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     // memory check before touching the current tables: 4 B ordered cost + 4 B
     // device float cost + 4 B pinned host cost per entry
@@ -469,6 +471,7 @@ int search_build_tables(ulg_ctx *c, uint64_t scope, uint64_t tvars) {
     }
     s.table_vars = tvars;
     s.table_entries = total;
+    ULG_HIP(c, hipMemcpyAsync(s.d_support.p, s.d_support_new.p, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
     if ((rc = ensure(c, s.d_table, total)) || (rc = ensure(c, s.d_tb_off, (size_t)n + 1)) ||
         (rc = ensure(c, s.d_mbits, (size_t)n)))
         return rc;
@@ -578,6 +581,7 @@ int search_build_pdb(ulg_ctx *c, int pd_count, uint64_t ancestors, uint64_t scc)
     SearchState &s = *c->search;
     if (!s.lists_ready) return set_err(c, ULG_ERR_STATE, "pattern database needs the parent-set lists");
     if (pd_count < 1 || pd_count > kMaxGroups) return set_err(c, ULG_ERR_ARG, "pd_count must be 1..8");
+    s.pdb_ready = false;  // groups and pd_off change below, also when the build is refused
     // groups: consecutive scc variables, ceil(|scc| / pd_count) each (static_pattern_database.cpp:95-120)
     s.groups.clear();
     const int remaining = __builtin_popcountll(scc);
@@ -789,6 +793,24 @@ int search_pdb_query(ulg_ctx *c, int64_t count, const uint64_t *S, float *h, int
     ULG_HIP(c, hipMemcpyAsync(h, s.q_costs.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     if (complete) ULG_HIP(c, hipMemcpyAsync(complete, s.q_vars.p, (size_t)count * 4, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
+    return ULG_OK;
+}
+
+// ulg_bestscore_table: var's slice of the lattice as costs (cost_table_kernel
+// on that slice, through a staging buffer released again: up to 2^m floats)
+int search_table_read(ulg_ctx *c, int var, float *costs) {
+    SearchState &s = *c->search;
+    const uint64_t cnt = s.tb_off[var + 1] - s.tb_off[var];
+    if (cnt == 0) return ULG_OK;
+    DevBuf<float> stage;
+    int rc;
+    if ((rc = ensure(c, stage, (size_t)cnt))) return rc;
+    cost_table_kernel<<<flat_grid((cnt + kB - 1) / kB), kB, 0, c->stream>>>(s.d_table.p + s.tb_off[var], cnt, stage.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(costs, stage.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    release(stage);
+    ULG_HIP(c, e);
     return ULG_OK;
 }
 

@@ -576,6 +576,37 @@ int ulg_pdb_query(ulg_ctx *c, int64_t count, const uint64_t *S, float *h, int *c
     return search_pdb_query(c, count, S, h, complete);
 }
 
+int ulg_bestscore_table(ulg_ctx *c, int var, uint64_t *support, float *costs, int64_t cap, int64_t *count) {
+    if (!c || !support || !count || cap < 0 || (cap && !costs)) return ULG_ERR_ARG;
+    if (!c->search || !c->search->lists_ready || !c->search->tables_ready)
+        return set_err(c, ULG_ERR_STATE, "ulg_bestscore_table: no best-score tables");
+    const SearchState &s = *c->search;
+    if (var < 0 || var >= s.n) return set_err(c, ULG_ERR_ARG, "ulg_bestscore_table: bad variable");
+    const int64_t total = (int64_t)(s.tb_off[var + 1] - s.tb_off[var]);  // 0: no table for var (sharded tables)
+    *support = s.support[var];
+    *count = total;
+    if (cap == 0 || !costs || total == 0) return ULG_OK;
+    if (cap < total) return set_err(c, ULG_ERR_ARG, "ulg_bestscore_table: cap below 2^m");
+    ULG_HIP(c, hipSetDevice(c->device));
+    return search_table_read(c, var, costs);
+}
+
+int ulg_pdb_table(ulg_ctx *c, int group, uint64_t *mask, float *values, int64_t cap, int64_t *count) {
+    if (!c || !mask || !count || cap < 0 || (cap && !values)) return ULG_ERR_ARG;
+    if (!c->search || !c->search->pdb_ready) return set_err(c, ULG_ERR_STATE, "ulg_pdb_table: no pattern database");
+    const SearchState &s = *c->search;
+    if (group < 0 || group >= s.pd_count) return set_err(c, ULG_ERR_ARG, "ulg_pdb_table: bad group");
+    const int64_t total = (int64_t)(s.pd_off[group + 1] - s.pd_off[group]);
+    *mask = s.groups[group];
+    *count = total;
+    if (cap == 0 || !values) return ULG_OK;
+    if (cap < total) return set_err(c, ULG_ERR_ARG, "ulg_pdb_table: cap below 2^size");
+    ULG_HIP(c, hipSetDevice(c->device));
+    ULG_HIP(c, hipMemcpyAsync(values, s.d_pd.p + s.pd_off[group], (size_t)total * 4, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    return ULG_OK;
+}
+
 namespace {
 // The replay's host counters (perf_event_open on the calling thread, user
 // space only): cycles, instructions and the kernel's generic cache-miss event

@@ -116,7 +116,8 @@ struct SearchDev {
     const float *pd;         // pattern databases
     const uint64_t *gmeta;   // groups[kMaxGroups], pd_off[kMaxGroups]
     uint64_t scope;          // the tables hold every stored set inside scope
-    uint64_t table_vars;     // variables that have a table (all but in the sharded sweep)
+    uint64_t table_vars;     // variables whose table answers lookups: those that have one (all but in the
+                             // sharded sweep) and lie inside scope
     int tables;              // 1 if the tables are built (for scope)
     int pd_count;
     int n;
@@ -207,7 +208,7 @@ struct SearchState {
     std::vector<int> mbits;
     uint64_t table_entries = 0;
     DevBuf<uint32_t> d_table;      // ordkey(best cost) per subset of D_v
-    DevBuf<uint64_t> d_tb_off, d_support;
+    DevBuf<uint64_t> d_tb_off, d_support, d_support_new;  // _new: a build's supports until it is accepted
     DevBuf<uint64_t> e_idx, e_idx2;  // sorted (table index, key) of the stored sets
     DevBuf<uint32_t> e_key, e_key2;
     DevBuf<unsigned char> sort_tmp;
@@ -282,7 +283,9 @@ struct SearchState {
         d.offsets = d_offsets.p;
         d.costs = d_costs.p;
         d.scope = scope;
-        d.table_vars = table_vars;
+        // a variable outside the scope has a one-entry table (D_v = {}) that
+        // leaves out its stored sets inside the scope: its lookups scan the list
+        d.table_vars = table_vars & scope;
         d.tables = tables_ready ? 1 : 0;
         d.pd = d_pd.p;
         d.gmeta = d_groups.p;
@@ -292,7 +295,7 @@ struct SearchState {
     }
     void release_all() {
         release(d_sets); release(d_costs); release(d_scores_tmp); release(d_offsets);
-        release(d_table); release(d_tb_off); release(d_support); release(d_mbits); release(d_prefix);
+        release(d_table); release(d_tb_off); release(d_support); release(d_support_new); release(d_mbits); release(d_prefix);
         release(e_idx); release(e_key); release(e_idx2); release(e_key2); release(sort_tmp);
         release(d_cost_table); release(d_pd); release(d_bsv); release(d_bitpos); release(d_groups);
         release(q_vars); release(q_sets); release(q_par); release(q_costs);
@@ -330,5 +333,7 @@ int search_cost_rows_host(ulg_ctx *c, uint64_t scope, uint64_t scc, int64_t dead
                           bool *timed_out = nullptr);
 int search_query(ulg_ctx *c, int64_t count, const int *vars, const uint64_t *S, float *costs, uint64_t *parents);
 int search_pdb_query(ulg_ctx *c, int64_t count, const uint64_t *S, float *h, int *complete);
+// var's 2^m table entries as costs (tables built, var has a table)
+int search_table_read(ulg_ctx *c, int var, float *costs);
 
 }  // namespace ulg

@@ -61,6 +61,8 @@ def lib():
         L.ulg_bestscore_query.argtypes = [P, I64, P, P, P, P]
         L.ulg_pdb_build.argtypes = [P, I, C.c_uint64, C.c_uint64]
         L.ulg_pdb_query.argtypes = [P, I64, P, P, P]
+        L.ulg_bestscore_table.argtypes = [P, I, C.POINTER(C.c_uint64), P, I64, C.POINTER(I64)]
+        L.ulg_pdb_table.argtypes = [P, I, C.POINTER(C.c_uint64), P, I64, C.POINTER(I64)]
         L.ulg_astar.argtypes = [P, P, I, I, P, P, C.POINTER(F), C.POINTER(I64), C.c_char_p, I64]
         L.ulg_triplet_astar.argtypes = [P, P, I, P, P]
         L.ulg_triplet_clusters.argtypes = [P, P, P, I64, C.POINTER(I64)]
@@ -405,6 +407,29 @@ class Context:
         comp = np.empty(len(s), dtype=np.int32)
         self._check(lib().ulg_pdb_query(self._h, len(s), _ptr(s), _ptr(h), _ptr(comp)), "ulg_pdb_query")
         return h, comp
+
+    def bestscore_table(self, v):
+        """ulg_bestscore_table: (D_v, float32[2^m]) -- variable v's best-score
+        table as the device holds it, indexed by pext(S, D_v); an empty array
+        for a variable without a table (sharded tables)."""
+        sup, cnt = C.c_uint64(), C.c_int64()
+        self._check(lib().ulg_bestscore_table(self._h, int(v), C.byref(sup), None, 0, C.byref(cnt)),
+                    "ulg_bestscore_table")
+        out = np.empty(cnt.value, dtype=np.float32)
+        if out.size:
+            self._check(lib().ulg_bestscore_table(self._h, int(v), C.byref(sup), _ptr(out), out.size, C.byref(cnt)),
+                        "ulg_bestscore_table")
+        return sup.value, out
+
+    def pdb_table(self, g):
+        """ulg_pdb_table: (group mask, float32[2^size]) -- pattern-database
+        group g from the device array, indexed by pext(R, mask)."""
+        mask, cnt = C.c_uint64(), C.c_int64()
+        self._check(lib().ulg_pdb_table(self._h, int(g), C.byref(mask), None, 0, C.byref(cnt)), "ulg_pdb_table")
+        out = np.empty(cnt.value, dtype=np.float32)
+        self._check(lib().ulg_pdb_table(self._h, int(g), C.byref(mask), _ptr(out), out.size, C.byref(cnt)),
+                    "ulg_pdb_table")
+        return mask.value, out
 
     def astar(self, edges=None, pd_count=2, mode=0, net_text=True, ancestors=None, scc=None):
         n = self.search_n

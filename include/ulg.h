@@ -563,8 +563,7 @@ int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
  * pieces whose loads are all in flight at once; 0 = from the separate arrays,
  * one loop each, as before.  The images are uploaded only when their bytes
  * change.  Lists and scores are bit-identical either way; ulg_get_info
- * "score_lds_image" / "lds_image_bytes" read the option and the bytes of the
- * last call's images.
+ * "lds_image_bytes" reads the bytes of the last call's images.
  * "disc_dense_cells" (1..32768, default 16384): a discrete set whose
  * contingency table has at most this many cells is counted in an int32 LDS
  * histogram; larger tables are counted in a hash table of their non-empty
@@ -610,7 +609,14 @@ int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
  * default 16): host threads for those replays.
  * All variants compute identical results; the knob exists for A/B timing. */
 int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
-/* Read-back of per-call state: "out_of_time" (1 if the last ulg_cbic_score,
+/* Read-back.  Every option name of ulg_set_option gives that option as it
+ * stands (its default, or the last value a ulg_set_option accepted).
+ * "device_bytes_live" / "pinned_bytes_live": the bytes of device memory and
+ * of pinned host memory that the library's buffers hold at this moment --
+ * process-wide, every live context's together, the asking one's included; a
+ * destroyed context has given all of its bytes back (the exact search's
+ * host row table, an anonymous mapping, is not counted).
+ * Per-call state: "out_of_time" (1 if the last ulg_cbic_score,
  * ulg_astar* or ulg_triplet_astar ran out of time_limit_ms), "highest_completed_layer" (the
  * reference's ScoreCalculator::highestCompletedLayer of the last scoring call,
  * score_calculator.h:45), "exact_cycles" / "exact_instructions" /
@@ -619,7 +625,9 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
  * counted on each path), "disc_pruned" (sets its prune pass removed, option
  * "disc_prune"), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
- * ulg_disc_mmpc performed / left out by its reliability rule), "score_error_word" (the last scoring call's device error word: 0,
+ * ulg_disc_mmpc performed / left out by its reliability rule),
+ * "unrank_lut_entries" (entries of the unrank tables the context holds),
+ * "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero
  * word also made that call return a nonzero status). */

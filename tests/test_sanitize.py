@@ -9,6 +9,10 @@
   * urlearning-cpp_amd/bin/san/plan_check: the scoring call's host arithmetic
     (csrc/score_plan.h) against brute-force enumeration of parent sets;
   * urlearning-cpp_amd/bin/san/pss_dump: the parallel .pss reader (host/io.cpp);
+  * urlearning-cpp_amd/bin/san/devbuf_check: the owning device / pinned buffers
+    (csrc/dev_buf.h) over malloc, with LeakSanitizer watching the exit;
+  * urlearning-cpp_amd/bin/san/options_check: the option table (csrc/options.h)
+    against the record of what every option accepts;
   * oracle/build/san/ref_{score,astar,triplet}: the CPU oracle's command lines.
 Any sanitizer report aborts the program, so a zero exit status is the check."""
 import os
@@ -49,6 +53,16 @@ def test_heap_replays_agree_under_sanitizers(san_built, seed, ops, bits):
 def test_score_plan_matches_enumeration_under_sanitizers(san_built):
     r = _run([os.path.join(SAN, "plan_check")])
     assert "plan_check ok" in r.stdout
+
+
+def test_owning_buffers_under_sanitizers(san_built):
+    r = _run([os.path.join(SAN, "devbuf_check")])
+    assert "devbuf_check ok" in r.stdout
+
+
+def test_option_table_under_sanitizers(san_built):
+    r = _run([os.path.join(SAN, "options_check")])
+    assert "options_check ok" in r.stdout
 
 
 def test_pss_reader_under_sanitizers(san_built, tmp_path):

@@ -2294,7 +2294,7 @@ int host_walks(ulg_ctx *c, WideGroup &G, int L, int ph, int q, uint64_t sn, uint
             }
         };
         const unsigned nth = (unsigned)std::min<uint64_t>(
-            k, std::min((unsigned)c->wide_host_threads, std::max(1u, std::thread::hardware_concurrency())));
+            k, std::min((unsigned)c->opt.wide_host_threads, std::max(1u, std::thread::hardware_concurrency())));
         const auto twa = std::chrono::steady_clock::now();
         std::vector<std::thread> th;
         for (unsigned t = 1; t < nth; ++t) th.emplace_back(work);
@@ -2349,7 +2349,7 @@ int wide_score(const ScoreCall &k, int L, int ph, WideGroup &G, unsigned long lo
     wa.hmax = nullptr;
     wa.pval = nullptr;
     wa.hoff = nullptr;
-    wa.reduced = c->wide_reduced;
+    wa.reduced = c->opt.wide_reduced;
     wa.N = (double)c->N;
     wa.pen = c->pen;
     wa.n = c->n;
@@ -2441,8 +2441,8 @@ int wide_walks(const ScoreCall &k, int L, int ph, WideGroup &G, uint64_t &budget
         ULG_HIP(c, hipMemsetAsync(ws, 0, 64, st));
     }
     // long walks move to the LDS kernel (reduced walks with hi-cover tables only)
-    budget = (wa.hoff && wa.reduced && q <= kStragQMax && c->wide_lds)
-                     ? (c->wide_lds == 2 ? 1 : strag_budget())
+    budget = (wa.hoff && wa.reduced && q <= kStragQMax && c->opt.wide_lds)
+                     ? (c->opt.wide_lds == 2 ? 1 : strag_budget())
                      : 0;
     uint64_t *sq = G.queue + 3 * G.qn;  // straggler queue after this launch's entries (the queue has room)
     if (budget) ULG_HIP(c, hipMemsetAsync(G.scnt, 0, 8, st));
@@ -2500,15 +2500,15 @@ int wide_lds_replays(const ScoreCall &k, int L, int ph, WideGroup &G, unsigned l
     // few host threads would queue them behind each other while the GPU
     // runs them all at once (C1 10.7 s GPU-only against 32 s with every
     // launch handing over).
-    const uint64_t hbud = sn > c->wide_host_max ? 0
-                          : sn <= kHostFewReplays ? std::min<uint64_t>(c->wide_host_iters, kHostFewBudget)
-                                                  : c->wide_host_iters;
+    const uint64_t hbud = sn > c->opt.wide_host_max ? 0
+                          : sn <= kHostFewReplays ? std::min<uint64_t>(c->opt.wide_host_iters, kHostFewBudget)
+                                                  : c->opt.wide_host_iters;
     // ... and so do launches of few replays over 2^q >= 2^wide_host_q
     // local subsets: at the top layers of the largest candidate sets
     // nearly every replay outlives the LDS budget anyway (C4 v = 23:
     // L >= 15 hands over 13 of 14, 13 of 15, 1 of 1), so its LDS phase is
     // pure latency
-    if (hbud && (sn <= c->wide_host_first || (c->wide_host_q > 0 && q >= c->wide_host_q && sn <= 128))) {
+    if (hbud && (sn <= c->opt.wide_host_first || (c->opt.wide_host_q > 0 && q >= c->opt.wide_host_q && sn <= 128))) {
         // so few replays that the host takes them all at once: no GPU
         // replay phase (its length is its longest walk's), straight to
         // the fills, the copy and the host threads
@@ -2687,7 +2687,7 @@ int wide_pool(const ScoreCall &k) {
                         rcs[t] = set_err(c, ULG_ERR_HIP, "hipMemsetAsync failed in a wide-layer thread");
                         return;
                     }
-                    const int r = score_wide_groups(k, L, ph, one, c->wide_pinned + 2 * t);
+                    const int r = score_wide_groups(k, L, ph, one, c->wide_pinned.p + 2 * t);
                     if (r) {
                         rcs[t] = r;
                         next = p.pool_order.size();  // the other threads stop at their next task
@@ -2717,7 +2717,7 @@ int launch_wide_grouped(const ScoreCall &k, int L, int ph) {
         const size_t wo = p.work_offset(g, L, ph);
         wide.push_back(wide_group(k, g, L, ph, k.d_wk + wo, p.group_work().data() + wo, cnt));
     }
-    return wide.empty() ? ULG_OK : score_wide_groups(k, L, ph, wide, k.c->wide_pinned);
+    return wide.empty() ? ULG_OK : score_wide_groups(k, L, ph, wide, k.c->wide_pinned.p);
 }
 
 // The call's first launch: the empty sets' slots, and the queue counters zeroed.
@@ -2849,7 +2849,7 @@ int launch_unrolled(const ScoreCall &k, int g, int L, int ph) {
                           k.gst[g], kLayerNames[ph][L], sa)))
         return rc;
     if (!two_pass) return ULG_OK;
-    const int wk = sliced_k(L, cnt, (uint64_t)c->walk_small_sets, c->walk_k6);
+    const int wk = sliced_k(L, cnt, (uint64_t)c->opt.walk_small_sets, c->opt.walk_k6);
     if (bk) return walk_bucketed(k, g, L, ph, sa, blocks, wk);
     if ((p.variant & 32) && sliced_fn(L, ph, wk)) return walk_sliced(k, g, L, ph, sa, blocks, wk);
     return ULG_OK;
@@ -2892,11 +2892,11 @@ int launch_layers(const ScoreCall &k, int &done_L) {
             for (int g = 0; g < G; ++g)
                 if ((rc = launch_unrolled(k, g, L, ph))) return rc;
         }
-        if (c->time_limit_ms > 0 && L < kmax) {
+        if (c->opt.time_limit_ms > 0 && L < kmax) {
             for (int g = 0; g < (forked ? G : 1); ++g) ULG_HIP(c, hipStreamSynchronize(k.gst[g]));
             const double ms =
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            if (ms > (double)c->time_limit_ms) {
+            if (ms > (double)c->opt.time_limit_ms) {
                 done_L = L;
                 c->out_of_time = 1;
                 break;
@@ -2990,9 +2990,9 @@ int ulg_cbic_score_finish(ulg_ctx *c, int64_t *total_stored, int64_t *total_scor
         ULG_HIP(c, hipSetDevice(c->device));
         ULG_HIP(c, hipStreamSynchronize(c->stream));
         prof_collect(c);
-        c->total_stored = (int64_t)c->async_pinned[0];
-        c->last_err_word = c->async_pinned[1];
-        if (int rc = call_error(c, c->async_pinned[1])) {
+        c->total_stored = (int64_t)c->async_pinned.p[0];
+        c->last_err_word = c->async_pinned.p[1];
+        if (int rc = call_error(c, c->async_pinned.p[1])) {
             c->scored = false;
             return rc;
         }
@@ -3023,13 +3023,10 @@ int reserve_luts(ulg_ctx *c, const CbicPlan &p, LutCache &staged) {
                 hipError_t e = hipMemcpyAsync(grown.p, c->d_lut.p, old_total * sizeof(uint32_t),
                                               hipMemcpyDeviceToDevice, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) {
-                    release(grown);  // d_lut and the context's cache stay as they were
+                if (e != hipSuccess)  // d_lut and the context's cache stay as they were
                     return set_err(c, ULG_ERR_HIP, std::string("unrank table copy failed: ") + hipGetErrorString(e));
-                }
             }
-            release(c->d_lut);
-            c->d_lut = grown;
+            c->d_lut = std::move(grown);
         }
         for (const LutTable &t : p.lut_new)
             unrank_lut_fill_kernel<<<(unsigned)((t.count + kBlock - 1) / kBlock), kBlock, 0, c->stream>>>(
@@ -3091,10 +3088,7 @@ int reserve_buffers(ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p) {
                 return rc;
         }
         if ((int)c->wide_host.size() < 2 * G) {
-            if (c->wide_pinned) (void)hipHostFree(c->wide_pinned);
-            c->wide_pinned = nullptr;
-            ULG_HIP(c, hipHostMalloc((void **)&c->wide_pinned, sizeof(unsigned long long) * 2 * (size_t)G,
-                                     hipHostMallocDefault));
+            if ((rc = ensure(c, c->wide_pinned, 2 * (size_t)G))) return rc;
             c->wide_host.assign(2 * G, 0);
         }
     }
@@ -3107,16 +3101,16 @@ void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const 
                std::vector<uint64_t> &gkey) {
     auto ptr = [](const void *q) { return (uint64_t)(uintptr_t)q; };
     gkey.assign({(uint64_t)ls.nv, (uint64_t)ls.max_parents, (uint64_t)p.variant, (uint64_t)p.G, (uint64_t)p.Ls,
-                 (uint64_t)c->score_xcd, (uint64_t)ls.n, (uint64_t)c->N, dbits(c->lambda), (uint64_t)c->prof,
-                 (uint64_t)c->walk_small_sets, (uint64_t)c->walk_k6, (uint64_t)c->walk_bucket, ptr(c->d_qaux.p),
+                 (uint64_t)c->opt.score_xcd, (uint64_t)ls.n, (uint64_t)c->N, dbits(c->lambda), (uint64_t)c->prof,
+                 (uint64_t)c->opt.walk_small_sets, (uint64_t)c->opt.walk_k6, (uint64_t)c->opt.walk_bucket, ptr(c->d_qaux.p),
                  ptr(c->d_qsidx.p), ptr(c->d_qkey.p), ptr(c->d_qoffs.p), ptr(c->table.p), ptr(c->d_work.p),
                  ptr(c->d_workg.p), ptr(c->d_queue.p), ptr(c->d_qcount.p), ptr(c->d_qseg.p), ptr(c->d_cand.p),
                  ptr(c->d_meta.p), ptr(c->d_tbl_off.p), ptr(c->out_sets.p), ptr(c->out_scores.p),
                  ptr(c->out_offsets.p), ptr(c->d_blk.p), ptr(c->gram.p), ptr(c->d_binom.p), ptr(c->d_binom64.p),
-                 ptr(c->d_hsub.p), (uint64_t)ls.total_slots, (uint64_t)c->score_small_layers, (uint64_t)c->score_fused,
+                 ptr(c->d_hsub.p), (uint64_t)ls.total_slots, (uint64_t)c->opt.score_small_layers, (uint64_t)c->opt.score_fused,
                  (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr), dbits(c->pen),
-                 (uint64_t)c->score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
-                 ptr(p.lut_any ? c->d_lutoff.p : nullptr), (uint64_t)c->score_lds_image,
+                 (uint64_t)c->opt.score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
+                 ptr(p.lut_any ? c->d_lutoff.p : nullptr), (uint64_t)c->opt.score_lds_image,
                  ptr(p.image_any ? c->d_image.p : nullptr)});
     for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
     for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
@@ -3179,7 +3173,7 @@ struct CaptureGuard {
 int launch_call(const ScoreCall &k, const uint64_t *candidates) {
     ulg_ctx *c = k.c;
     const int kmax = k.p.kmax;
-    const bool use_graph = c->score_graph && !c->prof && kmax <= kMaxL && c->time_limit_ms == 0 && !k.wck;
+    const bool use_graph = c->opt.score_graph && !c->prof && kmax <= kMaxL && c->opt.time_limit_ms == 0 && !k.wck;
     std::vector<uint64_t> gkey;
     CaptureGuard capture_guard{c, false};
     c->out_of_time = 0;
@@ -3219,15 +3213,14 @@ int launch_call(const ScoreCall &k, const uint64_t *candidates) {
 // into the context.  Async: no host sync; ulg_cbic_score_finish collects the
 // words once the launches are done.
 int collect(ulg_ctx *c, const ScoreLists &ls, int64_t nb, bool async, int64_t *total_stored, int64_t *total_scored) {
-    if (!c->async_pinned)
-        ULG_HIP(c, hipHostMalloc((void **)&c->async_pinned, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-    ULG_HIP(c, hipMemcpyAsync(c->async_pinned, c->d_blk.p + nb, 16, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = ensure(c, c->async_pinned, 2)) return rc;
+    ULG_HIP(c, hipMemcpyAsync(c->async_pinned.p, c->d_blk.p + nb, 16, hipMemcpyDeviceToHost, c->stream));
     int64_t stored = 0;
     if (!async) {
         ULG_HIP(c, hipStreamSynchronize(c->stream));
-        stored = (int64_t)c->async_pinned[0];
+        stored = (int64_t)c->async_pinned.p[0];
         prof_collect(c);
-        if (int rc = call_error(c, c->async_pinned[1])) return rc;
+        if (int rc = call_error(c, c->async_pinned.p[1])) return rc;
     }
     publish(c, ls, stored, async);
     if (total_stored) *total_stored = c->total_stored;
@@ -3245,29 +3238,17 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     if (ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents))
         return lists_error(c, "ulg_cbic_score", st);
     ULG_HIP(c, hipSetDevice(c->device));
-    CbicOptions o;
-    o.score_variant = c->score_variant;
-    o.score_streams = c->score_streams;
-    o.score_small_layers = c->score_small_layers;
-    o.score_fused = c->score_fused;
-    o.walk_bucket = c->walk_bucket;
-    o.wide_prune = c->wide_prune;
-    o.wide_pool = c->wide_pool;
-    o.time_limit_ms = c->time_limit_ms;
     const char *wck = std::getenv("ULG_WALK_CLOCK");
-    o.wck = wck != nullptr;
-    o.score_unrank_lut = c->score_unrank_lut;
-    o.score_lds_image = c->score_lds_image;
-    p.build(ls, c->cons_var, c->cons_req, c->cons_forb, o);
+    p.build(ls, c->cons_var, c->cons_req, c->cons_forb, c->opt, wck != nullptr);
     // the tables are planned on a copy of the context's cache, which takes
     // the copy's place only once they are allocated and their fills enqueued
     LutCache staged = c->lut_cache;
-    p.build_luts(ls, o.score_unrank_lut, staged);
+    p.build_luts(ls, c->opt.score_unrank_lut, staged);
     if (int rc = reserve_buffers(c, ls, p)) return rc;
     if (int rc = reserve_luts(c, p, staged)) return rc;
     // the launch images last: they hold the tables' offsets, and a call that
     // failed above has changed neither d_image nor its mirror
-    p.build_images(ls, c->h_gram.data(), host_binom().data(), c->score_lds_image != 0);
+    p.build_images(ls, c->h_gram.data(), host_binom().data(), c->opt.score_lds_image != 0);
     if (p.image_any)
         if (int rc = upload(c, c->d_image, c->mir_image, p.image)) return rc;
 
@@ -3291,9 +3272,9 @@ int cbic_score(ulg_ctx *c, const int *vars, int nv, const uint64_t *candidates, 
     sa.n = ls.n;
     sa.nv = ls.nv;
     sa.S = ls.S;
-    sa.xcd = c->score_xcd;
+    sa.xcd = c->opt.score_xcd;
     if (int rc = launch_call(k, candidates)) return rc;
-    return collect(c, ls, p.nb, async && p.kmax <= kMaxL && c->time_limit_ms == 0, total_stored, total_scored);
+    return collect(c, ls, p.nb, async && p.kmax <= kMaxL && c->opt.time_limit_ms == 0, total_stored, total_scored);
 }
 
 }  // namespace

@@ -492,7 +492,7 @@ uint64_t table_cells(const ulg_ctx *c, int v, uint64_t parents) {
 // (which bounds the grid).
 int disc_work(ulg_ctx *c, uint64_t max_cells, uint64_t items, DiscWork &W, size_t &lds, unsigned &grid) {
     W = DiscWork{};
-    W.dense_cells = c->disc_dense_cells;
+    W.dense_cells = c->opt.disc_dense_cells;
     W.word = c->d_disc_word.p;
     uint64_t hs = 64;
     while (hs < 4ull * (uint64_t)c->N) hs <<= 1;
@@ -664,11 +664,11 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             prof_end(c);
             ULG_HIP(c, hipGetLastError());
         }
-        if (c->time_limit_ms > 0 && L < kmax) {
+        if (c->opt.time_limit_ms > 0 && L < kmax) {
             ULG_HIP(c, hipStreamSynchronize(c->stream));
             const double ms =
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            if (ms > (double)c->time_limit_ms) {
+            if (ms > (double)c->opt.time_limit_ms) {
                 done_L = L;
                 c->out_of_time = 1;
                 break;
@@ -676,7 +676,7 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
         }
     }
     c->completed_layer = done_L;
-    if (c->disc_prune) {
+    if (c->opt.disc_prune) {
         // the completed layers only: nothing above done_L was stored
         if ((rc = ensure(c, c->d_disc_best, total_slots))) return rc;
         PruneArgs P{};

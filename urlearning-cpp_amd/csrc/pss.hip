@@ -193,16 +193,10 @@ struct PssState {
     DevBuf<char> names, text;
     DevBuf<int> name_off;
     DevBuf<unsigned char> scan_tmp;
-    char *host = nullptr;
-    size_t host_cap = 0;
+    PinnedBuf<char> host;  // the text handed to the caller, valid until the next call
 };
 
-void pss_release(ulg_ctx *c) {
-    if (!c->pss) return;
-    PssState &s = *c->pss;
-    release(s.len); release(s.pos); release(s.bounds); release(s.sets); release(s.base); release(s.offsets);
-    release(s.scores); release(s.names); release(s.text); release(s.name_off); release(s.scan_tmp);
-    if (s.host) (void)hipHostFree(s.host);
+void pss_delete(ulg_ctx *c) {
     delete c->pss;
     c->pss = nullptr;
 }
@@ -267,24 +261,19 @@ static int pss_format_impl(ulg_ctx *c, int n, int nl, const int *var_of_list, co
         pss_write_kernel<<<(unsigned)((total + kB - 1) / kB), kB, 0, c->stream>>>(a, s.pos.p, s.base.p, s.text.p);
     prof_end(c);
     ULG_HIP(c, hipGetLastError());
-    if (s.host_cap < (size_t)bytes) {
-        if (s.host) (void)hipHostFree(s.host);
-        s.host = nullptr;
-        s.host_cap = 0;
-        ULG_HIP(c, hipHostMalloc((void **)&s.host, (size_t)bytes + 1, hipHostMallocDefault));
-        s.host_cap = (size_t)bytes;
-    }
-    ULG_HIP(c, hipMemcpyAsync(s.host, s.text.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = ensure(c, s.host, (size_t)bytes + 1))) return rc;
+    char *host = s.host.p;
+    ULG_HIP(c, hipMemcpyAsync(host, s.text.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
-    std::memcpy(s.host, header, std::strlen(header));
+    std::memcpy(host, header, std::strlen(header));
     for (int v = 0; v < n; ++v) {
-        std::memcpy(s.host + vstart[v], vhead[v].data(), vhead[v].size());
+        std::memcpy(host + vstart[v], vhead[v].data(), vhead[v].size());
         const int l = list_of_var[v];
-        s.host[base[l] + (int64_t)bounds[l + 1]] = '\n';
+        host[base[l] + (int64_t)bounds[l + 1]] = '\n';
     }
-    s.host[bytes] = 0;
-    *text = s.host;
+    host[bytes] = 0;
+    *text = host;
     *len = bytes;
     return ULG_OK;
 }

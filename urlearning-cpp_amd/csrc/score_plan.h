@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ulg.h"
+#include "options.h"  // Options: the plan reads the scorer's options from it
 
 #if defined(__HIPCC__)
 #define ULG_HD __host__ __device__
@@ -261,8 +262,7 @@ ULG_HD inline __attribute__((always_inline)) uint32_t child_ranks_t(uint64_t cm,
 // phase, layer and call with the same (U, l) shares it.
 constexpr int kLutMinL = 4;     // layers below run in the fused small kernel
 constexpr int kLutMaxU = 32;    // a table entry is a 32-bit mask
-constexpr int64_t kLutDefaultCap = 1 << 20;  // entries of the largest table (profiles/r15/README.md)
-constexpr uint64_t kLutMaxTotal = 0x7fffffffull;  // offsets are int32, -1 = none
+// kLutDefaultCap, kLutMaxTotal: options.h
 struct LutTable {
     int U, l;
     uint64_t off, count;  // entries
@@ -284,21 +284,6 @@ inline bool lut_pair(int m, bool z, int L, int ph, int &U, int &l) {
     l = ph == 0 ? L - 1 : L;
     return l >= 0 && l <= U;
 }
-
-// the context options a cBIC scoring call's plan depends on
-struct CbicOptions {
-    int score_variant = 241;
-    int score_streams = 3;
-    int score_small_layers = 4;
-    int score_fused = 3;
-    int walk_bucket = 1;
-    int wide_prune = 1;
-    int wide_pool = 2;
-    int64_t time_limit_ms = 0;
-    bool wck = false;  // ULG_WALK_CLOCK diagnostics (synchronising, one stream)
-    int64_t score_unrank_lut = kLutDefaultCap;  // largest unrank table in entries, 0: none
-    int score_lds_image = 1;  // the layer launches fill LDS from a packed image (build_images)
-};
 
 // Everything ulg_cbic_score derives from the lists before its first launch.
 // A layer L >= 1 runs as two launches (score_calculator.cpp:78-123): phase 0
@@ -467,7 +452,8 @@ struct CbicPlan {
     size_t hmeta_stride() const { return nv + (size_t)(nv + 1) * 8; }
 
     void build(const ScoreLists &ls, const std::vector<int> &cons_var, const std::vector<uint64_t> &cons_req,
-               const std::vector<uint64_t> &cons_forb, const CbicOptions &o) {
+               const std::vector<uint64_t> &cons_forb, const Options &o, bool wck) {
+        // wck: ULG_WALK_CLOCK diagnostics (synchronising, one stream)
         nv = ls.nv;
         kmax = ls.kmax;
         const std::vector<int> &mv = ls.mv;
@@ -494,8 +480,8 @@ struct CbicPlan {
             }
         build_constraints(ls, cons_var, cons_req, cons_forb);
 
-        variant = (ls.total_slots >> 30) ? 1 : o.score_variant;
-        G = ((variant & 16) && !o.wck) ? std::max(1, std::min(o.score_streams, nv)) : 1;
+        variant = (ls.total_slots >> 30) ? 1 : (int)o.score_variant;
+        G = ((variant & 16) && !wck) ? std::max(1, std::min((int)o.score_streams, nv)) : 1;
         workg.assign(G == 1 ? 0 : (size_t)G * wstride, 0);
         for (int g = 0; g < G && G > 1; ++g)
             for (int L = 1; L <= kmax; ++L)
@@ -527,7 +513,7 @@ struct CbicPlan {
                     segoff[i + 1] = segoff[i] + (queued ? nseg * kSegStride : 0) + (bhdr && cnt ? kBucketHdrWords : 0);
                 }
         nqc = nseg_slots + 1;
-        bucket = (variant & 112) == 112 && o.walk_bucket && !o.wck && kmax >= 5;  // the CMP path queues with keys
+        bucket = (variant & 112) == 112 && o.walk_bucket && !wck && kmax >= 5;  // the CMP path queues with keys
         qcap = (qwords / 3 + 255) & ~255ull;
         wave_cap = qcap / 64 + kBucketMax;
         zero_q = (variant & 16) || kmax > kMaxL;
@@ -549,9 +535,9 @@ struct CbicPlan {
                 if (htot == 0) hoff.clear();
             }
         }
-        Ls = (variant & 16) && !o.wck ? std::min(kmax, std::min(kMaxL, o.score_small_layers)) : 0;
+        Ls = (variant & 16) && !wck ? std::min(kmax, std::min(kMaxL, (int)o.score_small_layers)) : 0;
         vsmall = variant & 65;
-        Lf = vsmall == 65 && o.time_limit_ms == 0 ? std::min(Ls, o.score_fused) : 0;
+        Lf = vsmall == 65 && o.time_limit_ms == 0 ? std::min(Ls, (int)o.score_fused) : 0;
         build_pool(ls, o);
         nb = (int64_t)((ls.total_slots + kSlotsPerBlock - 1) / kSlotsPerBlock);
     }
@@ -592,7 +578,7 @@ private:
         cons_lds = cons_words <= kConsLdsWords ? cons_words * 8 : 0;
     }
 
-    void build_pool(const ScoreLists &ls, const CbicOptions &o) {
+    void build_pool(const ScoreLists &ls, const Options &o) {
         const std::vector<int> &mv = ls.mv;
         pool_order.clear();
         vw.clear();

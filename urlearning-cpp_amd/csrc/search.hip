@@ -446,7 +446,7 @@ int search_build_tables(ulg_ctx *c, uint64_t scope, uint64_t tvars) {
         total += 1ull << m;
     }
     if (total == 0) return set_err(c, ULG_ERR_ARG, "best-score tables for no variable");
-    uint64_t budget = c->table_budget_kb << 10;
+    uint64_t budget = (uint64_t)c->opt.table_budget_kb << 10;
     if (budget == 0) {
         size_t free_b = 0, tot_b = 0;
         ULG_HIP(c, hipMemGetInfo(&free_b, &tot_b));
@@ -673,13 +673,8 @@ int search_cost_table_host(ulg_ctx *c) {
     prof_begin(c, "bs_cost_table");
     cost_table_kernel<<<flat_grid((total + kB - 1) / kB), kB, 0, c->stream>>>(s.d_table.p, total, s.d_cost_table.p);
     prof_end(c);
-    if (s.host_cost_cap < total) {
-        if (s.host_costs) (void)hipHostFree(s.host_costs);
-        s.host_costs = nullptr;
-        ULG_HIP(c, hipHostMalloc((void **)&s.host_costs, total * 4, hipHostMallocDefault));
-        s.host_cost_cap = total;
-    }
-    ULG_HIP(c, hipMemcpyAsync(s.host_costs, s.d_cost_table.p, total * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = ensure(c, s.host_costs, total))) return rc;
+    ULG_HIP(c, hipMemcpyAsync(s.host_costs.p, s.d_cost_table.p, total * 4, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     s.host_costs_ready = true;
@@ -797,7 +792,7 @@ int search_pdb_query(ulg_ctx *c, int64_t count, const uint64_t *S, float *h, int
 }
 
 // ulg_bestscore_table: var's slice of the lattice as costs (cost_table_kernel
-// on that slice, through a staging buffer released again: up to 2^m floats)
+// on that slice, through a staging buffer of the call: up to 2^m floats)
 int search_table_read(ulg_ctx *c, int var, float *costs) {
     SearchState &s = *c->search;
     const uint64_t cnt = s.tb_off[var + 1] - s.tb_off[var];
@@ -809,7 +804,6 @@ int search_table_read(ulg_ctx *c, int var, float *costs) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(costs, stage.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release(stage);
     ULG_HIP(c, e);
     return ULG_OK;
 }

@@ -621,7 +621,7 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
         const uint64_t half = m >= 1 ? (1ull << (m - 1)) : 1ull;
         std::vector<uint64_t> loffm1(kMaxM + 1, 0);
         for (int p = 0; p < m; ++p) loffm1[p + 1] = loffm1[p] + binom64(m - 1, p);
-        bool use_w = !filt && m >= 2 && c->sweep_table != 0;
+        bool use_w = !filt && m >= 2 && c->opt.sweep_table != 0;
         if (use_w && !(s.sweep_ready && s.sweep_comp == comp)) {
             s.sweep_ready = false;
             size_t free_b = 0, tot_b = 0;
@@ -632,7 +632,6 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
             } else {
                 DevBuf<uint64_t> d_lo;
                 if ((rc = ensure(c, s.d_sweep_w, (size_t)need)) || (rc = ensure(c, d_lo, kMaxM + 1))) {
-                    release(d_lo);
                     cleanup();
                     return rc;
                 }
@@ -650,7 +649,6 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
                     e = hipGetLastError();
                 }
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                release(d_lo);
                 if (e != hipSuccess) { cleanup(); return set_err(c, ULG_ERR_HIP, hipGetErrorString(e)); }
                 s.sweep_ready = true;
                 s.sweep_comp = comp;
@@ -660,9 +658,9 @@ int astar_gpu(ulg_ctx *c, const uint64_t *edges, uint64_t *vpar, int *order, flo
             const uint64_t cnt = binom64(m, d);
             LayerArgs a{dv, d_bn.p, d_cv.p, d_edges.p, filt, symmetric && filt ? 1 : 0, m, d, cnt, gprev, gcur,
                         d_leaf.p + loff[d], d < m ? d_acc.p : nullptr,
-                        use_w ? s.d_sweep_w.p : nullptr, half, loffm1[d - 1], c->sweep_xcd};
+                        use_w ? s.d_sweep_w.p : nullptr, half, loffm1[d - 1], (int)c->opt.sweep_xcd};
             prof_begin(c, "search_layer_pull");
-            if (use_w && c->sweep_table == 1)
+            if (use_w && c->opt.sweep_table == 1)
                 layer_pull_w32_kernel<<<(unsigned)((cnt + kB * kPullPer - 1) / (kB * kPullPer)), kB, 0, c->stream>>>(a);
             else if (use_w) layer_pull_kernel<true><<<(unsigned)((cnt + kB - 1) / kB), kB, 0, c->stream>>>(a);
             else layer_pull_kernel<false><<<(unsigned)((cnt + kB - 1) / kB), kB, 0, c->stream>>>(a);
@@ -759,11 +757,8 @@ int sweep_shard_begin(ulg_ctx *c, uint64_t own, int64_t *max_nodes) {
         (rc = ensure(c, s.shard_loff, loff.size())) || (rc = ensure(c, s.shard_wslot, (size_t)m)) ||
         (rc = ensure(c, s.shard_cv, (size_t)m)) || (rc = ensure(c, s.shard_chain, kMaxM)) ||
         (rc = ensure(c, s.shard_g0, (size_t)maxl)) || (rc = ensure(c, s.shard_g1, (size_t)maxl)) ||
-        (rc = ensure(c, s.shard_leaf, (size_t)loff[m + 1])) || (rc = ensure(c, s.shard_acc, kCounters))) {
-        release(d_lo);
-        release(d_jl);
+        (rc = ensure(c, s.shard_leaf, (size_t)loff[m + 1])) || (rc = ensure(c, s.shard_acc, kCounters)))
         return rc;
-    }
     hipError_t e = hipMemcpyAsync(d_lo.p, loffm1.data(), (kMaxM + 1) * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_jl.p, jlist.data(), (size_t)nown * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(s.shard_bn.p, bn.data(), bn.size() * 8, hipMemcpyHostToDevice, c->stream);
@@ -791,8 +786,6 @@ int sweep_shard_begin(ulg_ctx *c, uint64_t own, int64_t *max_nodes) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release(d_lo);
-    release(d_jl);
     if (e != hipSuccess) return set_err(c, ULG_ERR_HIP, hipGetErrorString(e));
     prof_collect(c);
     s.shard_own = own;

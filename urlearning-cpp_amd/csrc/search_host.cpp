@@ -437,7 +437,7 @@ namespace exact {
 void host_tables(const SearchState &s, HostTables &T) {
     const int n = s.n;
     const uint64_t all = (n >= 64) ? ~0ull : ((1ull << n) - 1ull);
-    T.cost = s.host_costs;
+    T.cost = s.host_costs.p;
     T.tb_off = s.tb_off.data();
     T.support = s.support.data();
     T.all = all;
@@ -684,7 +684,7 @@ int ulg_astar_scc(ulg_ctx *c, const uint64_t *edges, int pd_count, int mode, uin
     *expanded = 0;
     *goal_cost = 0.0f;
     c->out_of_time = 0;
-    const Clock::time_point deadline = Clock::now() + std::chrono::milliseconds(c->time_limit_ms);
+    const Clock::time_point deadline = Clock::now() + std::chrono::milliseconds(c->opt.time_limit_ms);
     for (int i = 0; i < n; ++i) { vpar[i] = 0; order[i] = 0; }
     if (net_text && net_cap > 0) net_text[0] = 0;
     if (mode == ULG_ASTAR_GPU) return astar_gpu(c, edges, vpar, order, goal_cost, expanded);
@@ -706,7 +706,7 @@ int ulg_astar_scc(ulg_ctx *c, const uint64_t *edges, int pd_count, int mode, uin
         // the -r budget also covers the successor-cost rows (up to 8 GiB)
         bool rows_late = false;
         const int64_t dl_ns =
-            c->time_limit_ms > 0 ? std::chrono::duration_cast<std::chrono::nanoseconds>(deadline.time_since_epoch()).count()
+            c->opt.time_limit_ms > 0 ? std::chrono::duration_cast<std::chrono::nanoseconds>(deadline.time_since_epoch()).count()
                                  : 0;
         if ((rc = dense ? search_cost_rows_host(c, ancestors | comp, comp, dl_ns, &rows_late) : search_cost_table_host(c)))
             return rc;
@@ -717,7 +717,7 @@ int ulg_astar_scc(ulg_ctx *c, const uint64_t *edges, int pd_count, int mode, uin
         }
         HostTables T;
         host_tables(s, T);
-        const Clock::time_point *dl = c->time_limit_ms > 0 ? &deadline : nullptr;
+        const Clock::time_point *dl = c->opt.time_limit_ms > 0 ? &deadline : nullptr;
         HostPmu pmu;
         rc = dense ? astar_dense(c, T, edges, good, ancestors, comp, expanded, &hang, r, dl)
                    : astar_one(c, T, edges, good, ancestors, comp, expanded, &hang, r, dl);

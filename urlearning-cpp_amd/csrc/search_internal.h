@@ -219,8 +219,7 @@ struct SearchState {
     uint64_t table_vars = 0;    // variables with a table (every variable, except for ulg_sweep_shard_*)
     // host copy of the per-subset best costs (exact-order search)
     DevBuf<float> d_cost_table;
-    float *host_costs = nullptr;
-    uint64_t host_cost_cap = 0;
+    PinnedBuf<float> host_costs;
     bool host_costs_ready = false;
     // exact-order search: one row of successor costs per subset of the scope,
     // row[pext(S, scope)][i] = getScore(scc_i, S) (FLT_MAX for scc_i in S)
@@ -292,27 +291,6 @@ struct SearchState {
         d.pd_count = pd_count;
         d.n = n;
         return d;
-    }
-    void release_all() {
-        release(d_sets); release(d_costs); release(d_scores_tmp); release(d_offsets);
-        release(d_table); release(d_tb_off); release(d_support); release(d_support_new); release(d_mbits); release(d_prefix);
-        release(e_idx); release(e_key); release(e_idx2); release(e_key2); release(sort_tmp);
-        release(d_cost_table); release(d_pd); release(d_bsv); release(d_bitpos); release(d_groups);
-        release(q_vars); release(q_sets); release(q_par); release(q_costs);
-        if (host_costs) (void)hipHostFree(host_costs);
-        host_costs = nullptr;
-        release(d_rows); release(d_rowmeta);
-        release(d_sweep_w);
-        sweep_ready = false;
-        release(gs_bn); release(gs_edges); release(gs_layer_off); release(gs_cv); release(gs_chain);
-        release(gs_g0); release(gs_g1); release(gs_leaf); release(gs_acc);
-        release(shard_g0); release(shard_g1); release(shard_leaf); release(shard_bn); release(shard_loff);
-        release(shard_wslot); release(shard_cv); release(shard_chain); release(shard_acc);
-        shard_active = false;
-        leaf_src = 0;
-        host_rows.release();
-        rows_ready = false;
-        host_cost_cap = 0;
     }
 };
 

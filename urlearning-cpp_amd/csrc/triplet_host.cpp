@@ -776,9 +776,9 @@ extern "C" int ulg_triplet_astar(ulg_ctx *c, const uint64_t *edges, int pd_count
     t.pd_count = pd_count;
     t.memo = memo_for(s, pd_count);
     c->out_of_time = 0;
-    if (c->time_limit_ms > 0) {
+    if (c->opt.time_limit_ms > 0) {
         t.timed = true;
-        t.deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(c->time_limit_ms);
+        t.deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(c->opt.time_limit_ms);
     }
     init_skeleton(t, edges);
     set_parallel(t);

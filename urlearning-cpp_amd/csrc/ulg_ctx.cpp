@@ -1,4 +1,5 @@
 // ulg_ctx.cpp -- context lifecycle, errors, profiling for libulg.so.
+#include <atomic>
 #include <mutex>
 #include <cstdio>
 #include <cstring>
@@ -102,7 +103,61 @@ void graph_reset(ulg_ctx *c) {
     c->gprof.clear();
 }
 
+// ---- dev_buf.h's memory, over HIP ----------------------------------------------
+// bytes live through DevBuf / PinnedBuf in this process (ulg_get_info)
+static std::atomic<int64_t> g_device_bytes{0}, g_pinned_bytes{0};
+
+int dev_alloc(void **p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) g_device_bytes += (int64_t)bytes;
+    return (int)e;
+}
+int dev_free(void *p, size_t bytes) {
+    g_device_bytes -= (int64_t)bytes;
+    return (int)hipFree(p);
+}
+int pinned_alloc(void **p, size_t bytes) {
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) g_pinned_bytes += (int64_t)bytes;
+    return (int)e;
+}
+int pinned_free(void *p, size_t bytes) {
+    g_pinned_bytes -= (int64_t)bytes;
+    return (int)hipHostFree(p);
+}
+int alloc_failed(ulg_ctx *c, const char *call, int status) {
+    return set_err(c, ULG_ERR_HIP, std::string(call) + " failed: " + hipGetErrorString((hipError_t)status));
+}
+int dev_upload(ulg_ctx *c, void *dst, const void *src, size_t bytes) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return set_err(c, ULG_ERR_HIP, std::string("hipMemcpyAsync failed: ") + hipGetErrorString(e));
+    return ULG_OK;
+}
+
+CtxStreams::~CtxStreams() {
+    for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+    for (hipStream_t s : aux_streams) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : sync_events) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
 }  // namespace ulg
+
+// The one place the teardown order is written.  With the context's device
+// current: wait until the stream is idle, so that no launch still reads a
+// buffer; drop the captured graph, which hands its events back to the pool;
+// delete the search and .pss states, whose buffers free themselves.  Then the
+// members go, and with them every DevBuf and PinnedBuf of the context; last
+// the base CtxStreams destroys the streams and the events.
+ulg_ctx::~ulg_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) {
+        (void)hipStreamSynchronize(stream);
+        ulg::graph_reset(this);
+    }
+    ulg::pss_delete(this);
+    delete search;
+}
 
 using namespace ulg;
 
@@ -141,40 +196,7 @@ int ulg_create(const int *device_ids, int ndev, ulg_ctx **out) {
 }
 
 void ulg_destroy(ulg_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    graph_reset(c);
-    if (c->wide_pinned) (void)hipHostFree(c->wide_pinned);
-    c->wide_pinned = nullptr;
-    if (c->async_pinned) (void)hipHostFree(c->async_pinned);
-    c->async_pinned = nullptr;
-    for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    c->event_pool.clear();
-    for (hipStream_t s : c->aux_streams) (void)hipStreamDestroy(s);
-    c->aux_streams.clear();
-    for (hipEvent_t e : c->sync_events) (void)hipEventDestroy(e);
-    c->sync_events.clear();
-    release(c->raw); release(c->z); release(c->gram); release(c->partials); release(c->colstat);
-    release(c->table); release(c->d_tbl_off); release(c->d_work); release(c->d_blk);
-    release(c->d_cand); release(c->d_meta); release(c->d_binom); release(c->d_binom64); release(c->d_wqueue); release(c->d_wbits); release(c->d_stats); release(c->d_dump); release(c->d_queue); release(c->d_qcount); release(c->d_workg); release(c->d_vwork); release(c->d_hq); release(c->d_hqc); release(c->d_hmax); release(c->d_hoff); release(c->d_hmeta); release(c->d_scount); release(c->d_hsub); release(c->d_qseg);
-    release(c->d_qaux); release(c->d_qsidx); release(c->d_qoffs); release(c->d_qkey);
-    release(c->out_sets); release(c->out_scores); release(c->out_offsets);
-    release(c->qbuf_in); release(c->qbuf_out);
-    release(c->d_cons); release(c->d_cons_var);
-    release(c->d_lut); release(c->d_lutoff); release(c->d_image); release(c->d_pen);
-    release(c->d_codes); release(c->d_disc_sets); release(c->d_disc_slab); release(c->d_disc_word);
-    release(c->d_disc_counts); release(c->d_disc_meta); release(c->d_disc_cand); release(c->d_disc_vm);
-    release(c->d_disc_table); release(c->d_disc_blk); release(c->d_disc_best);
-    release(c->d_g2_tests); release(c->d_g2_out);
-    pss_release(c);
-    if (c->search) {
-        c->search->release_all();
-        delete c->search;
-        c->search = nullptr;
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c) delete c;  // ~ulg_ctx
 }
 
 const char *ulg_last_error(const ulg_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -190,149 +212,16 @@ int ulg_disc_set_ess(ulg_ctx *c, double ess) {
 
 int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return ULG_ERR_ARG;
-    if (std::strcmp(name, "score_streams") == 0) {
-        if (value < 1 || value > 4) return set_err(c, ULG_ERR_ARG, "score_streams must be 1..4");
-        c->score_streams = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "score_small_layers") == 0) {
-        if (value < 0 || value > ULG_UNROLLED_PARENTS_GPU)
-            return set_err(c, ULG_ERR_ARG, "score_small_layers must be 0..8");
-        c->score_small_layers = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "score_fused") == 0) {
-        if (value < 0 || value > 4) return set_err(c, ULG_ERR_ARG, "score_fused must be 0..4");
-        c->score_fused = (int)value;
-        return ULG_OK;
-    }
-    // the largest unrank table in entries (score_plan.h); part of the graph key
-    if (std::strcmp(name, "score_unrank_lut") == 0) {
-        if (value < 0 || value > (int64_t)kLutMaxTotal)
-            return set_err(c, ULG_ERR_ARG, "score_unrank_lut must be 0..2^31-1");
-        c->score_unrank_lut = value;
-        return ULG_OK;
-    }
-    // the layer launches fill LDS from one packed image per launch
-    // (score_plan.h build_images), 0: from the separate arrays; part of the graph key
-    if (std::strcmp(name, "score_lds_image") == 0) {
-        if (value != 0 && value != 1) return set_err(c, ULG_ERR_ARG, "score_lds_image must be 0 or 1");
-        c->score_lds_image = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "score_variant") == 0) {
-        if (value != 1 && value != 49 && value != 65 && value != 113 && value != 241)
-            return set_err(c, ULG_ERR_ARG, "score_variant must be 1, 49, 65, 113 or 241");
-        c->score_variant = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "time_limit_ms") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "time_limit_ms must be >= 0");
-        c->time_limit_ms = value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "disc_dense_cells") == 0) {
-        if (value < 1 || value > 32768) return set_err(c, ULG_ERR_ARG, "disc_dense_cells must be 1..32768");
-        c->disc_dense_cells = value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "disc_prune") == 0) {
-        if (value != 0 && value != 1) return set_err(c, ULG_ERR_ARG, "disc_prune must be 0 or 1");
-        c->disc_prune = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "table_budget_kb") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "table_budget_kb must be >= 0");
-        c->table_budget_kb = (uint64_t)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "sweep_xcd") == 0) {
-        if (value < 0 || value > 1) return set_err(c, ULG_ERR_ARG, "sweep_xcd must be 0 or 1");
-        c->sweep_xcd = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "walk_k6") == 0) {
-        if (value != 1 && value != 2 && value != 4 && value != 8)
-            return set_err(c, ULG_ERR_ARG, "walk_k6 must be 1, 2, 4 or 8");
-        c->walk_k6 = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "walk_bucket") == 0) {
-        if (value != 0 && value != 1) return set_err(c, ULG_ERR_ARG, "walk_bucket must be 0 or 1");
-        c->walk_bucket = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "walk_small_sets") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "walk_small_sets must be >= 0");
-        c->walk_small_sets = value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "score_graph") == 0) {
-        if (value < 0 || value > 1) return set_err(c, ULG_ERR_ARG, "score_graph must be 0 or 1");
-        c->score_graph = (int)value;
-        if (!value) graph_reset(c);
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "score_xcd") == 0) {
-        if (value < 0 || value > 1) return set_err(c, ULG_ERR_ARG, "score_xcd must be 0 or 1");
-        c->score_xcd = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_host") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "wide_host must be >= 0");
-        c->wide_host_iters = (uint64_t)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_host_max") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "wide_host_max must be >= 0");
-        c->wide_host_max = (uint64_t)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_host_first") == 0) {
-        if (value < 0) return set_err(c, ULG_ERR_ARG, "wide_host_first must be >= 0");
-        c->wide_host_first = (uint64_t)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_host_q") == 0) {
-        if (value < 0 || value > 32) return set_err(c, ULG_ERR_ARG, "wide_host_q must be 0..32");
-        c->wide_host_q = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_host_threads") == 0) {
-        if (value < 1 || value > 64) return set_err(c, ULG_ERR_ARG, "wide_host_threads must be 1..64");
-        c->wide_host_threads = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_pool") == 0) {
-        if (value < 0 || value > 2) return set_err(c, ULG_ERR_ARG, "wide_pool must be 0, 1 or 2");
-        c->wide_pool = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_lds") == 0) {
-        if (value < 0 || value > 2) return set_err(c, ULG_ERR_ARG, "wide_lds must be 0, 1 or 2");
-        c->wide_lds = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_reduced") == 0) {
-        if (value < 0 || value > 1) return set_err(c, ULG_ERR_ARG, "wide_reduced must be 0 or 1");
-        c->wide_reduced = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "wide_prune") == 0) {
-        if (value < 0 || value > 1) return set_err(c, ULG_ERR_ARG, "wide_prune must be 0 or 1");
-        c->wide_prune = (int)value;
-        return ULG_OK;
-    }
-    if (std::strcmp(name, "sweep_table") == 0) {
-        if (value < 0 || value > 2) return set_err(c, ULG_ERR_ARG, "sweep_table must be 0, 1 or 2");
-        c->sweep_table = (int)value;
-        return ULG_OK;
-    }
-    return set_err(c, ULG_ERR_ARG, std::string("unknown option: ") + name);
+    std::string msg;
+    if (!options_set(c->opt, name, value, &msg)) return set_err(c, ULG_ERR_ARG, msg);
+    // the one option with a side effect: a graph captured earlier is dropped
+    if (std::strcmp(name, "score_graph") == 0 && !value) graph_reset(c);
+    return ULG_OK;
 }
 
 int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     if (!c || !name || !value) return ULG_ERR_ARG;
+    if (options_get(c->opt, name, value)) return ULG_OK;  // any option, as it stands
     if (std::strcmp(name, "out_of_time") == 0) {
         *value = c->out_of_time;
         return ULG_OK;
@@ -347,14 +236,23 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = (int64_t)c->last_err_word;
         return ULG_OK;
     }
-    // option score_unrank_lut as it stands, and the entries of the unrank tables the context holds
-    if (std::strcmp(name, "score_unrank_lut") == 0 || std::strcmp(name, "unrank_lut_entries") == 0) {
-        *value = name[0] == 's' ? c->score_unrank_lut : (int64_t)c->lut_cache.total;
+    // bytes the process holds through DevBuf / PinnedBuf, every context's together
+    if (std::strcmp(name, "device_bytes_live") == 0) {
+        *value = g_device_bytes.load();
         return ULG_OK;
     }
-    // option score_lds_image as it stands, and the bytes of the launch images the last call built
-    if (std::strcmp(name, "score_lds_image") == 0 || std::strcmp(name, "lds_image_bytes") == 0) {
-        *value = name[0] == 's' ? c->score_lds_image : (int64_t)c->plan.image.size();
+    if (std::strcmp(name, "pinned_bytes_live") == 0) {
+        *value = g_pinned_bytes.load();
+        return ULG_OK;
+    }
+    // the entries of the unrank tables the context holds
+    if (std::strcmp(name, "unrank_lut_entries") == 0) {
+        *value = (int64_t)c->lut_cache.total;
+        return ULG_OK;
+    }
+    // the bytes of the launch images the last call built
+    if (std::strcmp(name, "lds_image_bytes") == 0) {
+        *value = (int64_t)c->plan.image.size();
         return ULG_OK;
     }
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table

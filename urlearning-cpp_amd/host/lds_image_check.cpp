@@ -76,12 +76,12 @@ int main(int argc, char **argv) {
     }
     ScoreLists ls;
     if (ls.build(n, vars.data(), (int)vars.size(), masks.data(), maxp) != ScoreLists::kOk) return 3;
-    CbicOptions o;
+    Options o;
     o.score_variant = variant;
     o.score_unrank_lut = cap;
     CbicPlan p;
     LutCache cache;
-    p.build(ls, {}, {}, {}, o);
+    p.build(ls, {}, {}, {}, o, false);
     p.build_luts(ls, cap, cache);
     std::vector<double> gram((size_t)n * n);
     for (size_t i = 0; i < gram.size(); ++i) gram[i] = 1.0 + (double)i / 4096.0;  // no zero byte pattern repeats

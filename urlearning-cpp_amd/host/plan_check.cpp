@@ -60,7 +60,7 @@ Brute enumerate(int n, const std::vector<int> &vars, const std::vector<uint64_t>
 }
 
 void check_case(int n, const std::vector<int> &vars, const std::vector<uint64_t> &masks, int max_parents,
-                const CbicOptions &o, bool with_cons, ScoreLists &ls, CbicPlan &p) {
+                const Options &o, bool with_cons, ScoreLists &ls, CbicPlan &p) {
     const int nv = (int)vars.size();
     const int maxp = (max_parents < 1 || max_parents > n - 1) ? n - 1 : max_parents;
     const Brute b = enumerate(n, vars, masks, maxp);
@@ -102,7 +102,8 @@ void check_case(int n, const std::vector<int> &vars, const std::vector<uint64_t>
         cr = {1ull << 1, (1ull << 0) | (1ull << 4), 1ull << 5};
         cf = {1ull << 2, 1ull << 7, 0};
     }
-    p.build(ls, cv, cr, cf, o);
+    const bool wck = false;  // the ULG_WALK_CLOCK diagnostics are off
+    p.build(ls, cv, cr, cf, o, wck);
     CHECK(p.nv == nv && p.kmax == kmax);
     for (int i = 0; i < nv; ++i)
         CHECK(p.meta[i * 4] == vars[i] && p.meta[i * 4 + 1] == b.m[i] && p.meta[i * 4 + 2] == (int)(b.C[i] & 1ull));
@@ -118,7 +119,7 @@ void check_case(int n, const std::vector<int> &vars, const std::vector<uint64_t>
     // variant, groups and their stripes
     const bool two_pass = (o.score_variant & 16) != 0;
     CHECK(p.variant == o.score_variant);  // far below 2^30 slots
-    CHECK(p.G == (two_pass && !o.wck ? std::max(1, std::min(o.score_streams, nv)) : 1));
+    CHECK(p.G == (two_pass && !wck ? std::max(1, std::min((int)o.score_streams, nv)) : 1));
     const int G = p.G;
     std::vector<uint64_t> gcnt((size_t)G * (kmax + 1) * 2, 0);  // brute-force launch sizes
     for (int g = 0; g < G; ++g)
@@ -163,11 +164,11 @@ void check_case(int n, const std::vector<int> &vars, const std::vector<uint64_t>
     CHECK(p.qcap % 256 == 0 && 3 * p.qcap >= p.qwords && p.wave_cap == p.qcap / 64 + kBucketMax);
     CHECK(p.zero_q == (two_pass || kmax > kMaxL));
     CHECK(p.nqseg == (p.zero_q ? std::max<uint64_t>(p.segoff.back(), 1) : 0));
-    CHECK(p.bucket == ((o.score_variant & 112) == 112 && o.walk_bucket && !o.wck && kmax >= 5));
+    CHECK(p.bucket == ((o.score_variant & 112) == 112 && o.walk_bucket && !wck && kmax >= 5));
     // small and fused layers
-    CHECK(p.Ls == (two_pass && !o.wck ? std::min(kmax, std::min(kMaxL, o.score_small_layers)) : 0));
+    CHECK(p.Ls == (two_pass && !wck ? std::min(kmax, std::min(kMaxL, (int)o.score_small_layers)) : 0));
     CHECK(p.vsmall == (o.score_variant & 65));
-    CHECK(p.Lf == (p.vsmall == 65 && o.time_limit_ms == 0 ? std::min(p.Ls, o.score_fused) : 0));
+    CHECK(p.Lf == (p.vsmall == 65 && o.time_limit_ms == 0 ? std::min(p.Ls, (int)o.score_fused) : 0));
     CHECK(p.nb == (int64_t)((acc + kSlotsPerBlock - 1) / kSlotsPerBlock));
     // hi-cover offsets, the checked-bitset slice
     {
@@ -281,7 +282,7 @@ int main() {
                     for (int variant : {1, 113, 241})
                         for (int cons = 0; cons < 2; ++cons)
                             for (int alt = 0; alt < 3; ++alt) {
-                                CbicOptions o;  // alt 1: the pool forced, no pruning; alt 2: -r and the queue-order walk
+                                Options o;  // alt 1: the pool forced, no pruning; alt 2: -r and the queue-order walk
                                 o.score_variant = variant;
                                 o.score_streams = streams;
                                 if (alt == 1) o.wide_pool = 1, o.wide_prune = 0;

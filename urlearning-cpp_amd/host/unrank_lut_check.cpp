@@ -124,9 +124,9 @@ int run_plan(int argc, char **argv) {
         }
         if (a < argc) ++a;  // the separator
         if (ls.build(n, vars.data(), (int)vars.size(), masks.data(), maxp) != ScoreLists::kOk) return 3;
-        CbicOptions o;
+        Options o;
         o.score_unrank_lut = cap;
-        p.build(ls, {}, {}, {}, o);
+        p.build(ls, {}, {}, {}, o, false);
         p.build_luts(ls, cap, cache);
         std::printf("CALL %d kmax %d any %d new %zu total %llu\n", call++, p.kmax, p.lut_any ? 1 : 0, p.lut_new.size(),
                     (unsigned long long)cache.total);

@@ -564,6 +564,14 @@ int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
  * one loop each, as before.  The images are uploaded only when their bytes
  * change.  Lists and scores are bit-identical either way; ulg_get_info
  * "lds_image_bytes" reads the bytes of the last call's images.
+ * "score_narrow" (0/1, default 1): a layer launch of 5 or 6 parents of the
+ * default variant (241) whose every set mask, rank, launch-local index and
+ * table slot fits 32 bits runs the narrow form of the layer kernel, which
+ * carries them in 32-bit registers: every variable of the call has at most 32
+ * candidates, the launch's sets plus one block fit 32 bits and the table has
+ * fewer than 2^30 slots.  Any other launch, and every launch under 0, runs
+ * the 64-bit kernel.  Lists and scores are bit-identical either way;
+ * ulg_get_info "narrow_launches" counts the last call's narrow launches.
  * "disc_dense_cells" (1..32768, default 16384): a discrete set whose
  * contingency table has at most this many cells is counted in an int32 LDS
  * histogram; larger tables are counted in a hash table of their non-empty
@@ -627,6 +635,9 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * "disc_prune"), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
  * ulg_disc_mmpc performed / left out by its reliability rule),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
+ * "lds_image_bytes" (bytes of the last scoring call's launch images),
+ * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the
+ * narrow form, option "score_narrow"),
  * "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero

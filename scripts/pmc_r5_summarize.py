@@ -33,8 +33,11 @@ import sys
 # round 6: variant 241 (V = 209) and the key-sorted walk (walk_bucket_kernel;
 # its count / scatter kernels are summed in as "sort" when present)
 # round 15: the phase-0 launch (sets with variable 0) beside them, counters only
-KERNELS = {"score": "score_layer_kernel<6, 1, 209>", "walk": "walk_bucket_kernel<6, 1, ",
-           "score_var0": "score_layer_kernel<6, 0, 209>"}
+# round 21: the layer kernels carry a fourth template argument (the narrow
+# form); the prefixes match both the parent's names and the new ones, and the
+# summary names the form that ran ("kernels")
+KERNELS = {"score": "score_layer_kernel<6, 1, 209", "walk": "walk_bucket_kernel<6, 1, ",
+           "score_var0": "score_layer_kernel<6, 0, 209"}
 PAIR = ("score", "walk")  # the launch pair the traffic and L1 totals are summed over
 N_CU, N_XCD, N_SIMD = 256, 8, 1024
 
@@ -70,10 +73,15 @@ def main():
     pd = per_dispatch(outdir)
     out = {"config_id": "c3", "label": "score_layer_6_rest + walk_6_rest", "sets_per_launch": sets,
            "kernels": {k: pd[k]["kernel"] for k in KERNELS}, "grids": {k: pd[k]["grid"] for k in KERNELS},
-           "source": outdir}
+           "source": os.path.basename(os.path.normpath(outdir))}  # the run's tag, not where it was kept
+    # the commit the measured library was built from: ULG_COMMIT where the
+    # tree being measured is no git checkout (or the library is another
+    # commit's), else the checkout's HEAD
+    out["commit"] = os.environ.get("ULG_COMMIT") or None
     try:
-        out["commit"] = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True,
-                                       cwd=os.path.dirname(os.path.abspath(__file__))).stdout.strip() or None
+        if not out["commit"]:
+            out["commit"] = subprocess.run(["git", "rev-parse", "--short", "HEAD"], capture_output=True, text=True,
+                                           cwd=os.path.dirname(os.path.abspath(__file__))).stdout.strip() or None
     except OSError:
         out["commit"] = None
     tr, l1 = 0.0, 0.0

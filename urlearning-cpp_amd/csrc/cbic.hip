@@ -265,18 +265,29 @@ __device__ __forceinline__ uint32_t walk_key(const uint64_t (&ow)[W]) {
     return key;
 }
 
-template <int L, int PHASE, class BS>
+// MBCNT (the narrow layer kernels): the lane's place among the active lanes
+// from the hardware's masked bit count, the same number as the popcount of
+// the active lanes below it, without the lane index held in a register from
+// the top of the kernel (it was spilled there).
+template <int L, int PHASE, class BS, bool MBCNT = false>
 __device__ __forceinline__ void queue_walk(const BS &present, const BS &hi, uint64_t *queue,
                                            unsigned long long *qcount, unsigned long long *err, uint64_t slot,
                                            float ts, uint8_t *qkey = nullptr) {
     constexpr int W = BS::kWords;
     const unsigned long long act = __ballot(1);
-    const int lane = threadIdx.x & 63;
     const int leader = __ffsll((long long)act) - 1;
     unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(qcount, (unsigned long long)__popcll(act));
+    uint32_t below;  // active lanes below this one
+    if constexpr (MBCNT) {
+        below = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
+        if (below == 0u) base = atomicAdd(qcount, (unsigned long long)__popcll(act));
+    } else {
+        const int lane = threadIdx.x & 63;
+        if (lane == leader) base = atomicAdd(qcount, (unsigned long long)__popcll(act));
+        below = (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+    }
     base = __shfl(base, leader);
-    const uint64_t pos = base + (uint64_t)__popcll(act & ((1ull << lane) - 1ull));
+    const uint64_t pos = base + (uint64_t)below;
     // a segment holds at most kSegBlocks blocks' lanes by construction
     // (seg_count); a sizing mistake becomes an error status, not a stray write
     if (pos >= kSegEntries) {
@@ -377,11 +388,12 @@ __device__ void gather_stats(const BS &present, const BS &hi, uint32_t hotA, uin
 // Set r of variable vi's (layer L, phase) launch: its compact mask over the
 // candidate list, colex rank, and parent variables in ascending order (==
 // BIC_OLS parent_vec order).  smeta / scand / binom: the LDS copies.
-template <int L>
+// M: uint64_t, or uint32_t in the narrow form of the layer kernels
+template <int L, class M = uint64_t>
 struct SetHead {
     int v;
     bool z;
-    uint64_t cm, rankP;
+    M cm, rankP;
     int gv[L];
 };
 // out[r] = unrank_colex(r, l, U) for r < count = C(U, l): a context's unrank
@@ -452,27 +464,26 @@ __device__ __forceinline__ WaveVar wave_variable(const uint64_t *work, const int
 // have_um: um is the set's unranked mask read from the launch's unrank table
 // (UnrankPick below); otherwise the lane computes it.  RANK false: the caller
 // takes the set's rank from child_ranks and rankP stays 0.
-template <int L, int PHASE, bool RANK = true>
-__device__ __forceinline__ SetHead<L> set_head(const int *smeta, const uint8_t *scand, const uint32_t *binom, int vi,
-                                               uint64_t r, bool have_um = false, uint32_t um32 = 0u) {
-    SetHead<L> h;
+// M = uint32_t (narrow launches: m <= 32): the shift by one for variable 0
+// moves a mask over U = m - 1 <= 31 candidates, so bit 31 is the last one used.
+template <int L, int PHASE, bool RANK = true, class M = uint64_t>
+__device__ __forceinline__ SetHead<L, M> set_head(const int *smeta, const uint8_t *scand, const uint32_t *binom, int vi,
+                                                  M r, bool have_um = false, uint32_t um32 = 0u) {
+    SetHead<L, M> h;
     h.v = smeta[vi * 4 + 0];
     const int m = smeta[vi * 4 + 1];
     h.z = smeta[vi * 4 + 2] != 0;
-    uint64_t um = um32;
-    if (!have_um) um = unrank_colex(r, (PHASE == 0) ? L - 1 : L, (PHASE == 0 || h.z) ? m - 1 : m, binom);
-    if (PHASE == 0) h.cm = (um << 1) | 1ull;
+    M um = um32;
+    if (!have_um) um = unrank_colex<M>(r, (PHASE == 0) ? L - 1 : L, (PHASE == 0 || h.z) ? m - 1 : m, binom);
+    if (PHASE == 0) h.cm = (um << 1) | (M)1;
     else if (h.z) h.cm = um << 1;
     else h.cm = um;
-    h.rankP = RANK ? rank_colex(h.cm, binom) : 0ull;
+    h.rankP = RANK ? rank_colex(h.cm, binom) : (M)0;
     const uint8_t *cl = scand + vi * 64;
-    uint64_t rem = h.cm;
+    int el[L];
+    mask_elements<L>(h.cm, el);
 #pragma unroll
-    for (int i = 0; i < L; ++i) {
-        const int b = __builtin_ctzll(rem);
-        rem &= rem - 1;
-        h.gv[i] = cl[b];
-    }
+    for (int i = 0; i < L; ++i) h.gv[i] = cl[el[i]];
     return h;
 }
 
@@ -595,13 +606,14 @@ __device__ __forceinline__ void one_pass_set(const ScoreArgs &a, unsigned char *
 // The rest of a queued set's gathers (the keys the rules did not read), then
 // either the walk queue or, when the walk closure shows the walk cannot reach
 // a key >= -ts, the store it would make.  toffv: this variable's slab offsets.
-template <int L, int PHASE, int V, class BS>
+// (TO, M: the offsets' and the slot's 64-bit or narrow types, cbic_dev.h)
+template <int L, int PHASE, int V, class BS, class TO, class M>
 __device__ __forceinline__ void walk_or_store(const ScoreArgs &a, BS &present, BS &hib, const LocalSet<L> &ls,
-                                              float tk, const uint32_t *binom, bool zk, const uint64_t *toffv,
-                                              uint64_t seg, uint64_t sk, float hch) {
+                                              float tk, const uint32_t *binom, bool zk, TO toffv, uint64_t seg, M sk,
+                                              float hch) {
     constexpr int W = BS::kWords;
 #ifndef ULG_PROBE_NOPART2
-    gather_keys<L, PHASE, V, BS, LdPlain, 2>(present, hib, ls, -tk, binom, zk, a.table, toffv);
+    gather_keys<L, PHASE, V, BS, LdPlain, 2, TO>(present, hib, ls, -tk, binom, zk, a.table, toffv);
 #endif
     // no key >= -ts among the nodes the walk can test: it would store P
     // (80 % of the walked sets at C3's layer 6 end stored)
@@ -617,14 +629,14 @@ __device__ __forceinline__ void walk_or_store(const ScoreArgs &a, BS &present, B
     }
     if (may_hit) {
 #ifndef ULG_PROBE_NOQUEUE
-        queue_walk<L, PHASE>(present, hib, a.queue + seg * kSegEntries * (uint64_t)(1 + 2 * W),
-                             a.qcount + seg * kSegStride, a.err, sk, tk,
+        queue_walk<L, PHASE, BS, sizeof(M) == 4>(present, hib, a.queue + seg * kSegEntries * (uint64_t)(1 + 2 * W),
+                                                 a.qcount + seg * kSegStride, a.err, sk, tk,
                              a.qkey ? a.qkey + seg * kSegEntries : nullptr);
 #endif
-        if (a.hsub_out) a.hsub[sk] = hch;  // the walk raises it to -ts if it stores P
+        if (a.hsub_out) *slot_ptr(a.hsub, sk) = hch;  // the walk raises it to -ts if it stores P
     } else {
-        a.table[sk] = -tk;
-        if (a.hsub_out) a.hsub[sk] = fmaxf(-tk, hch);
+        *slot_ptr(a.table, sk) = -tk;
+        if (a.hsub_out) *slot_ptr(a.hsub, sk) = fmaxf(-tk, hch);
     }
 }
 
@@ -1992,10 +2004,11 @@ template <bool CONS, class... A>
 using TwinFn = std::conditional_t<CONS, void (*)(A..., const uint64_t *, int), void (*)(A...)>;
 template <bool CONS>
 using LayerFn = TwinFn<CONS, ScoreArgs>;
-template <int L, int V, bool CONS>
+template <int L, int V, bool CONS, bool NARROW = false>
 LayerFn<CONS> pick_phase(int phase) {
-    if constexpr (CONS) return phase == 0 ? score_layer_cons_kernel<L, 0, V> : score_layer_cons_kernel<L, 1, V>;
-    else return phase == 0 ? score_layer_kernel<L, 0, V> : score_layer_kernel<L, 1, V>;
+    if constexpr (CONS)
+        return phase == 0 ? score_layer_cons_kernel<L, 0, V, NARROW> : score_layer_cons_kernel<L, 1, V, NARROW>;
+    else return phase == 0 ? score_layer_kernel<L, 0, V, NARROW> : score_layer_kernel<L, 1, V, NARROW>;
 }
 // variants (ulg_set_option "score_variant"): bit 0 unrolled presence gathers
 // (layers <= 6), bit 4 two-pass (settle, queue the rest for a walk launch),
@@ -2008,8 +2021,13 @@ LayerFn<CONS> pick_phase(int phase) {
 // against 3.59 ms: a 64-set union tree repeats work a 256-set one shares);
 // round 1's loop gathers at every layer, stack-machine recursion,
 // decision-only per-lane walk and statistics build.
+// narrow: the launch's 32-bit form (CbicPlan::launch_narrow), built where
+// CbicPlan::narrow_built says so: the default variant's layers 5 and 6
 template <int L, bool CONS>
-LayerFn<CONS> pick(int phase, int variant) {
+LayerFn<CONS> pick(int phase, int variant, bool narrow) {
+    if constexpr (CbicPlan::narrow_built(L, 241))
+        if (narrow && variant == 241) return pick_phase<L, 209, CONS, true>(phase);
+    if (narrow) return nullptr;
     switch (variant) {
         case 1: return pick_phase<L, 1, CONS>(phase);
         case 49: return pick_phase<L, 17, CONS>(phase);
@@ -2118,16 +2136,16 @@ TwinFn<CONS, ScoreArgs, const uint64_t *> small_kernel(int Lf) {
 }
 
 template <bool CONS>
-LayerFn<CONS> layer_kernel(int L, int phase, int variant) {
+LayerFn<CONS> layer_kernel(int L, int phase, int variant, bool narrow = false) {
     switch (L) {
-        case 1: return pick<1, CONS>(phase, variant);
-        case 2: return pick<2, CONS>(phase, variant);
-        case 3: return pick<3, CONS>(phase, variant);
-        case 4: return pick<4, CONS>(phase, variant);
-        case 5: return pick<5, CONS>(phase, variant);
-        case 6: return pick<6, CONS>(phase, variant);
-        case 7: return pick<7, CONS>(phase, variant);
-        case 8: return pick<8, CONS>(phase, variant);
+        case 1: return pick<1, CONS>(phase, variant, narrow);
+        case 2: return pick<2, CONS>(phase, variant, narrow);
+        case 3: return pick<3, CONS>(phase, variant, narrow);
+        case 4: return pick<4, CONS>(phase, variant, narrow);
+        case 5: return pick<5, CONS>(phase, variant, narrow);
+        case 6: return pick<6, CONS>(phase, variant, narrow);
+        case 7: return pick<7, CONS>(phase, variant, narrow);
+        case 8: return pick<8, CONS>(phase, variant, narrow);
         default: return nullptr;
     }
 }
@@ -2843,8 +2861,11 @@ int launch_unrolled(const ScoreCall &k, int g, int L, int ph) {
     sa.qkey = bk ? c->d_qkey.p + (size_t)g * p.qcap : nullptr;
     // nothing reads the subset maxima of the top layer's second phase
     sa.hsub_out = !(L == p.kmax && ph == 1);
+    const bool nw = p.launch_narrow(g, L, ph);
+    if (nw && !layer_kernel<false>(L, ph, p.variant, true))
+        return set_err(c, ULG_ERR_STATE, "ulg_cbic_score: no narrow kernel for a launch planned narrow");
     int rc;
-    if ((rc = launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.variant), layer_kernel<true>(L, ph, p.variant),
+    if ((rc = launch_twin(c, k.cons, layer_kernel<false>(L, ph, p.variant, nw), layer_kernel<true>(L, ph, p.variant, nw),
                           dim3((unsigned)blocks), dim3(kBlock), lds_layout(k.ls.n, p.nv, k.ls.S, L, p.variant).total,
                           k.gst[g], kLayerNames[ph][L], sa)))
         return rc;
@@ -3111,7 +3132,7 @@ void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const 
                  (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr), dbits(c->pen),
                  (uint64_t)c->opt.score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
                  ptr(p.lut_any ? c->d_lutoff.p : nullptr), (uint64_t)c->opt.score_lds_image,
-                 ptr(p.image_any ? c->d_image.p : nullptr)});
+                 ptr(p.image_any ? c->d_image.p : nullptr), (uint64_t)c->opt.score_narrow});
     for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
     for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
     for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));

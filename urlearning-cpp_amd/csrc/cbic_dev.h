@@ -46,11 +46,14 @@ __device__ __forceinline__ uint32_t B(const uint32_t *binom, int a, int k) { ret
 // Ranks of the unrolled layers fit 32 bits (C(63, 8) < 2^32, and the table
 // clamps C(a, b) to 32 bits anyway), so the arithmetic stays in 32-bit
 // registers: the callers are the layer kernels (L <= 8) and the list write.
-__device__ __forceinline__ uint64_t unrank_colex(uint64_t r64, int l, int U, const uint32_t *binom) {
+// M: the mask type; uint32_t (the narrow layer kernels) holds every set of
+// U <= 32, element 31 at bit 31.
+template <class M = uint64_t>
+__device__ __forceinline__ M unrank_colex(uint64_t r64, int l, int U, const uint32_t *binom) {
     constexpr float kFact[9] = {1.f, 1.f, 2.f, 6.f, 24.f, 120.f, 720.f, 5040.f, 40320.f};
     constexpr float kInv[9] = {1.f, 1.f, 0.5f, 1.f / 3.f, 0.25f, 0.2f, 1.f / 6.f, 1.f / 7.f, 0.125f};
     uint32_t r = (uint32_t)r64;
-    uint64_t mask = 0;
+    M mask = 0;
     int c = U - 1;
     for (int i = l; i >= 1; --i) {
         int e;
@@ -73,18 +76,19 @@ __device__ __forceinline__ uint64_t unrank_colex(uint64_t r64, int l, int U, con
             while (cc >= 0 && B(binom, cc, i) > r) --cc;
             bc = B(binom, cc, i);
         }
-        mask |= 1ull << cc;
+        mask |= (M)1 << cc;
         r -= bc;
         c = cc - 1;
     }
     return mask;
 }
 
-__device__ __forceinline__ uint64_t rank_colex(uint64_t mask, const uint32_t *binom) {
+template <class M>
+__device__ __forceinline__ M rank_colex(M mask, const uint32_t *binom) {
     uint32_t r = 0;
     int j = 0;
     while (mask) {
-        const int a = __builtin_ctzll(mask);
+        const int a = mask_ctz(mask);
         mask &= mask - 1;
         ++j;
         r += B(binom, a, j);
@@ -249,9 +253,11 @@ struct PresList {
 //
 // vals (non-null): each gathered key's value at vals[t] (a local array of
 // 2^Q floats the caller indexes with constants only, so it stays in registers)
-template <int L, int PHASE, int Q, int W, class LD = LdPlain, int NB = 16, bool B32 = true, int PART = 0>
+// TO: the variable's slab offsets, `const uint64_t *` or their low words (LowWords)
+template <int L, int PHASE, int Q, int W, class LD = LdPlain, int NB = 16, bool B32 = true, int PART = 0,
+          class TO = const uint64_t *>
 __device__ __forceinline__ void presence_unrolled(Bits<W> &present, Bits<W> &hi, float thr, const uint32_t *binom,
-                                                  uint64_t cpack, bool z, const float *table, const uint64_t *toffv,
+                                                  uint64_t cpack, bool z, const float *table, TO toffv,
                                                   float *vals = nullptr) {
     constexpr PresList<L, PHASE, Q, PART> PL{};
     using Slot = std::conditional_t<B32, uint32_t, uint64_t>;
@@ -352,17 +358,17 @@ struct LocalSet {
 // candidate (z; the host counts no phase-0 sets otherwise), phase-1 sets never
 // hold it -- so the root and the top list are constants of the phase and the
 // rule tests on them compile to fixed bit positions.
-template <int L, int PHASE>
-__device__ __forceinline__ LocalSet<L> local_set(uint64_t cm, bool z) {
+template <int L, int PHASE, class M>
+__device__ __forceinline__ LocalSet<L> local_set(M cm, bool z) {
     LocalSet<L> s;
     s.v0inP = PHASE == 0;
-    const uint64_t E = (PHASE == 0 || z) ? (cm & ~1ull) : cm;
+    const M E = (PHASE == 0 || z) ? (cm & ~(M)1) : cm;
     s.cpack = 0;
-    uint64_t rem = E;
+    M rem = E;
 #pragma unroll
     for (int i = 1; i <= L; ++i) {
         if (rem) {
-            const uint64_t b = (uint64_t)__builtin_ctzll(rem);
+            const uint64_t b = (uint64_t)mask_ctz(rem);
             rem &= rem - 1;
             s.cpack |= b << (6 * i);
         }
@@ -379,14 +385,13 @@ __device__ __forceinline__ LocalSet<L> local_set(uint64_t cm, bool z) {
 // V == 1 is the form kept for tables of 2^30 slots or more (64-bit slots).
 // PART (unrolled layers only): 0 every key, 1 the keys settle_rules reads, 2
 // the rest (the loop form gathers every key under PART 0 and 1, none under 2).
-template <int L, int PHASE, int V, class BS, class LD = LdPlain, int PART = 0>
+template <int L, int PHASE, int V, class BS, class LD = LdPlain, int PART = 0, class TO = const uint64_t *>
 __device__ __forceinline__ void gather_keys(BS &present, BS &hi, const LocalSet<L> &ls, float thr,
-                                            const uint32_t *binom, bool z, const float *table,
-                                            const uint64_t *toffv) {
+                                            const uint32_t *binom, bool z, const float *table, TO toffv) {
     constexpr int W = BS::kWords;
     if constexpr (L <= 6 && (V & 1)) {
-        presence_unrolled<L, PHASE, (PHASE == 0 ? L : L + 1), W, LD, 8, (V != 1), PART>(present, hi, thr, binom,
-                                                                                        ls.cpack, z, table, toffv);
+        presence_unrolled<L, PHASE, (PHASE == 0 ? L : L + 1), W, LD, 8, (V != 1), PART, TO>(present, hi, thr, binom,
+                                                                                            ls.cpack, z, table, toffv);
     } else if constexpr (PART == 2) {
         return;
     } else {
@@ -505,10 +510,37 @@ __device__ __forceinline__ bool settle_rules(const BS &present, const BS &hi, co
 // and a set whose U(P) holds no key >= -ts is stored without its 2^(L+1)
 // presence gathers.  The children's ranks, and P's own: child_ranks_t,
 // score_plan.h (host-checked there).
-template <int L, bool WITH0>
-__device__ __forceinline__ uint32_t child_ranks(uint64_t cm, const uint32_t *binom, uint64_t (&rc)[L],
-                                                uint64_t (&rz)[L]) {
+template <int L, bool WITH0, class M>
+__device__ __forceinline__ uint32_t child_ranks(M cm, const uint32_t *binom, M (&rc)[L], M (&rz)[L]) {
     return child_ranks_t<L, WITH0, kBinomK>(cm, binom, rc, rz);
+}
+
+// The 32-bit side of the layer kernels' two forms.  The LDS
+// copies of the work prefixes and slab offsets stay 8-byte entries (one
+// layout, one launch image for both forms); the narrow form reads their low
+// words.
+template <class M>
+__device__ __forceinline__ M low_entry(const uint64_t *p, uint32_t i) {
+    if constexpr (sizeof(M) == 4) return reinterpret_cast<const uint32_t *>(p)[2u * i];
+    else return p[i];
+}
+struct LowWords {
+    const uint32_t *p;  // the low word of 8-byte entry 0
+    __device__ __forceinline__ uint32_t operator[](int i) const { return p[2 * i]; }
+};
+// a variable's row of slab offsets as gather_keys / walk_or_store take it
+template <class M>
+__device__ __forceinline__ auto toff_row(const uint64_t *toff, int vi, int S) {
+    if constexpr (sizeof(M) == 4) return LowWords{reinterpret_cast<const uint32_t *>(toff) + 2u * ((uint32_t)vi * (uint32_t)S)};
+    else return toff + (uint64_t)vi * S;
+}
+// table slot -> address: a 32-bit slot is below 2^30 (narrow_fits), so its
+// byte offset is a 32-bit shift beside the base in SGPRs
+template <class T, class M>
+__device__ __forceinline__ T *slot_ptr(T *base, M slot) {
+    static_assert(sizeof(T) == 4, "4-byte table entries");
+    if constexpr (sizeof(M) == 4) return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + (slot << 2));
+    else return base + slot;
 }
 
 // May find_best_subset_score's walk of P reach a key >= -ts?  A superset of

@@ -6,13 +6,19 @@
 // after ts is the same text.  Two kernels from one text, not one template
 // with a flag: the unconstrained kernels keep the code, and so the register
 // allocation, they had before constraints existed (DESIGN.md 3.1h).
-template <int L, int PHASE, int V>
+// NARROW (DESIGN.md 3.1p; a launch CbicPlan::launch_narrow picks): every set
+// mask, rank, launch-local index and table slot of the launch fits 32 bits,
+// and M, the type that carries them, is uint32_t -- one register and one
+// instruction where the 64-bit form spends two or more.  The integers, the
+// LDS layout and every floating-point expression are the same.
+template <int L, int PHASE, int V, bool NARROW = false>
 __global__ void __launch_bounds__(kBlock, (score_min_waves<L, PHASE, V>()))
 #if ULG_CONS
 score_layer_cons_kernel(ScoreArgs a, const uint64_t *cons, int cons_words) {
 #else
 score_layer_kernel(ScoreArgs a) {
 #endif
+    using M = std::conditional_t<NARROW, uint32_t, uint64_t>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const LdsLayout lay = lds_layout(a.n, a.nv, a.S, L, V);
 #if ULG_CONS
@@ -46,16 +52,17 @@ score_layer_kernel(ScoreArgs a) {
     const uint4 im0 = piece(0), im1 = piece(1), im2 = piece(2), im3 = piece(3);
     // the wave's variable on the scalar unit, and with it the lane's unrank
     // table entry, before the fill (wave_variable, cbic.hip)
-    const uint64_t gid0 = (uint64_t)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
+    const M gid0 = (M)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
     const WaveVar wv = wave_variable(a.work, a.lut_off, a.nv, a.total, gid0 - (threadIdx.x & 63u));
-    const bool valid = gid0 < wv.total;
+    const M wtotal = (M)wv.total, wbase = (M)wv.base;  // wave-uniform; NARROW: below 2^32 with a block to spare
+    const bool valid = gid0 < wtotal;
     // CMP: every lane reaches the block's barrier; a lane past the launch's
     // sets scores the last one again and writes nothing
-    const uint64_t gid = valid ? gid0 : wv.total - 1;
+    const M gid = valid ? gid0 : wtotal - 1;
     bool have_um = false;
     uint32_t um = 0u;
     if (wv.vi >= 0 && wv.loff >= 0) {
-        um = a.lut[(uint32_t)wv.loff + (uint32_t)(gid - wv.base)];
+        um = a.lut[(uint32_t)wv.loff + (uint32_t)(gid - wbase)];
         have_um = true;
     }
     int32_t *slut = reinterpret_cast<int32_t *>(smem + lay.lutoff);
@@ -84,15 +91,15 @@ score_layer_kernel(ScoreArgs a) {
 
     if (!CMP && !valid) return;
     int vi = wv.vi;
-    uint64_t r = gid - wv.base;
+    M r = gid - wbase;
     if (wv.vi < 0) {  // the wave straddles variables: each lane finds its own
         int lo = 0, hi = a.nv;
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;
-            if (work[mid] <= gid) lo = mid; else hi = mid;
+            if (low_entry<M>(work, mid) <= gid) lo = mid; else hi = mid;
         }
         vi = lo;
-        r = gid - work[vi];
+        r = gid - low_entry<M>(work, vi);
         if (a.lut_off) {
             const int32_t lo2 = slut[vi];
             if (lo2 >= 0) {
@@ -102,9 +109,9 @@ score_layer_kernel(ScoreArgs a) {
         }
     }
     // CMP: the set's rank comes out of child_ranks below
-    const SetHead<L> hd = set_head<L, PHASE, !CMP>(smeta, scand, binom, vi, r, have_um, um);
+    const SetHead<L, M> hd = set_head<L, PHASE, !CMP, M>(smeta, scand, binom, vi, r, have_um, um);
     const bool z = hd.z;
-    const uint64_t cm = hd.cm;
+    const M cm = hd.cm;
 
 #ifndef ULG_PROBE_NOSCORE  // ULG_PROBE_*: timing-only builds, see the two-pass section below
 #if ULG_CONS
@@ -120,10 +127,10 @@ score_layer_kernel(ScoreArgs a) {
     if constexpr (CMP) {
         // 1. settle by the subset maxima: ts >= 0, no key >= -ts in U(P), or a
         //    present direct child >= -ts (always visited at the top level)
-        const uint64_t vbase = (uint64_t)vi * a.S;
-        uint64_t rc[L], rz[L];
-        const uint64_t rankP = child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
-        const uint64_t slot = toff[vbase + L] + rankP;
+        const M vbase = (M)vi * a.S;
+        M rc[L], rz[L];
+        const M rankP = child_ranks<L, PHASE == 1>(cm, binom, rc, rz);
+        const M slot = low_entry<M>(toff, vbase + L) + rankP;
         // every load of the settle issued at once (the children's maxima and
         // values, the var-0 toggles' maxima): one memory round trip instead
         // of up to three dependent ones
@@ -136,14 +143,17 @@ score_layer_kernel(ScoreArgs a) {
 #endif
         {
             float ch[L], cv[L], zv[L];
-            const uint32_t o1 = (uint32_t)toff[vbase + L - 1], o0 = (uint32_t)toff[vbase + L];
+            // a child's slot: 32-bit either way; NARROW turns it into a 32-bit
+            // byte offset beside the table's base (slot_ptr), not a 64-bit address per load
+            using S32 = std::conditional_t<NARROW, uint32_t, uint64_t>;
+            const uint32_t o1 = (uint32_t)low_entry<M>(toff, vbase + L - 1), o0 = (uint32_t)low_entry<M>(toff, vbase + L);
 #pragma unroll
             for (int i = 0; i < L; ++i) {
                 if constexpr (L > 1) {
-                    ch[i] = a.hsub[o1 + (uint32_t)rc[i]];
-                    cv[i] = a.table[o1 + (uint32_t)rc[i]];
+                    ch[i] = *slot_ptr(a.hsub, (S32)(o1 + (uint32_t)rc[i]));
+                    cv[i] = *slot_ptr(a.table, (S32)(o1 + (uint32_t)rc[i]));
                 }
-                if constexpr (PHASE == 1) zv[i] = a.hsub[(z ? o0 : 0u) + (z ? (uint32_t)rz[i] : 0u)];
+                if constexpr (PHASE == 1) zv[i] = *slot_ptr(a.hsub, (S32)((z ? o0 : 0u) + (z ? (uint32_t)rz[i] : 0u)));
             }
             const float thr = -ts;
 #pragma unroll
@@ -182,8 +192,8 @@ score_layer_kernel(ScoreArgs a) {
             }
         }
         if (valid && !need) {
-            a.table[slot] = out;
-            if (a.hsub_out) a.hsub[slot] = fmaxf(out, hch);
+            *slot_ptr(a.table, slot) = out;
+            if (a.hsub_out) *slot_ptr(a.hsub, slot) = fmaxf(out, hch);
         }
 // ULG_PROBE_*: timing-only builds (wrong lists, never shipped) that drop one
 // part of the two-pass kernel (scripts/r5_kernel_ab.sh, DESIGN.md §3.1d)
@@ -193,8 +203,9 @@ score_layer_kernel(ScoreArgs a) {
         // 2. the rest of the block's sets, compacted in LDS, so the presence
         //    gathers (2^(L+1) reads each) run on dense waves
         unsigned int *cnt = reinterpret_cast<unsigned int *>(smem + lay.cmp);
-        uint64_t *ecm = reinterpret_cast<uint64_t *>(smem + lay.cmp + 16);
-        uint32_t *eslot = reinterpret_cast<uint32_t *>(ecm + kBlock);
+        // (NARROW: 4-byte masks fill the first half of the masks' column; the carve is the same)
+        M *ecm = reinterpret_cast<M *>(smem + lay.cmp + 16);
+        uint32_t *eslot = reinterpret_cast<uint32_t *>(smem + lay.cmp + 16 + kBlock * 8);
         float *ets = reinterpret_cast<float *>(eslot + kBlock);
         float *ehch = ets + kBlock;
         int *evi = reinterpret_cast<int *>(ehch + kBlock);
@@ -232,8 +243,8 @@ score_layer_kernel(ScoreArgs a) {
 #endif
         const bool zk = smeta[vk * 4 + 2] != 0;
         const float tk = a1 ? ets[k] : -1.0f;
-        const uint64_t sk = a1 ? eslot[k] : 0u;
-        const uint64_t cmk = a1 ? ecm[k] : 1ull;
+        const M sk = a1 ? eslot[k] : 0u;
+        const M cmk = a1 ? ecm[k] : (M)1;
         const float hk1 = a1 ? ehch[k] : absent_f();
         uint64_t *lds_bits = reinterpret_cast<uint64_t *>(smem + lay.bits) + threadIdx.x;
         const LocalSet<L> ls = local_set<L, PHASE>(cmk, zk);
@@ -249,7 +260,7 @@ score_layer_kernel(ScoreArgs a) {
             // test)
 #ifndef ULG_PROBE_NOPART1
             gather_keys<L, PHASE, V, BS, LdPlain, 1>(present, hib, ls, -tk, binom, zk, a.table,
-                                                    toff + (uint64_t)vk * a.S);
+                                                    toff_row<M>(toff, vk, a.S));
 #endif
 #ifndef ULG_PROBE_NORULES
             const bool dom = settle_rules<L, PHASE, BS, true>(present, hib, ls, q);
@@ -263,14 +274,14 @@ score_layer_kernel(ScoreArgs a) {
                 p2.clear();
                 h2.clear();
                 gather_keys<L, PHASE, V, BS, LdPlain, 0>(p2, h2, ls, -tk, binom, zk, a.table,
-                                                        toff + (uint64_t)vk * a.S);
+                                                        toff_row<M>(toff, vk, a.S));
                 gather_stats<L, PHASE>(p2, h2, hk & 0xffu, hk >> 8, zk, q);
             }
 #endif
             if (!q) {
                 const float o = dom ? absent_f() : -tk;
-                a.table[sk] = o;
-                if (a.hsub_out) a.hsub[sk] = fmaxf(o, hk1);
+                *slot_ptr(a.table, sk) = o;
+                if (a.hsub_out) *slot_ptr(a.hsub, sk) = fmaxf(o, hk1);
             }
         }
         if constexpr (CMP2) {
@@ -299,7 +310,7 @@ score_layer_kernel(ScoreArgs a) {
             const int vq = evi[k];
             const bool zq = smeta[vq * 4 + 2] != 0;
             const float tq = ets[k];
-            const uint64_t sq = eslot[k];
+            const M sq = eslot[k];
             const float hq = ehch[k];
             const LocalSet<L> lq = local_set<L, PHASE>(ecm[k], zq);
             BS pq = make_bits<BS>(lds_bits), hq_bits = make_bits<BS>(lds_bits);
@@ -308,10 +319,10 @@ score_layer_kernel(ScoreArgs a) {
                 pq.w[j] = c2w[j * kBlock + k];
                 hq_bits.w[j] = c2w[(W + j) * kBlock + k];
             }
-            walk_or_store<L, PHASE, V, BS>(a, pq, hq_bits, lq, tq, binom, zq, toff + (uint64_t)vq * a.S, seg, sq, hq);
+            walk_or_store<L, PHASE, V, BS>(a, pq, hq_bits, lq, tq, binom, zq, toff_row<M>(toff, vq, a.S), seg, sq, hq);
         } else {
             if (q)
-                walk_or_store<L, PHASE, V, BS>(a, present, hib, ls, tk, binom, zk, toff + (uint64_t)vk * a.S, seg, sk,
+                walk_or_store<L, PHASE, V, BS>(a, present, hib, ls, tk, binom, zk, toff_row<M>(toff, vk, a.S), seg, sk,
                                                hk1);
         }
         return;

@@ -20,6 +20,7 @@ struct Options {
     int64_t score_fused = 3;         // ... and layers <= this (<= small layers) in one launch, a workgroup per variable
     int64_t score_unrank_lut = kLutDefaultCap;  // largest unrank table in entries (score_plan.h LutCache), 0: none
     int64_t score_lds_image = 1;     // the layer launches fill LDS from a packed image (score_plan.h build_images)
+    int64_t score_narrow = 1;        // layer launches whose every mask fits 32 bits run the narrow kernels (score_plan.h narrow_fits)
     int64_t score_variant = 241;
     int64_t score_graph = 1;         // scoring call: replay the captured launch sequence
     int64_t score_xcd = 1;           // scoring kernels: contiguous runs of sets per XCD
@@ -62,6 +63,7 @@ constexpr OptionRow kOptionRows[] = {
     {"score_fused", &Options::score_fused, 0, 4, 0, {}, "0..4"},
     {"score_unrank_lut", &Options::score_unrank_lut, 0, (int64_t)kLutMaxTotal, 0, {}, "0..2^31-1"},
     {"score_lds_image", &Options::score_lds_image, 0, 1, 0, {}, "0 or 1"},
+    {"score_narrow", &Options::score_narrow, 0, 1, 0, {}, "0 or 1"},
     {"score_variant", &Options::score_variant, 0, 0, 5, {1, 49, 65, 113, 241}, "1, 49, 65, 113 or 241"},
     {"score_graph", &Options::score_graph, 0, 1, 0, {}, "0 or 1"},
     {"score_xcd", &Options::score_xcd, 0, 1, 0, {}, "0 or 1"},

@@ -224,13 +224,30 @@ struct ScoreLists {
 // Ranks of the unrolled layers fit 32 bits.  Host and device: the layer
 // kernels' child_ranks (cbic_dev.h) is this function, and
 // host/unrank_lut_check.cpp runs it against the enumeration order.
-template <int L, bool WITH0, int STRIDE>
-ULG_HD inline __attribute__((always_inline)) uint32_t child_ranks_t(uint64_t cm, const uint32_t *binom, uint64_t (&rc)[L], uint64_t (&rz)[L]) {
-    uint32_t e[L], d[L], f[L];
-    uint64_t rem = cm;
+// M: the mask and rank type, uint64_t, or uint32_t in the narrow layer kernels
+// (launches whose every mask fits 32 bits, CbicPlan::narrow_fits): the same
+// integers from one-register masks (host/narrow_check.cpp).
+ULG_HD inline int mask_ctz(uint64_t x) { return __builtin_ctzll(x); }
+ULG_HD inline int mask_ctz(uint32_t x) { return __builtin_ctz(x); }
+// The L lowest elements of a mask in increasing order (the mask holds at
+// least L): set_head's walk of a set's members (cbic.hip); child_ranks_t
+// below walks the same chain, and the compiler shares the two.
+template <int L, class M>
+ULG_HD inline __attribute__((always_inline)) void mask_elements(M mask, int (&el)[L]) {
+    M rem = mask;
     ULG_UNROLL
     for (int j = 0; j < L; ++j) {
-        const int aj = __builtin_ctzll(rem);
+        el[j] = mask_ctz(rem);
+        rem &= rem - 1;
+    }
+}
+template <int L, bool WITH0, int STRIDE, class M>
+ULG_HD inline __attribute__((always_inline)) uint32_t child_ranks_t(M cm, const uint32_t *binom, M (&rc)[L], M (&rz)[L]) {
+    uint32_t e[L], d[L], f[L];
+    M rem = cm;
+    ULG_UNROLL
+    for (int j = 0; j < L; ++j) {
+        const int aj = mask_ctz(rem);
         rem &= rem - 1;
         e[j] = binom[aj * STRIDE + j + 1];
         d[j] = binom[aj * STRIDE + j];
@@ -357,6 +374,25 @@ struct CbicPlan {
     std::vector<LutTable> lut_new;
     bool lut_any = false;
     size_t lut_offset(int L, int ph) const { return ((size_t)L * 2 + ph) * nv; }
+
+    // Narrow launches (option score_narrow): the form of the
+    // layer kernels whose set masks, ranks, launch-local indices and slots
+    // are 32-bit.  A launch takes it when the form exists for its (layer,
+    // variant) and, whichever lane looks, no value can need a 33rd bit: every
+    // variable listed in the launch's tables -- all of the call's, whichever
+    // stream group scores them -- has at most 32 candidates (a compact mask,
+    // shifted left by one for variable 0 or not, ends at bit 31; a lane
+    // without an unrank table computes a mask over U <= 32), the launch's
+    // sets plus one block of lanes past them fit 32 bits, and every table
+    // slot is below 2^30 (the gathers' 32-bit byte offsets).  Anything else
+    // runs the 64-bit kernel.
+    static constexpr bool narrow_built(int L, int variant) { return variant == 241 && (L == 5 || L == 6); }
+    static constexpr bool narrow_fits(int max_m, uint64_t sets, uint64_t total_slots) {
+        return max_m <= 32 && sets <= (1ull << 32) - (uint64_t)kBlock && (total_slots >> 30) == 0;
+    }
+    std::vector<uint8_t> narrow;  // [seg_slot(g, L, ph)] 1: the launch runs the narrow form
+    int narrow_launches = 0;      // launches of this call that do
+    bool launch_narrow(int g, int L, int ph) const { return !narrow.empty() && narrow[seg_slot(g, L, ph)] != 0; }
 
     // After build(): which tables the call's layer launches read.  A table
     // exists for U <= kLutMaxU and 0 < C(U, l) <= cap, while the cache stays
@@ -538,6 +574,18 @@ struct CbicPlan {
         Ls = (variant & 16) && !wck ? std::min(kmax, std::min(kMaxL, (int)o.score_small_layers)) : 0;
         vsmall = variant & 65;
         Lf = vsmall == 65 && o.time_limit_ms == 0 ? std::min(Ls, (int)o.score_fused) : 0;
+        narrow.assign(nseg_slots, 0);
+        narrow_launches = 0;
+        int max_m = 0;
+        for (int i = 0; i < nv; ++i) max_m = std::max(max_m, mv[i]);
+        for (int g = 0; g < G && o.score_narrow; ++g)
+            for (int L = Ls + 1; L <= std::min(kmax, kMaxL); ++L)
+                for (int ph = 0; ph < 2; ++ph) {
+                    const uint64_t cnt = launch_count(g, L, ph);
+                    if (cnt == 0 || !narrow_built(L, variant) || !narrow_fits(max_m, cnt, ls.total_slots)) continue;
+                    narrow[seg_slot(g, L, ph)] = 1;
+                    ++narrow_launches;
+                }
         build_pool(ls, o);
         nb = (int64_t)((ls.total_slots + kSlotsPerBlock - 1) / kSlotsPerBlock);
     }

@@ -255,6 +255,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = (int64_t)c->plan.image.size();
         return ULG_OK;
     }
+    // layer launches of the last ulg_cbic_score that ran the narrow (32-bit) kernels
+    if (std::strcmp(name, "narrow_launches") == 0) {
+        *value = c->plan.narrow_launches;
+        return ULG_OK;
+    }
     // the last ulg_disc_score: sets counted in the LDS histogram / in the hash table
     if (std::strcmp(name, "disc_dense_sets") == 0 || std::strcmp(name, "disc_sparse_sets") == 0) {
         *value = c->disc_path_sets[name[5] == 's' ? 1 : 0];

@@ -207,11 +207,13 @@ int ulg_cbic_set_constraints(ulg_ctx *ctx, int count, const int *vars,
 int ulg_cbic_score_sets(ulg_ctx *ctx, int64_t count, const int *vars,
                         const uint64_t *parents, float *neg_scores);
 
-/* ---- discrete scoring: BIC (bic_scoring_function.cpp, log_likelihood_calculator.cpp)
- *      and BDeu (bdeu_scoring_function.cpp) ---- */
+/* ---- discrete scoring: BIC (bic_scoring_function.cpp, log_likelihood_calculator.cpp),
+ *      BDeu (bdeu_scoring_function.cpp) and fNML (fnml_scoring_function.cpp) ---- */
 #define ULG_SCORE_BIC 1
 /* 2 is not a kind: it has always been refused with ULG_ERR_ARG and stays so. */
 #define ULG_SCORE_BDEU 3
+/* 0 and 4 are not kinds either. */
+#define ULG_SCORE_FNML 5
 /* codes_colmajor: N x n value codes, column-major (column j = variable j);
  * arity[j] = cardinality of variable j.  n <= 63, 1 <= arity <= 255,
  * 2 <= N < 2^31.  Every code must be below its column's arity; the upload
@@ -222,7 +224,8 @@ int ulg_cbic_score_sets(ulg_ctx *ctx, int64_t count, const int *vars,
  * likewise.  Either load clears ulg_cbic_set_constraints. */
 int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n, const int *arity);
 /* ulg_cbic_score's arguments and counts for a discrete score (kind =
- * ULG_SCORE_BIC or ULG_SCORE_BDEU, see below; anything else is ULG_ERR_ARG).
+ * ULG_SCORE_BIC, ULG_SCORE_BDEU or ULG_SCORE_FNML, see below; anything else is
+ * ULG_ERR_ARG).
  * What follows is the BIC value.  max_parents is taken as
  * given (< 1 or > n - 1 means n - 1): the BIC limit log(2N / log N) is the
  * command line's job (score_main.cpp:300-304).  The value of (v, P) is
@@ -277,7 +280,43 @@ int ulg_disc_load(ulg_ctx *ctx, const uint8_t *codes_colmajor, int64_t N, int n,
  * cells on; here a_j and a_jk are FP64 for every q r < 2^63 and the sum is
  * exact, as for BIC.  De Campos pruning (enableDeCamposPruning) is not built.
  * Replaces BDeuScoringFunction::lg, calculateScore and calculate
- * (bdeu_scoring_function.cpp:21-35, 69-79, 117-166). */
+ * (bdeu_scoring_function.cpp:21-35, 69-79, 117-166).
+ *
+ * kind = ULG_SCORE_FNML: the factorized normalized maximum likelihood score,
+ * which has no hyper-parameter.  With r = r_v,
+ *   s(v, P) = sum_cells n_jk ln n_jk - sum_j n_j ln n_j
+ *           - sum over non-empty configs ln C(r, n_j)
+ * where C(r, n) is the normaliser (regret) of the multinomial NML distribution:
+ *   C(2, n) = sum_{h=0..n} binom(n, h) (h/n)^h ((n-h)/n)^(n-h)   (1, 2, 2.5, 26/9, ...)
+ * summed exactly for n <= 1000 (on the host, in long double, correct to an
+ * FP64 ulp) and Szpankowski's three-term approximation
+ *   exp(ln(n pi / 2) / 2 + sqrt(8 / (9 n pi)) + (1/12 - 4 / (9 pi)) / n)
+ * above, which is the reference's threshold: the approximation lies 5.5e-7
+ * above the exact sum at n = 1001, so a configuration's regret steps by that
+ * much between n_j = 1000 and 1001.  C(k, n) = C(k-1, n) + n / (k-2) C(k-2, n)
+ * runs in FP64 on the ratio C(k, n) / C(k-1, n) and in log space
+ * (csrc/disc_fnml.h).  The regrets of the loaded columns' arities live in a
+ * device table of fixed-point integers, built by the first fNML call after
+ * ulg_disc_load (fnml_regret_kernel) and kept until the next load of either
+ * kind: ulg_get_info("fnml_table_bytes") is its size, 0 while there is none.
+ * (distinct arities >= 2) x (N + 1) > 2^28 entries returns
+ * ULG_ERR_UNSUPPORTED.  Every term -- the n ln n terms and each regret -- is
+ * rounded once to a fixed-point integer (scale 2^-shift, a function of N and
+ * the largest arity), the integer sum is rounded to float once: bit-identical
+ * on the dense and sparse counting paths, across calls and for any grid.
+ * Everything else is as for BIC and BDeu: the store rule, 0 for a variable of
+ * arity 1, 1 and never stored for a violating set, ULG_ERR_UNSUPPORTED from
+ * 2^63 cells or above ULG_MAX_PARENTS_GPU parents, time_limit_ms, option
+ * "disc_prune" and every ulg_get_info value; there is no BIC parent limit
+ * (score_main.cpp:300-306 applies it to "bic" only).
+ * Two departures from the reference: it runs the recurrence on float values
+ * and sums the regrets in float, which turn infinite once C(r, n) passes
+ * 3.4e38 (r = 60, n = 1000: ln C = 117.5) -- here FP64 and log space, finite
+ * for every r <= 255 and N < 2^31; and below n = 1001 it reads 12-digit
+ * literals rounded to float where this is the exact sum.
+ * Replaces fNMLScoringFunction's calculateScore, calculate and regret
+ * (fnml_scoring_function.cpp:17-74) and the table of
+ * fnml_scoring_function.h:300-340. */
 int ulg_disc_score(ulg_ctx *ctx, int kind, const int *vars, int nv, const uint64_t *candidates,
                    int max_parents, int64_t *total_stored, int64_t *total_scored);
 /* The equivalent sample size of ULG_SCORE_BDEU: sticky, default 1.0, kept
@@ -289,6 +328,11 @@ int ulg_disc_set_ess(ulg_ctx *ctx, double ess);
  * either kind) without the store rule (a violating set gives 1). */
 int ulg_disc_score_sets(ulg_ctx *ctx, int kind, int64_t count, const int *vars,
                         const uint64_t *parents, float *scores);
+/* diagnostics: out[i] = ln C(arity, first + i), i < count, as ULG_SCORE_FNML
+ * uses it: the device table's fixed-point entries converted back.  Builds the
+ * table if need be.  ULG_ERR_ARG for an arity that no loaded column has or a
+ * range that leaves 0 .. N; ULG_ERR_STATE without discrete data. */
+int ulg_disc_regret(ulg_ctx *ctx, int arity, int64_t first, int64_t count, double *out);
 /* diagnostics: the dense contingency table of one (variable, parent set).
  * Cell index = sum_p code_p base_p + code_v q, parents in ascending variable
  * order, the first with base 1, q = prod r_p.  *ncells = q r_v;
@@ -632,7 +676,9 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * the calling thread, perf_event_open; -1 where the host does not grant
  * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
  * counted on each path), "disc_pruned" (sets its prune pass removed, option
- * "disc_prune"), "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
+ * "disc_prune"), "fnml_table_bytes" (the ULG_SCORE_FNML regret table of the
+ * loaded data; 0 until an fNML call builds it and after every load),
+ * "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
  * ulg_disc_mmpc performed / left out by its reliability rule),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
  * "lds_image_bytes" (bytes of the last scoring call's launch images),

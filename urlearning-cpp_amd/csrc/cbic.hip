@@ -2993,6 +2993,7 @@ int ulg_cbic_load(ulg_ctx *c, const double *data, int64_t N, int n, double lambd
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     c->loaded = true;
+    fnml_drop(c);  // the discrete data is no longer the context's
     return ULG_OK;
 }
 

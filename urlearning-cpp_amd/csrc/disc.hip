@@ -23,14 +23,19 @@
 // the float it is rounded to once -- does not depend on the path, the hash
 // placement or the scheduling.
 //
-// The reduction is a compile-time policy (BicReduce, BdeuReduce below) of
+// The reduction is a compile-time policy (BicReduce, BdeuReduce, FnmlReduce below) of
 // decode_item, sparse_count, item_value and the two scoring kernels: what
 // thread 0 prepares per item, the term of a cell, the term of a parent
 // configuration and the float made of the integer sum.  BDeu (ULG_SCORE_BDEU,
 // csrc/disc_bdeu.h) replaces BDeuScoringFunction::calculateScore and calculate
 // (bdeu_scoring_function.cpp:21-35, 69-79, 117-166) with the same counting and
 // its own terms [lgamma(a_jk + n_jk) - lgamma(a_jk)] and
-// [lgamma(a_j) - lgamma(a_j + n_j)].
+// [lgamma(a_j) - lgamma(a_j + n_j)].  fNML (ULG_SCORE_FNML, csrc/disc_fnml.h)
+// replaces fNMLScoringFunction::calculateScore and its regret table
+// (fnml_scoring_function.cpp:17-74, fnml_scoring_function.h:300-340): BIC's
+// n ln n terms, and per non-empty parent configuration the regret
+// ln C(r_v, n_j) read from a device table that fnml_regret_kernel fills once
+// per load.
 //
 // Option disc_prune adds the reference's prune() (score_calculator.cpp:
 // 137-197, disabled in its score_main.cpp:166-171) between the last layer and
@@ -41,6 +46,7 @@
 
 #include "disc_bdeu.h"  // BdeuItem, bdeu_cell_term, bdeu_cfg_term, bdeu_fix, bdeu_shift
 #include "disc_dev.h"  // DiscData, fix_nlogn, disc_ready, disc_data
+#include "disc_fnml.h"  // fnml_c2_table, fnml_c2_szpankowski, fnml_next_ratio, fnml_fix, fnml_shift, fnml_table_fits
 #include "disc_prune.h"  // for_each_subset_rank, kPruneTwoEps
 #include "ulg_internal.h"
 
@@ -73,6 +79,7 @@ struct Item {
     int col[ULG_MAX_PARENTS_GPU];
     uint64_t base[ULG_MAX_PARENTS_GPU];
     BdeuItem bdeu;             // BdeuReduce only
+    const long long *row;      // FnmlReduce only: the fixed regrets of arity rv, by n_j
 };
 
 // ---- the reductions ----------------------------------------------------------
@@ -107,6 +114,31 @@ struct BdeuReduce {
     }
     __device__ __forceinline__ float finish(const DiscData &, const Item &, long long sum) const {
         return (float)bdeu_unfix(sum, shift);
+    }
+};
+
+// arity -> row of the regret table (kFnmlNoRow: no loaded column has it)
+constexpr uint8_t kFnmlNoRow = 0xFF;
+struct FnmlRows {
+    uint8_t of[256];
+};
+
+struct FnmlReduce {
+    const long long *table;  // rows ascending by arity, stride entries each: fix(ln C(r, n)), n = 0 .. N
+    int64_t stride;          // N + 1
+    int shift;               // fnml_shift(N, rmax)
+    FnmlRows rows;
+    // it.rv >= 2 here (decode_item), and every loaded arity >= 2 has a row
+    __device__ __forceinline__ void prepare(Item &it) const { it.row = table + (int64_t)rows.of[it.rv] * stride; }
+    __device__ __forceinline__ long long cell(const DiscData &, const Item &, unsigned int c) const {
+        return fix_nlogn(c, shift);
+    }
+    // nj <= N: inside the row
+    __device__ __forceinline__ long long config(const DiscData &, const Item &it, unsigned int nj) const {
+        return nj ? -fix_nlogn(nj, shift) - it.row[nj] : 0;
+    }
+    __device__ __forceinline__ float finish(const DiscData &, const Item &, long long sum) const {
+        return (float)fnml_unfix(sum, shift);
     }
 };
 
@@ -264,6 +296,26 @@ __global__ void __launch_bounds__(kDiscBlock) disc_check_kernel(DiscData D, unsi
     for (int64_t i = (int64_t)blockIdx.x * kDiscBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kDiscBlock)
         bad |= D.codes[i] >= D.arity[(int)(i / D.N)];
     if (bad) atomicOr(word, kErrCode);
+}
+
+// ---- the regret table of fNML ----------------------------------------------------
+// One lane per n = 0 .. N: the ratio recurrence of disc_fnml.h from rho_2 =
+// C(2, n) (c2[n] for n <= kFnmlExact, Szpankowski's form above) up to arity
+// rmax, storing fix(ln C(k, n)) at every k that has a row.  Row `of[k]` is
+// N + 1 contiguous entries, so the lanes of a wave store side by side.
+__global__ void __launch_bounds__(kDiscBlock)
+fnml_regret_kernel(const double *c2, int64_t N, int rmax, int shift, FnmlRows rows, long long *table) {
+    const int64_t n = (int64_t)blockIdx.x * kDiscBlock + threadIdx.x;
+    if (n > N) return;
+    const int64_t stride = N + 1;
+    double rho = n <= kFnmlExact ? c2[n] : fnml_c2_szpankowski((double)n);
+    double lc = log(rho);  // n = 0: C(k, 0) = 1 for every k, every ratio is 1
+    if (rows.of[2] != kFnmlNoRow) table[(int64_t)rows.of[2] * stride + n] = fnml_fix(lc, shift);
+    for (int k = 3; k <= rmax; ++k) {
+        rho = fnml_next_ratio(rho, (double)n, k);
+        lc += log(rho);
+        if (rows.of[k] != kFnmlNoRow) table[(int64_t)rows.of[k] * stride + n] = fnml_fix(lc, shift);
+    }
 }
 
 // ---- one layer ---------------------------------------------------------------
@@ -513,9 +565,61 @@ int disc_work(ulg_ctx *c, uint64_t max_cells, uint64_t items, DiscWork &W, size_
     return ULG_OK;
 }
 
-bool kind_ok(int kind) { return kind == ULG_SCORE_BIC || kind == ULG_SCORE_BDEU; }
+bool kind_ok(int kind) { return kind == ULG_SCORE_BIC || kind == ULG_SCORE_BDEU || kind == ULG_SCORE_FNML; }
 
 BdeuReduce bdeu_reduce(const ulg_ctx *c) { return BdeuReduce{c->disc_ess, bdeu_shift(c->N, c->disc_ess)}; }
+
+// The rows of the loaded columns: one per distinct arity >= 2, ascending.
+int fnml_rows(const ulg_ctx *c, FnmlRows &R, int &rmax) {
+    std::memset(R.of, kFnmlNoRow, sizeof R.of);
+    bool has[256] = {};
+    for (int a : c->disc_arity) has[a] = true;
+    int rows = 0;
+    rmax = 1;
+    for (int a = 2; a < 256; ++a)
+        if (has[a]) {
+            R.of[a] = (uint8_t)rows++;
+            rmax = a;
+        }
+    return rows;
+}
+
+// The regret table of the loaded data, built at the first fNML call after a
+// ulg_disc_load and kept until the next load of either kind (fnml_drop).
+int fnml_ensure_table(ulg_ctx *c, const char *who) {
+    if (c->fnml_built) return ULG_OK;
+    FnmlRows R;
+    int rmax = 1;
+    const int rows = fnml_rows(c, R, rmax);
+    if (!fnml_table_fits(rows, c->N))
+        return set_err(c, ULG_ERR_UNSUPPORTED, std::string(who) + ": the fNML regret table would hold more than 2^28 entries");
+    const size_t entries = (size_t)rows * (size_t)(c->N + 1);
+    if (rows) {
+        const std::vector<double> &c2 = fnml_c2_table();
+        int rc;
+        if ((rc = ensure(c, c->d_fnml_c2, c2.size())) || (rc = ensure(c, c->d_fnml, entries))) return rc;
+        // a static source: it outlives the copy
+        ULG_HIP(c, hipMemcpyAsync(c->d_fnml_c2.p, c2.data(), c2.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        prof_begin(c, "fnml_regret");
+        fnml_regret_kernel<<<(unsigned)((c->N + 1 + kDiscBlock - 1) / kDiscBlock), kDiscBlock, 0, c->stream>>>(
+            c->d_fnml_c2.p, c->N, rmax, fnml_shift(c->N, rmax), R, c->d_fnml.p);
+        prof_end(c);
+        ULG_HIP(c, hipGetLastError());
+    }
+    c->fnml_built = true;
+    c->fnml_bytes = (int64_t)(entries * sizeof(long long));
+    return ULG_OK;
+}
+
+FnmlReduce fnml_reduce(const ulg_ctx *c) {
+    FnmlReduce red{};
+    int rmax = 1;
+    (void)fnml_rows(c, red.rows, rmax);
+    red.table = c->d_fnml.p;
+    red.stride = c->N + 1;
+    red.shift = fnml_shift(c->N, rmax);
+    return red;
+}
 
 }  // namespace
 
@@ -532,6 +636,7 @@ int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int 
     int rc;
     if ((rc = ensure(c, c->d_codes, (size_t)(N * n))) || (rc = ensure(c, c->d_disc_word, kDiscWords))) return rc;
     c->disc_loaded = false;  // the previous codes are gone
+    fnml_drop(c);            // ... and the regret table made for them
     ULG_HIP(c, hipMemcpyAsync(c->d_codes.p, codes, (size_t)(N * n), hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, kDiscWords * sizeof(unsigned long long), c->stream));
     DiscData D{};
@@ -572,7 +677,7 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     if (!c) return ULG_ERR_ARG;
     if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score: call ulg_disc_load first");
-    if (!kind_ok(kind)) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC or ULG_SCORE_BDEU");
+    if (!kind_ok(kind)) return set_err(c, ULG_ERR_ARG, "ulg_disc_score: kind must be ULG_SCORE_BIC, ULG_SCORE_BDEU or ULG_SCORE_FNML");
     ScoreLists &ls = c->lists;
     const ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents);
     if (st != ScoreLists::kOk && st != ScoreLists::kTooWide) return lists_error(c, "ulg_disc_score", st);
@@ -612,6 +717,8 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     ULG_HIP(c, hipSetDevice(c->device));
     const int64_t nb = (int64_t)((total_slots + kScanPerBlock - 1) / kScanPerBlock);
     int rc;
+    const bool bdeu = kind == ULG_SCORE_BDEU, fnml = kind == ULG_SCORE_FNML;
+    if (fnml && (rc = fnml_ensure_table(c, "ulg_disc_score"))) return rc;
     // the slot table and the block counts live in buffers of this scorer; the
     // context's lists are replaced only once every layer has been launched
     if ((rc = ensure(c, c->d_disc_meta, meta.size())) || (rc = ensure(c, c->d_disc_cand, cand.size())) ||
@@ -624,8 +731,9 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     unsigned grid_cap = 1;
     if ((rc = disc_work(c, max_cells, total_slots, W, lds, grid_cap))) return rc;
     // each instantiation is a kernel of its own, with its own attribute
-    const bool bdeu = kind == ULG_SCORE_BDEU;
-    const void *layer_fn = bdeu ? (const void *)disc_layer_kernel<BdeuReduce> : (const void *)disc_layer_kernel<BicReduce>;
+    const void *layer_fn = bdeu   ? (const void *)disc_layer_kernel<BdeuReduce>
+                           : fnml ? (const void *)disc_layer_kernel<FnmlReduce>
+                                  : (const void *)disc_layer_kernel<BicReduce>;
     ULG_HIP(c, hipFuncSetAttribute(layer_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
@@ -659,6 +767,8 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             const unsigned grid = (unsigned)std::min<uint64_t>(items, grid_cap);
             if (bdeu)
                 disc_layer_kernel<BdeuReduce><<<grid, kDiscBlock, lds, c->stream>>>(D, W, A, bdeu_reduce(c));
+            else if (fnml)
+                disc_layer_kernel<FnmlReduce><<<grid, kDiscBlock, lds, c->stream>>>(D, W, A, fnml_reduce(c));
             else
                 disc_layer_kernel<BicReduce><<<grid, kDiscBlock, lds, c->stream>>>(D, W, A, BicReduce{});
             prof_end(c);
@@ -756,8 +866,11 @@ static int disc_sets_launch(ulg_ctx *c, const char *what, int kind, int64_t coun
     size_t lds = 0;
     unsigned grid = 1;
     if ((rc = disc_work(c, max_cells, (uint64_t)count, W, lds, grid))) return rc;
-    const bool bdeu = kind == ULG_SCORE_BDEU;
-    const void *sets_fn = bdeu ? (const void *)disc_sets_kernel<BdeuReduce> : (const void *)disc_sets_kernel<BicReduce>;
+    const bool bdeu = kind == ULG_SCORE_BDEU, fnml = kind == ULG_SCORE_FNML;
+    if (fnml && (rc = fnml_ensure_table(c, what))) return rc;
+    const void *sets_fn = bdeu   ? (const void *)disc_sets_kernel<BdeuReduce>
+                          : fnml ? (const void *)disc_sets_kernel<FnmlReduce>
+                                 : (const void *)disc_sets_kernel<BicReduce>;
     ULG_HIP(c, hipFuncSetAttribute(sets_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ULG_HIP(c, hipMemcpyAsync(c->d_sets_in.p, pairs.data(), (size_t)count * 16, hipMemcpyHostToDevice, c->stream));
     prof_begin(c, "disc_sets");
@@ -765,6 +878,9 @@ static int disc_sets_launch(ulg_ctx *c, const char *what, int kind, int64_t coun
     if (bdeu)
         disc_sets_kernel<BdeuReduce><<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count, cons,
                                                                            out_dev, counts_dev, bdeu_reduce(c));
+    else if (fnml)
+        disc_sets_kernel<FnmlReduce><<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count, cons,
+                                                                           out_dev, counts_dev, fnml_reduce(c));
     else
         disc_sets_kernel<BicReduce><<<grid, kDiscBlock, lds, c->stream>>>(disc_data(c), W, c->d_sets_in.p, count, cons,
                                                                           out_dev, counts_dev, BicReduce{});
@@ -781,12 +897,37 @@ int ulg_disc_score_sets(ulg_ctx *c, int kind, int64_t count, const int *vars, co
     if (int rc0 = finish_pending(c)) return rc0;
     if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_score_sets: call ulg_disc_load first");
     if (!kind_ok(kind))
-        return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC or ULG_SCORE_BDEU");
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_score_sets: kind must be ULG_SCORE_BIC, ULG_SCORE_BDEU or ULG_SCORE_FNML");
     if (count == 0) return ULG_OK;
     int rc;
     if ((rc = ensure(c, c->qbuf_out, (size_t)count))) return rc;
     if ((rc = disc_sets_launch(c, "ulg_disc_score_sets", kind, count, vars, parents, c->qbuf_out.p, nullptr))) return rc;
     ULG_HIP(c, hipMemcpy(scores, c->qbuf_out.p, (size_t)count * 4, hipMemcpyDeviceToHost));
+    return ULG_OK;
+}
+
+int ulg_disc_regret(ulg_ctx *c, int arity, int64_t first, int64_t count, double *out) {
+    if (!c || count < 0 || (count > 0 && !out)) return ULG_ERR_ARG;
+    if (int rc0 = finish_pending(c)) return rc0;
+    if (!disc_ready(c)) return set_err(c, ULG_ERR_STATE, "ulg_disc_regret: call ulg_disc_load first");
+    if (arity < 1 || arity > 255 || std::find(c->disc_arity.begin(), c->disc_arity.end(), arity) == c->disc_arity.end())
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_regret: no loaded column has this arity");
+    if (first < 0 || first > c->N || count > c->N + 1 - first)
+        return set_err(c, ULG_ERR_ARG, "ulg_disc_regret: the range leaves 0 .. N");
+    ULG_HIP(c, hipSetDevice(c->device));
+    if (int rc = fnml_ensure_table(c, "ulg_disc_regret")) return rc;
+    if (count == 0) return ULG_OK;
+    if (arity == 1) {  // ln C(1, n) = 0: no row
+        std::fill(out, out + count, 0.0);
+        return ULG_OK;
+    }
+    const FnmlReduce red = fnml_reduce(c);
+    std::vector<long long> fixed((size_t)count);
+    ULG_HIP(c, hipMemcpyAsync(fixed.data(), red.table + (int64_t)red.rows.of[arity] * red.stride + first,
+                              (size_t)count * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    for (int64_t i = 0; i < count; ++i) out[i] = fnml_unfix(fixed[(size_t)i], red.shift);
     return ULG_OK;
 }
 

@@ -270,6 +270,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = c->disc_pruned;
         return ULG_OK;
     }
+    // the fNML regret table of the loaded data (0: not built since the last load)
+    if (std::strcmp(name, "fnml_table_bytes") == 0) {
+        *value = c->fnml_bytes;
+        return ULG_OK;
+    }
     // the last ulg_disc_mmpc: G^2 tests performed / left out by the reliability rule
     if (std::strcmp(name, "disc_mmpc_tests") == 0 || std::strcmp(name, "disc_mmpc_skipped") == 0) {
         *value = c->disc_mmpc_stat[name[10] == 's' ? 1 : 0];

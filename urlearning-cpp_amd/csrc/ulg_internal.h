@@ -175,6 +175,14 @@ struct ulg_ctx : ulg::CtxStreams {
     std::set<std::string> prof_only;  // ulg_profile_select: time only these kernels
     std::mutex mu;  // err / pending: the wide scoring layers use one host thread per stream group
     std::map<std::string, std::vector<double>> prof_ms;
+
+    // ---- fNML (ULG_SCORE_FNML, disc.hip) ----
+    // The regret table of the loaded discrete data, built by the first fNML
+    // call after ulg_disc_load, dropped by every load (fnml_drop).
+    ulg::DevBuf<long long> d_fnml;                // per distinct arity >= 2, ascending: fix(ln C(r, n)), n = 0 .. N
+    ulg::DevBuf<double> d_fnml_c2;                // C(2, n), n = 0 .. 1000, from the host
+    bool fnml_built = false;
+    int64_t fnml_bytes = 0;                       // ulg_get_info("fnml_table_bytes")
 };
 
 namespace ulg {
@@ -203,6 +211,13 @@ void pss_delete(ulg_ctx *c);   // delete the context's PssState (pss.hip, where 
 const std::vector<uint32_t> &host_binom();
 // C(a, b) for a, b < 64 (saturating at 2^64 - 1), [a * 64 + b]
 const std::vector<uint64_t> &host_binom64();
+
+// A load of either kind: the regret table of the previous records goes.
+inline void fnml_drop(ulg_ctx *c) {
+    c->d_fnml.reset();
+    c->fnml_built = false;
+    c->fnml_bytes = 0;
+}
 
 // An async scoring call's launches still own the buffers and the lists: every
 // entry point that reads or replaces them collects that call first.

@@ -5,6 +5,7 @@
 //
 //   score <in.csv> <out.pss> [-f BIC] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> --bdeu [-e ESS] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
+//   score <in.csv> <out.pss> --fnml [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //
 // -f BIC (the default, as in the reference) is the discrete score: the tokens
@@ -16,12 +17,15 @@
 // size -e (default 1, 1e-6 .. 1e6), "META score_type = bdeu", and no parent
 // limit besides -p, since the reference applies log(2N / log N) to "bic" only
 // (score_main.cpp:300-304) -- without -p every subset of the candidates is
-// scored.  fNML is not built; nor is --enableDeCamposPruning with a discrete
-// score (experimental in the reference).  Options that only matter for the
+// scored.  --fnml is the discrete fNML score (the reference's -f fNML; -f fNML
+// itself keeps being refused): same reader, no parameter, "META score_type =
+// fnml", no parent limit besides -p either; it does not go with --bdeu or
+// -f cBIC.  --enableDeCamposPruning is not built for a discrete score
+// (experimental in the reference).  Options that only matter for the
 // reference's AD-tree or its other paths (-m, -w, -a, -o) are accepted; -e
 // feeds the "META ess" header line as in score_main.cpp:388 whatever the score.
 //
-// --prune (-f BIC only) applies the reference's end-of-scoring prune()
+// --prune (-f BIC, --bdeu and --fnml) applies the reference's end-of-scoring prune()
 // (score_calculator.cpp:137-197; its call is commented out in
 // score_main.cpp:166-171 because it "might not work with continuous case") on
 // the GPU: a parent set goes when a kept proper subset scores at least as well
@@ -58,7 +62,8 @@ int main(int argc, char **argv) {
             {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171; --prune runs it for -f BIC)."},
             {"", "prune", false, "", "Drop every parent set that a kept proper subset dominates (the reference's prune(); -f BIC only)."},
             {"", "bdeu", false, "", "Score with BDeu (the reference's -f BDeu) and equivalent sample size -e. There is no BIC parent limit: without -p every subset of the candidates is scored."},
-            {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC and --bdeu."},
+            {"", "fnml", false, "", "Score with fNML (the reference's -f fNML). It has no parameter and no BIC parent limit: without -p every subset of the candidates is scored."},
+            {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC, --bdeu and --fnml."},
             {"", "device", true, "0", "HIP device to use."},
             {"h", "help", false, "", "Show this help message."},
         },
@@ -91,15 +96,26 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "score: --bdeu needs 1e-6 <= -e <= 1e6 (got '%s')\n", args.get("ess").c_str());
         return 2;
     }
+    const bool fnml = args.has("fnml");
+    if (fnml && bdeu) {
+        std::fprintf(stderr, "score: --fnml and --bdeu are two scores; give one of them\n");
+        return 2;
+    }
+    if (fnml && sf != "bic") {
+        std::fprintf(stderr, "score: --fnml is a discrete score of its own; it does not go with -f %s\n",
+                     args.get("function").c_str());
+        return 2;
+    }
     if (bdeu) sf = "bdeu";
-    const bool discrete = sf == "bic" || bdeu;
+    if (fnml) sf = "fnml";
+    const bool discrete = sf == "bic" || bdeu || fnml;
     if (discrete && args.has("enableDeCamposPruning")) {
-        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC or --bdeu (it is a no-op for -f cBIC)\n");
+        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC, --bdeu or --fnml (it is a no-op for -f cBIC)\n");
         return 2;
     }
     const bool prune = args.has("prune");
     if (prune && !discrete) {
-        std::fprintf(stderr, "score: --prune is for -f BIC and --bdeu: the store rule of -f cBIC already tests dominance, and the "
+        std::fprintf(stderr, "score: --prune is for -f BIC, --bdeu and --fnml: the store rule of -f cBIC already tests dominance, and the "
                              "reference disabled prune() for the continuous case\n");
         return 2;
     }
@@ -144,11 +160,11 @@ int main(int argc, char **argv) {
     if (discrete) {
         // score_main.cpp:300-304; the reference divides by log 1 at N = 1
         if (N < 2) {
-            std::fprintf(stderr, "score: %s needs at least 2 records ('%s' has %lld)\n", bdeu ? "--bdeu" : "-f BIC",
+            std::fprintf(stderr, "score: %s needs at least 2 records ('%s' has %lld)\n", bdeu ? "--bdeu" : fnml ? "--fnml" : "-f BIC",
                          input.c_str(), (long long)N);
             return 2;
         }
-        if (!bdeu) {
+        if (!bdeu && !fnml) {
             const int lim = (int)std::log(2 * (double)N / std::log((double)N));
             if (lim < maxp) maxp = lim;
         }
@@ -200,7 +216,7 @@ int main(int argc, char **argv) {
     if (rc == ULG_OK && prune) rc = ulg_set_option(ctx, "disc_prune", 1);
     if (rc == ULG_OK && bdeu) rc = ulg_disc_set_ess(ctx, ess);
     if (rc == ULG_OK)
-        rc = discrete ? ulg_disc_score(ctx, bdeu ? ULG_SCORE_BDEU : ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
+        rc = discrete ? ulg_disc_score(ctx, bdeu ? ULG_SCORE_BDEU : fnml ? ULG_SCORE_FNML : ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
                       : ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
     int64_t oot = 0, done_layer = 0, pruned = 0;
     if (rc == ULG_OK && prune) {

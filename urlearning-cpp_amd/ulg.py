@@ -50,6 +50,8 @@ def lib():
         L.ulg_disc_score_sets.argtypes = [P, I, I64, P, P, P]
         L.ulg_disc_set_ess.argtypes = [P, D]
         L.ulg_disc_counts.argtypes = [P, I, C.c_uint64, P, I64, C.POINTER(I64)]
+        if hasattr(L, "ulg_disc_regret"):  # ULG_LIB may name a build from before fNML (A/B runs of BIC and BDeu)
+            L.ulg_disc_regret.argtypes = [P, I, I64, I64, P]
         L.ulg_chi2_log_sf.argtypes = [D, D]
         L.ulg_chi2_log_sf.restype = D
         L.ulg_disc_g2.argtypes = [P, I64, P, P, P, P, P, P]
@@ -246,9 +248,10 @@ class Context:
     def clear_constraints(self):
         self._check(lib().ulg_cbic_set_constraints(self._h, 0, None, None, None), "ulg_cbic_set_constraints")
 
-    # ---- discrete BIC and BDeu ----------------------------------------------
+    # ---- discrete BIC, BDeu and fNML ----------------------------------------
     SCORE_BIC = 1
     SCORE_BDEU = 3
+    SCORE_FNML = 5
 
     def set_ess(self, ess: float):
         """ulg_disc_set_ess: the equivalent sample size of SCORE_BDEU (sticky, default 1.0,
@@ -274,7 +277,7 @@ class Context:
 
     def score_discrete(self, variables, candidates, max_parents: int, kind: int = SCORE_BIC, prune=None, ess=None):
         """ulg_disc_score -> (total_stored, total_scored); fetch() reads the lists.
-        kind: SCORE_BIC or SCORE_BDEU.
+        kind: SCORE_BIC, SCORE_BDEU or SCORE_FNML.
         prune: True / False sets option "disc_prune" (sticky) before the call -- the
         reference's prune(): a set goes when a kept proper subset scores at least as
         well; total_stored then counts the kept sets and info("disc_pruned") the
@@ -294,7 +297,7 @@ class Context:
         return st.value, sc.value
 
     def score_sets_discrete(self, variables, parents, kind: int = SCORE_BIC, ess=None) -> np.ndarray:
-        """calculateScore's value (BIC or BDeu, by kind) per (variable, parent mask) pair
+        """calculateScore's value (BIC, BDeu or fNML, by kind) per (variable, parent mask) pair
         (ulg_disc_score_sets).  ess: as in score_discrete."""
         if ess is not None:
             self.set_ess(ess)
@@ -306,6 +309,13 @@ class Context:
         self._check(lib().ulg_disc_score_sets(self._h, int(kind), len(v), _ptr(v), _ptr(p), _ptr(out)),
                     "ulg_disc_score_sets")
         return out[:len(v)]
+
+    def regret(self, arity: int, first: int, count: int) -> np.ndarray:
+        """ulg_disc_regret: ln C(arity, first .. first + count - 1) as SCORE_FNML uses it
+        (the device table's entries; the table is built if need be)."""
+        out = np.empty(max(int(count), 1), dtype=np.float64)
+        self._check(lib().ulg_disc_regret(self._h, int(arity), int(first), int(count), _ptr(out)), "ulg_disc_regret")
+        return out[:max(int(count), 0)]
 
     def discrete_counts(self, variable: int, parents: int, cap=None) -> np.ndarray:
         """ulg_disc_counts: the dense contingency table of (variable, parents),
@@ -564,7 +574,8 @@ class Context:
         """ulg_get_info: "out_of_time", "highest_completed_layer", "score_error_word",
         "exact_cycles", "exact_instructions", "exact_cache_misses", "disc_mmpc_tests",
         "disc_mmpc_skipped", "disc_pruned" (sets the last score_discrete's prune pass
-        removed; 0 with option "disc_prune" off)."""
+        removed; 0 with option "disc_prune" off), "fnml_table_bytes" (the SCORE_FNML
+        regret table of the loaded data; 0 while there is none)."""
         v = C.c_int64()
         self._check(lib().ulg_get_info(self._h, name.encode(), C.byref(v)), "ulg_get_info")
         return v.value

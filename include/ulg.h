@@ -96,7 +96,8 @@ const char *ulg_version(void);
 /* data_colmajor: N x n doubles, column-major (column j = variable j), as
  * Armadillo holds raw_data.  n <= 63.  Normalises each column to zero mean
  * and unit sample variance (N-1) and builds the FP64 Gram matrix Z'Z on the
- * device (MFMA f64). */
+ * device (MFMA f64).  A pending ulg_cbic_score_async call is collected
+ * first (its launches read the Gram matrix this call replaces). */
 int ulg_cbic_load(ulg_ctx *ctx, const double *data_colmajor, int64_t N, int n,
                   double lambda);
 /* Copy the device Gram matrix Z'Z (n x n, row-major) to host. */
@@ -684,6 +685,9 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * "lds_image_bytes" (bytes of the last scoring call's launch images),
  * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the
  * narrow form, option "score_narrow"),
+ * "score_graph_captures" (scoring calls of the context that captured a launch
+ * graph anew, option "score_graph"; a call that replays the held graph does
+ * not count),
  * "score_error_word" (the last scoring call's device error word: 0,
  * or bit 0 a wide walk over its cap, bit 1 a walk-queue segment overflow,
  * bit 2 a walk entry naming a slot past the call's table -- any nonzero

@@ -148,6 +148,12 @@ typedef struct ora_cache ora_cache;
 ora_cache *ora_cache_create(const ora_varset *sets, const float *scores, int64_t count);
 void ora_cache_free(ora_cache *c);
 int ora_decide(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value);
+/* The same decision, leaving the recursion at the first visited key >= -ts
+ * (best is a running maximum and the rule is best >= -ts, so nothing visited
+ * later changes it).  The literal form visits every absent subset of a
+ * dominated set: 2^|P| nodes on inputs whose dominated sets have few present
+ * subsets.  tests/test_wide_shapes.py holds the two forms to each other. */
+int ora_decide_stop(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value);
 
 /* MMPC skeleton with Fisher-z tests (ora_mmpc.c; parity unpinned: the
  * reference takes the skeleton from outside, README.md:16).  rows[i] bit j =

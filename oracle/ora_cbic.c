@@ -363,7 +363,11 @@ static int cache_at(const omap *cache, vs_t K, int L, int p_has0, float *val) {
     return 1;
 }
 
-static float fbss_at(vs_t parents, const omap *cache, int L, int p_has0, const int *pv, int m, omap *checked) {
+/* stop: leave as soon as best >= stop (INFINITY: never, the literal recursion).
+ * The caller's rule is best >= -ts with best a running maximum, so the first
+ * visited key >= -ts settles it; what the literal recursion visits after that
+ * cannot lower best. */
+static float fbss_at(vs_t parents, const omap *cache, int L, int p_has0, const int *pv, int m, omap *checked, float stop) {
     float best = 0.0f;
     for (int idx = 0; idx < m; idx++) {
         const int u = pv[idx];
@@ -372,6 +376,7 @@ static float fbss_at(vs_t parents, const omap *cache, int L, int p_has0, const i
         float val;
         if (cache_at(cache, thin, L, p_has0, &val)) {
             if (val > best) best = val;
+            if (best >= stop) return best;
         } else {
             int npv[64];
             memset(npv, 0, sizeof(int) * (size_t)(m > 1 ? m - 1 : 1));
@@ -379,9 +384,10 @@ static float fbss_at(vs_t parents, const omap *cache, int L, int p_has0, const i
             for (int i = 0; i < m; i++) {
                 if (u == pv[i]) continue;
                 npv[j++] = pv[i];
-                float s = fbss_at(thin, cache, L, p_has0, npv, m - 1, checked);
+                float s = fbss_at(thin, cache, L, p_has0, npv, m - 1, checked, stop);
                 omap_put(checked, thin, 1);
                 if (s > best) best = s;
+                if (best >= stop) return best;
             }
         }
     }
@@ -400,7 +406,19 @@ void ora_cache_free(ora_cache *c) {
     free(c);
 }
 
+static int decide_at(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value,
+                     int early);
+
 int ora_decide(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value) {
+    return decide_at(ds, lambda, v, P, cache, value, 0);
+}
+
+int ora_decide_stop(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value) {
+    return decide_at(ds, lambda, v, P, cache, value, 1);
+}
+
+static int decide_at(const ora_dataset *ds, double lambda, int v, ora_varset P, const ora_cache *cache, float *value,
+                     int early) {
     int pv[64] = {0};
     const int np = parent_vec(ds->n, v, P, pv);
     ols_ws w = {0};
@@ -412,7 +430,8 @@ int ora_decide(const ora_dataset *ds, double lambda, int v, ora_varset P, const 
     omap checked;
     omap_init(&checked, 64);
     omap_put(&checked, 0ULL, 1);
-    const float best = fbss_at(P, (const omap *)cache, popc64(P), (int)(P & 1ULL), pv, np, &checked);
+    const float best = fbss_at(P, (const omap *)cache, popc64(P), (int)(P & 1ULL), pv, np, &checked,
+                               early ? -the_score : INFINITY);
     omap_free(&checked);
     return !((double)best + 0.0 >= (double)(-the_score));
 }

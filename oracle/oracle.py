@@ -78,6 +78,7 @@ def lib():
         L.ora_cache_create.restype = P
         L.ora_cache_free.argtypes = [P]
         L.ora_decide.argtypes = [P, D, I, U64, P, C.POINTER(F)]
+        L.ora_decide_stop.argtypes = [P, D, I, U64, P, C.POINTER(F)]
         L.ora_norm_quantile.argtypes = [D]
         L.ora_norm_quantile.restype = D
         L.ora_partial_z.argtypes = [P, I, D, I, I, P, I]
@@ -123,10 +124,12 @@ class Dataset:
     def cbic_raw(self, lam, v, parents):
         return lib().ora_cbic_raw(self.h, float(lam), int(v), int(parents))
 
-    def decide(self, lam, v, P, cache):
-        """ora_decide -> (stored, value) for one set against a cache handle."""
+    def decide(self, lam, v, P, cache, stop=False):
+        """ora_decide (stop: ora_decide_stop, which leaves the recursion at the
+        first key >= -ts) -> (stored, value) for one set against a cache handle."""
         val = C.c_float()
-        st = lib().ora_decide(self.h, float(lam), int(v), int(P), cache.h, C.byref(val))
+        fn = lib().ora_decide_stop if stop else lib().ora_decide
+        st = fn(self.h, float(lam), int(v), int(P), cache.h, C.byref(val))
         return bool(st), val.value
 
     def mmpc(self, alpha=0.05, max_cond=-1):

@@ -270,14 +270,24 @@ def test_subset_maxima_identical_c3_and_without_var0(ulg_ctx):
 
 def test_walk_forms_identical_c3(ulg_ctx, monkeypatch):
     """At C3 (n=25, N=10k, k=6, full skeleton: 4,751,275 sets) 2 and 8 sets
-    per lane store the default walk's lists bit for bit."""
+    per lane store the default walk's lists bit for bit.  ULG_SLICED_K is read
+    at launch time; its resolved values are part of the graph key, so each
+    call here captures anew (score_graph_captures) and does not replay the
+    first call's graph with the first call's sets per lane, and a repeat
+    under the same value replays."""
     n = 25
     X, _ = synth.gaussian_sem(n, 10000, 9200)
     ulg_ctx.load(X, 2.0)
     res = {}
     for k in ("4", "2", "8"):
         monkeypatch.setenv("ULG_SLICED_K", k)
+        before = ulg_ctx.info("score_graph_captures")
         res[k] = ulg_ctx.score_all(list(range(n)), [(1 << n) - 1] * n, 6)
+        assert ulg_ctx.info("score_graph_captures") == before + 1, k
+    again = ulg_ctx.score_all(list(range(n)), [(1 << n) - 1] * n, 6)
+    assert ulg_ctx.info("score_graph_captures") == before + 1
+    for a, b in zip(res["8"], again):
+        assert a.tobytes() == b.tobytes()
     for k in ("2", "8"):
         for a, b in zip(res["4"], res[k]):
             assert a.tobytes() == b.tobytes(), k

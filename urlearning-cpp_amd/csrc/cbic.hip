@@ -2944,6 +2944,9 @@ extern "C" {
 
 int ulg_cbic_load(ulg_ctx *c, const double *data, int64_t N, int n, double lambda) {
     if (!c || !data || N < 2 || n < 1 || n > kMaxVars) return set_err(c, ULG_ERR_ARG, "ulg_cbic_load: bad arguments");
+    // an async call in flight reads the Gram matrix this load replaces, and its
+    // pending flag would outlive `scored`: collect it first, as ulg_disc_load does
+    if (int rc0 = finish_pending(c)) return rc0;
     ULG_HIP(c, hipSetDevice(c->device));
     c->loaded = false;
     c->scored = false;
@@ -3133,7 +3136,10 @@ void graph_key(const ulg_ctx *c, const ScoreLists &ls, const CbicPlan &p, const 
                  (uint64_t)p.cons_words, ptr(p.cons_words ? c->d_cons.p : nullptr), dbits(c->pen),
                  (uint64_t)c->opt.score_unrank_lut, ptr(p.lut_any ? c->d_lut.p : nullptr),
                  ptr(p.lut_any ? c->d_lutoff.p : nullptr), (uint64_t)c->opt.score_lds_image,
-                 ptr(p.image_any ? c->d_image.p : nullptr), (uint64_t)c->opt.score_narrow});
+                 ptr(p.image_any ? c->d_image.p : nullptr), (uint64_t)c->opt.score_narrow,
+                 // the sets per lane of the sliced walks as ULG_SLICED_K resolves them now
+                 // (layers <= 5, layer 6): sliced_k reads the variable at launch time
+                 (uint64_t)sliced_k(5), (uint64_t)sliced_k(6, ~0ull, 0, (int)c->opt.walk_k6)});
     for (int i = 0; i < ls.nv; ++i) gkey.push_back((uint64_t)ls.vars[i]);
     for (int i = 0; i < ls.nv; ++i) gkey.push_back(candidates[i]);
     for (const std::string &nm : c->prof_only) gkey.push_back(std::hash<std::string>{}(nm));
@@ -3208,6 +3214,7 @@ int launch_call(const ScoreCall &k, const uint64_t *candidates) {
             return ULG_OK;
         }
         graph_reset(c);
+        ++c->graph_captures;
         ULG_HIP(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
         capture_guard.active = true;
     }

@@ -236,6 +236,12 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = (int64_t)c->last_err_word;
         return ULG_OK;
     }
+    // scoring calls of this context that captured a launch graph anew (a call
+    // whose graph key equals the held one replays it and does not count)
+    if (std::strcmp(name, "score_graph_captures") == 0) {
+        *value = c->graph_captures;
+        return ULG_OK;
+    }
     // bytes the process holds through DevBuf / PinnedBuf, every context's together
     if (std::strcmp(name, "device_bytes_live") == 0) {
         *value = g_device_bytes.load();

@@ -128,6 +128,7 @@ struct ulg_ctx : ulg::CtxStreams {
     ulg::PinnedBuf<unsigned long long> async_pinned;  // [stored count, error word] of the last call
     unsigned long long last_err_word = 0;        // the last scoring call's error word (kErr* bits)
     bool async_pending = false;
+    int64_t graph_captures = 0;                  // scoring calls that captured a new graph (ulg_get_info)
     ulg::DevBuf<float> qbuf_in, qbuf_out;
     ulg::DevBuf<uint64_t> d_sets_in;              // ulg_cbic_score_sets: (variable, parent mask) pairs
 

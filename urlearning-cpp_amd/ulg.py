@@ -575,7 +575,8 @@ class Context:
         "exact_cycles", "exact_instructions", "exact_cache_misses", "disc_mmpc_tests",
         "disc_mmpc_skipped", "disc_pruned" (sets the last score_discrete's prune pass
         removed; 0 with option "disc_prune" off), "fnml_table_bytes" (the SCORE_FNML
-        regret table of the loaded data; 0 while there is none)."""
+        regret table of the loaded data; 0 while there is none), "score_graph_captures"
+        (scoring calls of this context that captured their launch graph anew)."""
         v = C.c_int64()
         self._check(lib().ulg_get_info(self._h, name.encode(), C.byref(v)), "ulg_get_info")
         return v.value

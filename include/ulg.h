@@ -340,6 +340,68 @@ int ulg_disc_regret(ulg_ctx *ctx, int arity, int64_t first, int64_t count, doubl
  * ULG_ERR_ARG if cap is smaller. */
 int ulg_disc_counts(ulg_ctx *ctx, int var, uint64_t parents, int32_t *counts, int64_t cap, int64_t *ncells);
 
+/* ---- BGe scoring of the continuous data (no reference counterpart) ---- */
+/* The Bayesian Gaussian equivalent score (Geiger & Heckerman 2002; corrected
+ * form of Kuipers, Moffa & Heckerman 2014): the continuous counterpart of BDeu,
+ * a marginal likelihood instead of cBIC's penalty with its free lambda, and
+ * score-equivalent.  It reads what ulg_cbic_load holds -- columns normalised to
+ * zero mean and unit sample variance (N - 1), G = Z'Z on the device -- and
+ * ignores lambda.  Prior: mean 0 (the sample mean of the normalised data),
+ * alpha_mu > 0, alpha_w > n + 1, T = t I with
+ * t = alpha_mu (alpha_w - n - 1) / (alpha_mu + 1), R = G + t I.  For |P| = l
+ * and A_l = (N + alpha_w - n + l + 1) / 2:
+ *   s(v, P) = c_l - 1/2 ln det R[P,P] - A_l ln sigma
+ *   sigma   = R[v,v] - R[v,P] R[P,P]^-1 R[P,v]
+ *   c_l     = lgamma(A_l) - lgamma((alpha_w - n + l + 1) / 2) - (N / 2) ln pi
+ *             + 1/2 ln(alpha_mu / (N + alpha_mu)) + ((alpha_w - n + 2 l + 1) / 2) ln t
+ * sigma is the last pivot of the Cholesky factorisation of R[Q,Q], Q = P + {v}
+ * with v last, det R[P,P] the product of the pivots before it (1 for no
+ * parent).  Everything runs in FP64 and is rounded to float once; c_l and A_l
+ * are computed on the host once per call (csrc/bge.h).  One device function
+ * computes the value (csrc/bge_dev.h: parents in ascending variable order, t
+ * added to each diagonal entry as it is read, every multiply-add an fma), so a
+ * pair's value is the same bits from ulg_bge_score and ulg_bge_score_sets, in
+ * every call and for any grid.
+ * The store rule departs from score_calculator.cpp:59,111 (the empty set iff
+ * < 1, any other set iff < 0): BGe is a log density, positive as soon as the
+ * residual variance of normalised data falls below about 0.06 (duplicated or
+ * near-deterministic columns), so every finite value is stored, the empty set
+ * included, and there is no dominance test.  A set that touches a constant
+ * column (NaN in G) or whose pivot comes out <= 0 gives NaN and is never
+ * stored.  A set that violates ulg_cbic_set_constraints is not evaluated and
+ * never stored; ulg_bge_score_sets returns NaN for it.  Costs (-score) may
+ * therefore be negative; the "%f" round trip, the best-score tables and the
+ * searches take either sign.
+ *
+ * ulg_bge_set_prior: sticky, default (1, 0), kept across loads.  alpha_w = 0
+ * means n + alpha_mu + 1 at scoring time.  ULG_ERR_ARG (and the previous prior
+ * stays) outside 1e-3 <= alpha_mu <= 1e3, for a non-finite value, or for
+ * 0 != alpha_w <= n + 1 or alpha_w > n + 1e6 against the n loaded at the time
+ * (0 without data); the scoring calls check again against their n. */
+int ulg_bge_set_prior(ulg_ctx *ctx, double alpha_mu, double alpha_w);
+/* ulg_disc_score's arguments and counts: the lists replace the context's
+ * (ulg_cbic_fetch, ulg_pss_format, ulg_search_from_scores read them), ordered
+ * by (|set|, set value); max_parents < 1 or > n - 1 means n - 1; up to
+ * ULG_MAX_PARENTS_GPU parents (ULG_ERR_UNSUPPORTED above); time_limit_ms is
+ * checked after each complete layer ("out_of_time",
+ * "highest_completed_layer"); *total_scored counts every set of the completed
+ * layers, sum over the variables of C(m, <= k).  A refused call leaves the
+ * previous lists.  One launch per layer (bge_layer_kernel), one lane per set;
+ * layers of 1 .. ULG_UNROLLED_PARENTS_GPU parents run fully unrolled.
+ * Option "bge_prune" (0/1, default 0, sticky; only this call reads it): 1 runs
+ * ulg_disc_score's prune pass (disc_prune_kernel, unchanged) over the BGe slot
+ * table: a stored set goes iff a kept proper subset scores at least as well
+ * within 2 FLT_EPSILON.  ulg_get_info("bge_pruned") then gives the sets
+ * removed (0 with the option off).  ULG_ERR_STATE without continuous data (no
+ * load yet, or after ulg_disc_load). */
+int ulg_bge_score(ulg_ctx *ctx, const int *vars, int nv, const uint64_t *candidates, int max_parents,
+                  int64_t *total_stored, int64_t *total_scored);
+/* s(vars[i], parents[i]) for arbitrary pairs (the variable's own bit is
+ * ignored), without the store rule: NaN for a constant column, a pivot <= 0 or
+ * a violating set.  At most ULG_MAX_PARENTS_GPU parents per set.  The context's
+ * lists stay as they are. */
+int ulg_bge_score_sets(ulg_ctx *ctx, int64_t count, const int *vars, const uint64_t *parents, float *scores);
+
 /* ---- discrete skeleton: G^2 tests and MMPC (no reference counterpart) ---- */
 /* ln of the chi-square survival function: ln P(chi2_dof >= x), pure host FP64,
  * no context.  x <= 0 gives 0.  Computed in log space (the series of the lower
@@ -624,6 +686,7 @@ int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
  * give bit-identical values.
  * "disc_prune" (0/1, default 0): ulg_disc_score drops every set that a kept
  * proper subset dominates (the reference's prune(); see ulg_disc_score).
+ * "bge_prune" (0/1, default 0): the same pass for ulg_bge_score.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -677,7 +740,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * the calling thread, perf_event_open; -1 where the host does not grant
  * them), "disc_dense_sets" / "disc_sparse_sets" (sets of the last ulg_disc_score
  * counted on each path), "disc_pruned" (sets its prune pass removed, option
- * "disc_prune"), "fnml_table_bytes" (the ULG_SCORE_FNML regret table of the
+ * "disc_prune"), "bge_pruned" (likewise for the last ulg_bge_score, option
+ * "bge_prune"), "fnml_table_bytes" (the ULG_SCORE_FNML regret table of the
  * loaded data; 0 until an fNML call builds it and after every load),
  * "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
  * ulg_disc_mmpc performed / left out by its reliability rule),

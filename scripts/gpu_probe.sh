@@ -29,6 +29,9 @@
 #               (default "6"), two alternating rounds -> exact_<mode>_<rep>.json
 #   disc_mmpc   scripts/disc_mmpc_profile.py (discrete MMPC, n = 30,
 #               N = 100k)                                     -> disc_mmpc.json
+#   bge         scripts/bge_profile.py (BGe at the C3 shape against cBIC and
+#               the generic ulg_bge_score_sets; RESOURCE_USAGE = the text of
+#               `make resource-usage`, optional)              -> bge.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -137,6 +140,10 @@ for step in ${STEPS:-suite smoke bench}; do
     disc_mmpc)
       timeout -k 10 300 python3 scripts/disc_mmpc_profile.py "$OUT/disc_mmpc.json" > "$OUT/disc_mmpc.log" 2>&1
       tail -n 1 "$OUT/disc_mmpc.log" | cut -c1-900 ;;
+    bge)
+      timeout -k 10 300 python3 scripts/bge_profile.py "$OUT/bge.json" \
+        ${RESOURCE_USAGE:+--resource-usage $RESOURCE_USAGE} > "$OUT/bge.log" 2>&1
+      tail -n 1 "$OUT/bge.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

@@ -48,6 +48,7 @@
 #include "disc_dev.h"  // DiscData, fix_nlogn, disc_ready, disc_data
 #include "disc_fnml.h"  // fnml_c2_table, fnml_c2_szpankowski, fnml_next_ratio, fnml_fix, fnml_shift, fnml_table_fits
 #include "disc_prune.h"  // for_each_subset_rank, kPruneTwoEps
+#include "slot_table.h"  // SlotTable, slot_table_begin / time_up / prune / compact
 #include "ulg_internal.h"
 
 using namespace ulg;
@@ -61,7 +62,7 @@ constexpr int kHashLdsSlots = 8192;                 // 8192 x 12 B = 96 KB of th
 constexpr int kScanPerThread = 8;
 constexpr int kScanPerBlock = kDiscBlock * kScanPerThread;
 constexpr unsigned long long kErrCode = 1ull;       // a value code >= its column's arity
-constexpr int kDiscWords = 5;                       // the call's words: [error word, dense sets, sparse sets, stored, pruned]
+constexpr int kDiscWords = kSlotWords;              // the call's words: [error word, dense sets, sparse sets, stored, pruned]
 
 struct DiscWork {
     unsigned long long *slab;  // sparse path in HBM: hslots keys, then hslots uint32 counts, per workgroup
@@ -623,6 +624,114 @@ FnmlReduce fnml_reduce(const ulg_ctx *c) {
 
 }  // namespace
 
+// ---- the score-agnostic steps (slot_table.h) -------------------------------------
+namespace ulg {
+
+void SlotTable::build(const ScoreLists &ls) {
+    nv = ls.nv;
+    S = ls.S;
+    total_slots = ls.total_slots;
+    nb = (int64_t)((total_slots + kScanPerBlock - 1) / kScanPerBlock);
+    vm.assign((size_t)nv * 2, 0);
+    for (int i = 0; i < nv; ++i) {
+        vm[2 * i] = ls.vars[i];
+        vm[2 * i + 1] = ls.mv[i];
+    }
+    // [toff: nv * S + 1][work: S x (nv + 1)]
+    meta.assign((size_t)nv * S + 1 + (size_t)S * (nv + 1), 0);
+    std::copy(ls.toff.begin(), ls.toff.end(), meta.begin());
+    uint64_t *work = meta.data() + (size_t)nv * S + 1;
+    for (int L = 0; L < S; ++L) {
+        uint64_t s = 0;
+        for (int i = 0; i < nv; ++i) {
+            work[(size_t)L * (nv + 1) + i] = s;
+            s += ls.slab_count(i, L);
+        }
+        work[(size_t)L * (nv + 1) + nv] = s;
+    }
+}
+
+int slot_table_begin(ulg_ctx *c, const ScoreLists &ls, const SlotTable &st) {
+    const std::vector<uint8_t> &cand = ls.cand;
+    const uint64_t total_slots = st.total_slots;
+    int rc;
+    // the slot table and the block counts live in buffers of the scorers; the
+    // context's lists are replaced only once every layer has been launched
+    if ((rc = ensure(c, c->d_disc_meta, st.meta.size())) || (rc = ensure(c, c->d_disc_cand, cand.size())) ||
+        (rc = ensure(c, c->d_disc_vm, st.vm.size())) || (rc = ensure(c, c->d_disc_table, total_slots)) ||
+        (rc = ensure(c, c->d_disc_sets, total_slots)) || (rc = ensure(c, c->d_disc_blk, (size_t)st.nb + 1)) ||
+        (rc = ensure(c, c->d_disc_word, kDiscWords)))
+        return rc;
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_meta.p, st.meta.data(), st.meta.size() * 8, hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemcpyAsync(c->d_disc_vm.p, st.vm.data(), st.vm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_table.p, 0xFF, total_slots * sizeof(float), c->stream));  // absent
+    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, kDiscWords * sizeof(unsigned long long), c->stream));
+    // pageable sources: the copies above must be done before `st` goes away
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    return ULG_OK;
+}
+
+int slot_table_time_up(ulg_ctx *c, std::chrono::steady_clock::time_point t_call, bool *up) {
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    *up = ms > (double)c->opt.time_limit_ms;
+    return ULG_OK;
+}
+
+int slot_table_prune(ulg_ctx *c, const SlotTable &st, int done_L) {
+    // the completed layers only: nothing above done_L was stored
+    int rc;
+    if ((rc = ensure(c, c->d_disc_best, st.total_slots))) return rc;
+    PruneArgs P{};
+    P.vm = c->d_disc_vm.p;
+    P.toff = c->d_disc_meta.p;
+    P.binom64 = c->d_binom64.p;
+    P.table = c->d_disc_table.p;
+    P.best = c->d_disc_best.p;
+    P.pruned = c->d_disc_word.p + 4;
+    P.nv = st.nv;
+    P.S = st.S;
+    for (int L = 0; L <= done_L; ++L) {
+        const uint64_t items = st.items(L);
+        if (!items) continue;
+        P.L = L;
+        P.work = c->d_disc_meta.p + st.work_at(L);
+        prof_begin(c, "disc_prune");
+        disc_prune_kernel<<<(unsigned)std::min<uint64_t>((items + kDiscBlock - 1) / kDiscBlock, 2048), kDiscBlock, 0,
+                            c->stream>>>(P);
+        prof_end(c);
+        ULG_HIP(c, hipGetLastError());
+    }
+    return ULG_OK;
+}
+
+int slot_table_compact(ulg_ctx *c, const SlotTable &st, unsigned long long (&word)[kSlotWords]) {
+    const uint64_t total_slots = st.total_slots;
+    const int64_t nb = st.nb;
+    const int nv = st.nv, S = st.S;
+    int rc;
+    if ((rc = ensure(c, c->out_sets, total_slots)) || (rc = ensure(c, c->out_scores, total_slots)) ||
+        (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
+        return rc;
+    prof_begin(c, "disc_compact");
+    disc_count_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, total_slots, c->d_disc_blk.p);
+    disc_scan_kernel<<<1, kDiscBlock, 0, c->stream>>>(c->d_disc_blk.p, nb, c->d_disc_word.p);
+    disc_write_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_sets.p, total_slots,
+                                                                 c->d_disc_blk.p, c->out_sets.p, c->out_scores.p);
+    disc_offsets_kernel<<<(nv + 1 + 63) / 64, 64, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_meta.p, nv, S,
+                                                                 c->d_disc_blk.p, c->out_offsets.p);
+    prof_end(c);
+    ULG_HIP(c, hipGetLastError());
+    for (unsigned long long &w : word) w = 0;
+    ULG_HIP(c, hipMemcpyAsync(word, c->d_disc_word.p, sizeof word, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ULG_OK;
+}
+
+}  // namespace ulg
+
 extern "C" {
 
 int ulg_disc_load(ulg_ctx *c, const uint8_t *codes, int64_t N, int n, const int *arity) {
@@ -681,14 +790,11 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     ScoreLists &ls = c->lists;
     const ScoreLists::Status st = ls.build(c->n, vars, nv, candidates, max_parents);
     if (st != ScoreLists::kOk && st != ScoreLists::kTooWide) return lists_error(c, "ulg_disc_score", st);
-    std::vector<int> vm((size_t)nv * 2, 0);
     uint64_t max_cells = 0;
     for (int i = 0; i < nv; ++i) {
         const int m = ls.mv[i];
         std::vector<int> ar(m);
         for (int j = 0; j < m; ++j) ar[j] = c->disc_arity[ls.cand[(size_t)i * 64 + j]];
-        vm[2 * i] = vars[i];
-        vm[2 * i + 1] = m;
         const int k = std::min(m, ls.max_parents);
         // the variable's largest table: its k candidates of largest arity
         std::sort(ar.begin(), ar.end(), std::greater<int>());
@@ -700,48 +806,22 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     }
     if (st != ScoreLists::kOk) return lists_error(c, "ulg_disc_score", st);
     const int kmax = ls.kmax, S = ls.S;
-    const uint64_t total_slots = ls.total_slots;
-    const std::vector<uint8_t> &cand = ls.cand;
-    // [toff: nv * S + 1][work: S x (nv + 1)]
-    std::vector<uint64_t> meta((size_t)nv * S + 1 + (size_t)S * (nv + 1), 0);
-    std::copy(ls.toff.begin(), ls.toff.end(), meta.begin());
-    uint64_t *work = meta.data() + (size_t)nv * S + 1;
-    for (int L = 0; L < S; ++L) {
-        uint64_t s = 0;
-        for (int i = 0; i < nv; ++i) {
-            work[(size_t)L * (nv + 1) + i] = s;
-            s += ls.slab_count(i, L);
-        }
-        work[(size_t)L * (nv + 1) + nv] = s;
-    }
+    SlotTable tb;
+    tb.build(ls);
     ULG_HIP(c, hipSetDevice(c->device));
-    const int64_t nb = (int64_t)((total_slots + kScanPerBlock - 1) / kScanPerBlock);
     int rc;
     const bool bdeu = kind == ULG_SCORE_BDEU, fnml = kind == ULG_SCORE_FNML;
     if (fnml && (rc = fnml_ensure_table(c, "ulg_disc_score"))) return rc;
-    // the slot table and the block counts live in buffers of this scorer; the
-    // context's lists are replaced only once every layer has been launched
-    if ((rc = ensure(c, c->d_disc_meta, meta.size())) || (rc = ensure(c, c->d_disc_cand, cand.size())) ||
-        (rc = ensure(c, c->d_disc_vm, vm.size())) || (rc = ensure(c, c->d_disc_table, total_slots)) ||
-        (rc = ensure(c, c->d_disc_sets, total_slots)) || (rc = ensure(c, c->d_disc_blk, (size_t)nb + 1)) ||
-        (rc = ensure(c, c->d_disc_word, kDiscWords)))
-        return rc;
+    if ((rc = slot_table_begin(c, ls, tb))) return rc;
     DiscWork W;
     size_t lds = 0;
     unsigned grid_cap = 1;
-    if ((rc = disc_work(c, max_cells, total_slots, W, lds, grid_cap))) return rc;
+    if ((rc = disc_work(c, max_cells, tb.total_slots, W, lds, grid_cap))) return rc;
     // each instantiation is a kernel of its own, with its own attribute
     const void *layer_fn = bdeu   ? (const void *)disc_layer_kernel<BdeuReduce>
                            : fnml ? (const void *)disc_layer_kernel<FnmlReduce>
                                   : (const void *)disc_layer_kernel<BicReduce>;
     ULG_HIP(c, hipFuncSetAttribute(layer_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ULG_HIP(c, hipMemcpyAsync(c->d_disc_meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream));
-    ULG_HIP(c, hipMemcpyAsync(c->d_disc_cand.p, cand.data(), cand.size(), hipMemcpyHostToDevice, c->stream));
-    ULG_HIP(c, hipMemcpyAsync(c->d_disc_vm.p, vm.data(), vm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    ULG_HIP(c, hipMemsetAsync(c->d_disc_table.p, 0xFF, total_slots * sizeof(float), c->stream));  // absent
-    ULG_HIP(c, hipMemsetAsync(c->d_disc_word.p, 0, kDiscWords * sizeof(unsigned long long), c->stream));
-    // pageable sources: the copies above must be done before `meta` goes away
-    ULG_HIP(c, hipStreamSynchronize(c->stream));
 
     const DiscData D = disc_data(c);
     LayerArgs A{};
@@ -759,10 +839,10 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
     c->out_of_time = 0;
     int done_L = kmax;
     for (int L = 0; L <= kmax; ++L) {
-        const uint64_t items = work[(size_t)L * (nv + 1) + nv];
+        const uint64_t items = tb.items(L);
         if (items) {
             A.L = L;
-            A.work = c->d_disc_meta.p + (size_t)nv * S + 1 + (size_t)L * (nv + 1);
+            A.work = c->d_disc_meta.p + tb.work_at(L);
             prof_begin(c, "disc_layer");
             const unsigned grid = (unsigned)std::min<uint64_t>(items, grid_cap);
             if (bdeu)
@@ -775,10 +855,9 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
             ULG_HIP(c, hipGetLastError());
         }
         if (c->opt.time_limit_ms > 0 && L < kmax) {
-            ULG_HIP(c, hipStreamSynchronize(c->stream));
-            const double ms =
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            if (ms > (double)c->opt.time_limit_ms) {
+            bool up = false;
+            if ((rc = slot_table_time_up(c, t_call, &up))) return rc;
+            if (up) {
                 done_L = L;
                 c->out_of_time = 1;
                 break;
@@ -786,46 +865,9 @@ int ulg_disc_score(ulg_ctx *c, int kind, const int *vars, int nv, const uint64_t
         }
     }
     c->completed_layer = done_L;
-    if (c->opt.disc_prune) {
-        // the completed layers only: nothing above done_L was stored
-        if ((rc = ensure(c, c->d_disc_best, total_slots))) return rc;
-        PruneArgs P{};
-        P.vm = c->d_disc_vm.p;
-        P.toff = c->d_disc_meta.p;
-        P.binom64 = c->d_binom64.p;
-        P.table = c->d_disc_table.p;
-        P.best = c->d_disc_best.p;
-        P.pruned = c->d_disc_word.p + 4;
-        P.nv = nv;
-        P.S = S;
-        for (int L = 0; L <= done_L; ++L) {
-            const uint64_t items = work[(size_t)L * (nv + 1) + nv];
-            if (!items) continue;
-            P.L = L;
-            P.work = c->d_disc_meta.p + (size_t)nv * S + 1 + (size_t)L * (nv + 1);
-            prof_begin(c, "disc_prune");
-            disc_prune_kernel<<<(unsigned)std::min<uint64_t>((items + kDiscBlock - 1) / kDiscBlock, 2048), kDiscBlock, 0,
-                                c->stream>>>(P);
-            prof_end(c);
-            ULG_HIP(c, hipGetLastError());
-        }
-    }
-    if ((rc = ensure(c, c->out_sets, total_slots)) || (rc = ensure(c, c->out_scores, total_slots)) ||
-        (rc = ensure(c, c->out_offsets, (size_t)nv + 1)))
-        return rc;
-    prof_begin(c, "disc_compact");
-    disc_count_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, total_slots, c->d_disc_blk.p);
-    disc_scan_kernel<<<1, kDiscBlock, 0, c->stream>>>(c->d_disc_blk.p, nb, c->d_disc_word.p);
-    disc_write_kernel<<<(unsigned)nb, kDiscBlock, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_sets.p, total_slots,
-                                                                 c->d_disc_blk.p, c->out_sets.p, c->out_scores.p);
-    disc_offsets_kernel<<<(nv + 1 + 63) / 64, 64, 0, c->stream>>>(c->d_disc_table.p, c->d_disc_meta.p, nv, S,
-                                                                 c->d_disc_blk.p, c->out_offsets.p);
-    prof_end(c);
-    ULG_HIP(c, hipGetLastError());
-    unsigned long long word[kDiscWords] = {0, 0, 0, 0, 0};
-    ULG_HIP(c, hipMemcpyAsync(word, c->d_disc_word.p, sizeof word, hipMemcpyDeviceToHost, c->stream));
-    ULG_HIP(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
+    if (c->opt.disc_prune && (rc = slot_table_prune(c, tb, done_L))) return rc;
+    unsigned long long word[kDiscWords];
+    if ((rc = slot_table_compact(c, tb, word))) return rc;
     c->last_err_word = 0;
     c->disc_path_sets[0] = (int64_t)word[1];
     c->disc_path_sets[1] = (int64_t)word[2];

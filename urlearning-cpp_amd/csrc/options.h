@@ -44,6 +44,8 @@ struct Options {
     // ---- discrete scorer ----
     int64_t disc_dense_cells = 16384;  // tables up to this many cells are counted in LDS
     int64_t disc_prune = 0;          // ulg_disc_score: drop dominated sets (the reference's prune())
+    // ---- BGe scorer ----
+    int64_t bge_prune = 0;           // ulg_bge_score: the same pass over the BGe slot table
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -85,6 +87,7 @@ constexpr OptionRow kOptionRows[] = {
     {"wide_prune", &Options::wide_prune, 0, 1, 0, {}, "0 or 1"},
     {"disc_dense_cells", &Options::disc_dense_cells, 1, 32768, 0, {}, "1..32768"},
     {"disc_prune", &Options::disc_prune, 0, 1, 0, {}, "0 or 1"},
+    {"bge_prune", &Options::bge_prune, 0, 1, 0, {}, "0 or 1"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -276,6 +276,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = c->disc_pruned;
         return ULG_OK;
     }
+    // the last ulg_bge_score: sets its prune pass removed (0 with bge_prune off)
+    if (std::strcmp(name, "bge_pruned") == 0) {
+        *value = c->bge_pruned;
+        return ULG_OK;
+    }
     // the fNML regret table of the loaded data (0: not built since the last load)
     if (std::strcmp(name, "fnml_table_bytes") == 0) {
         *value = c->fnml_bytes;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ulg.h"
+#include "bge.h"         // BgeConsts
 #include "dev_buf.h"     // DevBuf, PinnedBuf, ensure, upload, Mirror
 #include "options.h"     // Options
 #include "score_plan.h"  // kMaxVars, kMaxL, kWideMax, kBinomK, binom64, ScoreLists, CbicPlan
@@ -158,6 +159,11 @@ struct ulg_ctx : ulg::CtxStreams {
     int64_t disc_pruned = 0;                      // sets the last ulg_disc_score's prune pass dropped
     ulg::DevBuf<float> d_disc_best;               // ... per table slot: the best kept score among the set and its subsets
     ulg::DevBuf<int32_t> d_disc_counts;           // ulg_disc_counts' table
+    // ---- BGe (bge.hip): the continuous data's Bayesian score, over the slot table above ----
+    double bge_alpha_mu = 1.0, bge_alpha_w = 0.0; // ulg_bge_set_prior (sticky; alpha_w 0 = n + alpha_mu + 1)
+    ulg::BgeConsts bge_k;                         // the last call's t, c_l and A_l (the upload's source)
+    ulg::DevBuf<double> d_bge_tab;                // [64]: c_l, A_l
+    int64_t bge_pruned = 0;                       // sets the last ulg_bge_score's prune pass dropped
     // ---- discrete G^2 tests and MMPC (disc_mmpc.hip) ----
     ulg::DevBuf<uint64_t> d_g2_tests;             // per test: (x, t), conditioning mask
     ulg::DevBuf<unsigned long long> d_g2_out;     // per test: the fixed-point sum

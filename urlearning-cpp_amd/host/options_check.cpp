@@ -2,7 +2,7 @@
 // what ulg_set_option accepted, refused and defaulted to before the table
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
-// (score_narrow, added since, is recorded the same way).
+// (score_narrow and bge_prune, added since, are recorded the same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +66,7 @@ const std::vector<Want> kWant = {
     {"wide_prune", {0, 1}, 0, 0, 1, "0 or 1"},
     {"disc_dense_cells", {}, 1, 32768, 16384, "1..32768"},
     {"disc_prune", {0, 1}, 0, 0, 0, "0 or 1"},
+    {"bge_prune", {0, 1}, 0, 0, 0, "0 or 1"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -101,7 +102,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 27);
+    CHECK(kWant.size() == 28);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

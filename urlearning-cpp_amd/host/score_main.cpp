@@ -7,6 +7,7 @@
 //   score <in.csv> <out.pss> --bdeu [-e ESS] [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> --fnml [--prune] [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
 //   score <in.csv> <out.pss> -f cBIC --lambda L [-k skeleton] [-c constraints] [-p k] [-s] [-d ,]
+//   score <in.csv> <out.pss> --bge [--alpha-mu A] [--alpha-w W] [--prune] [-k skeleton] [-c constraints] [-p k] [-r s] [-s] [-d ,]
 //
 // -f BIC (the default, as in the reference) is the discrete score: the tokens
 // of each column are its values (load_discrete_csv), the parent limit is
@@ -32,6 +33,15 @@
 // (within 2 FLT_EPSILON).  The .pss then holds the kept sets only, stdout gains
 // "Size before pruning" / "Size after pruning" and the metrics line "pruned".
 // -f cBIC refuses it: its store rule already tests dominance.
+//
+// --bge is the Bayesian score of the continuous data (ulg_bge_score; the
+// reference has none): the columns are read as numbers, as for -f cBIC, the
+// prior is --alpha-mu (default 1, 1e-3 .. 1e3) and --alpha-w (default 0 =
+// n + alpha_mu + 1; otherwise above n + 1), "META score_type = bge", --lambda
+// is ignored, and every finite value is written, positive ones included.
+// --prune applies.  It does not go with --bdeu, --fnml, -f cBIC or
+// --enableDeCamposPruning; -f BGe keeps being refused like every -f but BIC
+// and cBIC.
 #include <cmath>
 #include <cctype>
 #include <cstdio>
@@ -60,9 +70,12 @@ int main(int argc, char **argv) {
             {"r", "time", true, "-1", "The maximum amount of time (s) to use for each variable (every variable is scored at once: the budget of the whole call, checked after each layer). A value less than 1 means no limit."},
             {"s", "hasHeader", false, "", "Add this flag if the first line of the input file gives the variable names."},
             {"o", "doNotPrune", false, "", "No effect (the reference's pruning is disabled, score_main.cpp:167-171; --prune runs it for -f BIC)."},
-            {"", "prune", false, "", "Drop every parent set that a kept proper subset dominates (the reference's prune(); -f BIC only)."},
+            {"", "prune", false, "", "Drop every parent set that a kept proper subset dominates (the reference's prune(); -f BIC, --bdeu, --fnml and --bge)."},
             {"", "bdeu", false, "", "Score with BDeu (the reference's -f BDeu) and equivalent sample size -e. There is no BIC parent limit: without -p every subset of the candidates is scored."},
             {"", "fnml", false, "", "Score with fNML (the reference's -f fNML). It has no parameter and no BIC parent limit: without -p every subset of the candidates is scored."},
+            {"", "bge", false, "", "Score continuous data with BGe, the Bayesian Gaussian equivalent score (prior: --alpha-mu, --alpha-w). Every finite value is stored; --lambda is ignored."},
+            {"", "alpha-mu", true, "1", "The prior's alpha_mu of --bge, 1e-3 to 1e3."},
+            {"", "alpha-w", true, "0", "The prior's alpha_w of --bge: above n + 1, at most n + 1e6; 0 means n + alpha_mu + 1."},
             {"", "enableDeCamposPruning", false, "", "No effect for cBIC; refused for BIC, --bdeu and --fnml."},
             {"", "device", true, "0", "HIP device to use."},
             {"h", "help", false, "", "Show this help message."},
@@ -106,15 +119,41 @@ int main(int argc, char **argv) {
                      args.get("function").c_str());
         return 2;
     }
+    const bool bge = args.has("bge");
+    if (bge && (bdeu || fnml)) {
+        std::fprintf(stderr, "score: --bge is the score of continuous data; it does not go with --bdeu or --fnml\n");
+        return 2;
+    }
+    if (bge && sf != "bic") {
+        std::fprintf(stderr, "score: --bge is a continuous score of its own; it does not go with -f %s\n",
+                     args.get("function").c_str());
+        return 2;
+    }
+    if (bge && args.has("enableDeCamposPruning")) {
+        std::fprintf(stderr, "score: --enableDeCamposPruning is not built for --bge\n");
+        return 2;
+    }
+    const double alpha_mu = std::strtod(args.get("alpha-mu").c_str(), nullptr);
+    const double alpha_w = std::strtod(args.get("alpha-w").c_str(), nullptr);
+    if (bge && !(alpha_mu >= 1e-3 && alpha_mu <= 1e3)) {
+        std::fprintf(stderr, "score: --bge needs 1e-3 <= --alpha-mu <= 1e3 (got '%s')\n", args.get("alpha-mu").c_str());
+        return 2;
+    }
+    if (bge && !(alpha_w == 0.0 || (alpha_w > 0.0 && std::isfinite(alpha_w)))) {
+        std::fprintf(stderr, "score: --bge needs --alpha-w above n + 1, or 0 for n + alpha_mu + 1 (got '%s')\n",
+                     args.get("alpha-w").c_str());
+        return 2;
+    }
     if (bdeu) sf = "bdeu";
     if (fnml) sf = "fnml";
-    const bool discrete = sf == "bic" || bdeu || fnml;
+    if (bge) sf = "bge";
+    const bool discrete = !bge && (sf == "bic" || bdeu || fnml);
     if (discrete && args.has("enableDeCamposPruning")) {
         std::fprintf(stderr, "score: --enableDeCamposPruning is not built for -f BIC, --bdeu or --fnml (it is a no-op for -f cBIC)\n");
         return 2;
     }
     const bool prune = args.has("prune");
-    if (prune && !discrete) {
+    if (prune && !discrete && !bge) {
         std::fprintf(stderr, "score: --prune is for -f BIC, --bdeu and --fnml: the store rule of -f cBIC already tests dominance, and the "
                              "reference disabled prune() for the continuous case\n");
         return 2;
@@ -213,14 +252,17 @@ int main(int argc, char **argv) {
     if (rc == ULG_OK && !cons.vars.empty())
         rc = ulg_cbic_set_constraints(ctx, (int)cons.vars.size(), cons.vars.data(), cons.required.data(),
                                       cons.forbidden.data());
-    if (rc == ULG_OK && prune) rc = ulg_set_option(ctx, "disc_prune", 1);
+    if (rc == ULG_OK && prune) rc = ulg_set_option(ctx, bge ? "bge_prune" : "disc_prune", 1);
     if (rc == ULG_OK && bdeu) rc = ulg_disc_set_ess(ctx, ess);
-    if (rc == ULG_OK)
+    if (rc == ULG_OK && bge) rc = ulg_bge_set_prior(ctx, alpha_mu, alpha_w);
+    if (rc == ULG_OK && bge)
+        rc = ulg_bge_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
+    else if (rc == ULG_OK)
         rc = discrete ? ulg_disc_score(ctx, bdeu ? ULG_SCORE_BDEU : fnml ? ULG_SCORE_FNML : ULG_SCORE_BIC, vars.data(), n, cands.data(), maxp, &stored, &scored)
                       : ulg_cbic_score(ctx, vars.data(), n, cands.data(), maxp, &stored, &scored);
     int64_t oot = 0, done_layer = 0, pruned = 0;
     if (rc == ULG_OK && prune) {
-        ulg_get_info(ctx, "disc_pruned", &pruned);
+        ulg_get_info(ctx, bge ? "bge_pruned" : "disc_pruned", &pruned);
         // score_main.cpp:159,170, once for the whole call
         std::printf("Size before pruning: %lld\nSize after pruning: %lld\n", (long long)(stored + pruned), (long long)stored);
     }
@@ -275,11 +317,13 @@ int main(int argc, char **argv) {
     if (prune) std::snprintf(pruned_field, sizeof pruned_field, ", \"pruned\": %lld", (long long)pruned);
     char ess_field[48] = "";
     if (bdeu) std::snprintf(ess_field, sizeof ess_field, ", \"ess\": %.9g", ess);
+    char prior_field[96] = "";
+    if (bge) std::snprintf(prior_field, sizeof prior_field, ", \"alpha_mu\": %.9g, \"alpha_w\": %.9g", alpha_mu, alpha_w);
     std::fprintf(stderr,
                  "ulg_metrics {\"tool\": \"score\", \"function\": \"%s\", \"n\": %d, \"N\": %lld, \"k\": %d, \"lambda\": %g, "
                  "\"scored\": %lld, \"stored\": %lld, \"score_s\": %.6f, \"sets_per_s\": %.6g, \"format_s\": %.6f, "
-                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d%s%s}\n",
+                 "\"write_s\": %.6f, \"bytes\": %lld, \"out_of_time\": %d%s%s%s}\n",
                  sf.c_str(), n, (long long)N, maxp, lambda, (long long)scored, (long long)stored, t1 - t0,
-                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot, pruned_field, ess_field);
+                 (double)scored / (t1 - t0), t2 - t1, t3 - t2, (long long)len, (int)oot, pruned_field, ess_field, prior_field);
     return 0;
 }

@@ -52,6 +52,10 @@ def lib():
         L.ulg_disc_counts.argtypes = [P, I, C.c_uint64, P, I64, C.POINTER(I64)]
         if hasattr(L, "ulg_disc_regret"):  # ULG_LIB may name a build from before fNML (A/B runs of BIC and BDeu)
             L.ulg_disc_regret.argtypes = [P, I, I64, I64, P]
+        if hasattr(L, "ulg_bge_score"):  # ULG_LIB may name a build from before BGe (A/B runs of the benchmark)
+            L.ulg_bge_set_prior.argtypes = [P, D, D]
+            L.ulg_bge_score.argtypes = [P, P, I, P, I, C.POINTER(I64), C.POINTER(I64)]
+            L.ulg_bge_score_sets.argtypes = [P, I64, P, P, P]
         L.ulg_chi2_log_sf.argtypes = [D, D]
         L.ulg_chi2_log_sf.restype = D
         L.ulg_disc_g2.argtypes = [P, I64, P, P, P, P, P, P]
@@ -308,6 +312,48 @@ class Context:
         out = np.empty(max(len(v), 1), dtype=np.float32)
         self._check(lib().ulg_disc_score_sets(self._h, int(kind), len(v), _ptr(v), _ptr(p), _ptr(out)),
                     "ulg_disc_score_sets")
+        return out[:len(v)]
+
+    # ---- BGe (continuous data) ------------------------------------------------
+    def set_bge_prior(self, alpha_mu: float = 1.0, alpha_w: float = 0.0):
+        """ulg_bge_set_prior: sticky; alpha_w = 0 means n + alpha_mu + 1 at scoring time.
+        1e-3 <= alpha_mu <= 1e3 and alpha_w = 0 or n + 1 < alpha_w <= n + 1e6; a refused
+        value leaves the previous prior."""
+        self._check(lib().ulg_bge_set_prior(self._h, float(alpha_mu), float(alpha_w)), "ulg_bge_set_prior")
+        self._bge_prior = (float(alpha_mu), float(alpha_w))
+
+    def _bge_args(self, alpha_mu, alpha_w):
+        if alpha_mu is not None or alpha_w is not None:
+            cur = getattr(self, "_bge_prior", (1.0, 0.0))
+            self.set_bge_prior(cur[0] if alpha_mu is None else alpha_mu, cur[1] if alpha_w is None else alpha_w)
+
+    def score_bge(self, variables, candidates, max_parents: int, prune=None, alpha_mu=None, alpha_w=None):
+        """ulg_bge_score on the data of load() -> (total_stored, total_scored); fetch() reads
+        the lists.  Every finite value is stored, whatever its sign.
+        prune: True / False sets option "bge_prune" (sticky) before the call; info("bge_pruned")
+        then counts the removed sets.  None leaves the option as it is.
+        alpha_mu / alpha_w: set_bge_prior before the call (sticky; None keeps that part)."""
+        if prune is not None:
+            self.set_option("bge_prune", 1 if prune else 0)
+        self._bge_args(alpha_mu, alpha_w)
+        v = np.ascontiguousarray(variables, dtype=np.int32)
+        c = np.ascontiguousarray(candidates, dtype=np.uint64)
+        st, sc = C.c_int64(), C.c_int64()
+        self._check(lib().ulg_bge_score(self._h, _ptr(v), len(v), _ptr(c), int(max_parents),
+                                        C.byref(st), C.byref(sc)), "ulg_bge_score")
+        self._nv = len(v)
+        return st.value, sc.value
+
+    def score_sets_bge(self, variables, parents, alpha_mu=None, alpha_w=None) -> np.ndarray:
+        """The BGe value per (variable, parent mask) pair (ulg_bge_score_sets): NaN for a set on a
+        constant column, a pivot <= 0 or a set that violates the constraints."""
+        self._bge_args(alpha_mu, alpha_w)
+        v = np.ascontiguousarray(variables, dtype=np.int32)
+        p = np.ascontiguousarray(parents, dtype=np.uint64)
+        if v.shape != p.shape:
+            raise ValueError("score_sets_bge: variables and parents differ in length")
+        out = np.empty(max(len(v), 1), dtype=np.float32)
+        self._check(lib().ulg_bge_score_sets(self._h, len(v), _ptr(v), _ptr(p), _ptr(out)), "ulg_bge_score_sets")
         return out[:len(v)]
 
     def regret(self, arity: int, first: int, count: int) -> np.ndarray:
@@ -574,7 +620,8 @@ class Context:
         """ulg_get_info: "out_of_time", "highest_completed_layer", "score_error_word",
         "exact_cycles", "exact_instructions", "exact_cache_misses", "disc_mmpc_tests",
         "disc_mmpc_skipped", "disc_pruned" (sets the last score_discrete's prune pass
-        removed; 0 with option "disc_prune" off), "fnml_table_bytes" (the SCORE_FNML
+        removed; 0 with option "disc_prune" off), "bge_pruned" (likewise for score_bge and
+        option "bge_prune"), "fnml_table_bytes" (the SCORE_FNML
         regret table of the loaded data; 0 while there is none), "score_graph_captures"
         (scoring calls of this context that captured their launch graph anew)."""
         v = C.c_int64()

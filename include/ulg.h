@@ -615,6 +615,89 @@ int ulg_sweep_shard_end(ulg_ctx *ctx, uint64_t *vpar, int *order, float *goal_co
  * runs: one device-to-host copy. */
 int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
 
+/* ---- exact model averaging over the order lattice (no reference counterpart) ----
+ * What a Bayesian score (BDeu, BGe: log marginal likelihoods) is for beyond the
+ * single best DAG: the posterior probability of every stored parent set, the
+ * n x n matrix of edge posteriors and ln Z, by the sum-product form of the
+ * lattice recursions the searches run in min-plus form (Koivisto & Sood 2004;
+ * Koivisto 2006).  No sampling: the sums are exact.
+ *
+ * Input: per-variable lists (offsets[n+1], sets, scores), ulg_search_load_scores'
+ * layout.  Scores are natural-log float32 values of either sign.  V = {0..n-1};
+ * a stored set P of v has weight w_v(P) = exp(s_v(P)), an absent set weight 0.
+ * The model is the ORDER-MODULAR prior: the pair (linear order <, DAG G whose
+ * every parent set precedes its child in <) has weight prod_v w_v(Pa_v).  It
+ * is NOT uniform over DAGs: a DAG counts once per linear extension, so DAGs
+ * with many topological orders weigh more than under a flat structure prior.
+ * All in FP64 log space (a table holds ln of the quantity, -inf for 0):
+ *   alpha_v(S) = sum_{stored P subset of S} w_v(P),  S subset of V\{v}
+ *                2^(n-1) entries per variable; index of S = S with bit v
+ *                squeezed out (subset-sum transform of the scattered list)
+ *   f(0) = 1,  f(S) = sum_{v in S} f(S\v) alpha_v(S\v);     Z = f(V)
+ *   b(0) = 1,  b(T) = sum_{v in T} alpha_v(V\T) b(T\v)      (v first of T, its
+ *                predecessors exactly V\T);                  b(V) = Z as well
+ *   g_v(S) = f(S) b(V\S\{v}),   gamma_v(P) = sum_{S superset of P, S subset of V\{v}} g_v(S)
+ *   p(Pa_v = P) = w_v(P) gamma_v(P) / Z   for every stored P
+ *   p(u -> v)   = sum_{stored P containing u} p(Pa_v = P)
+ * f and b are indexed by the mask itself.
+ * Log space: logaddexp(a, b) = max + log1p(exp(-|a - b|)); -inf when both are
+ * -inf (inf - inf is never formed); the maximum unchanged when the gap exceeds
+ * 38 nats (exp(-38) < 2^-54: below half an ulp of any maximum of magnitude
+ * >= 1/2, and an absolute 5.6e-17 below that) -- one device function
+ * (csrc/posterior_dev.h) that every kernel uses.  Every output is a fixed
+ * expression tree of its inputs: the sweeps' sums run over v ascending, the
+ * transforms take bit 0 upward, the per-variable and per-edge sums take the
+ * maximum first (order-free) and then add in an order fixed by the list alone
+ * (entry i goes to lane i mod 256, lanes add their entries ascending, then a
+ * fixed binary tree over the lanes).  No floating-point atomics: the results
+ * are bit-identical across calls, contexts and launch geometry.
+ * set_logpost[i] = s_i + ln gamma_v(P_i) - L_v with L_v the log of the sum of
+ * w gamma over v's own stored sets.  L_v = ln Z in exact arithmetic
+ * (sum_S g_v(S) alpha_v(S) = Z for every v) and differs from the forward
+ * sweep's ln Z by rounding only; normalising by it makes a variable's stored
+ * sets sum to 1 to the last bit the sum allows, and gives the only set of a
+ * variable exactly 0.0.  If Z = 0 (e.g. a variable with an empty list) the
+ * call succeeds with *log_z = -inf, every set_logpost -inf and every edge 0.
+ *
+ * ulg_posterior: offsets is a host array; device_ptrs = 1: sets and scores are
+ * device pointers on this context's GPU, 0: host pointers.  Outputs are host
+ * pointers: edge[u*n+v] = p(u -> v), diagonal 0; set_logpost (one per list
+ * entry, in list order) may be NULL.
+ * ulg_posterior_from_scores: the lists of the last scoring call of any kind
+ * (ulg_cbic_score*, ulg_disc_score, ulg_bge_score; a pending async call is
+ * collected first), scores as they are -- not the "%f" costs.  That call must
+ * have scored every variable once; its vars may name them in any order (the
+ * lists are put in index order here, as ulg_search_from_scores does).  A call
+ * that scored only some variables, or one twice, is ULG_ERR_STATE.
+ * set_logpost is in variable index order, each variable's sets in their stored
+ * order.
+ * Lists pruned by dominance (cBIC's store rule, "disc_prune", "bge_prune")
+ * give the posterior over the pruned family only: Z is then a lower bound of
+ * the full sum, not the full average.
+ * ulg_posterior_table (tests, in the manner of ulg_bestscore_table): one table
+ * of the last successful posterior call.  which = 0: ln alpha_var, 1: ln f,
+ * 2: ln b, 3: ln gamma_var.  *count = 2^(n-1) for 0 and 3, 2^n for 1 and 2 (var
+ * is ignored); cap = 0 asks for the count only, a smaller nonzero cap is
+ * ULG_ERR_ARG.  The gamma tables are kept on request: with option
+ * "posterior_keep" 1 at the time of the call all n stay on the device; with 0
+ * (the default) one table is reused variable after variable and which = 3 is
+ * ULG_ERR_STATE.  ULG_ERR_STATE without a successful posterior call.
+ * Errors: ULG_ERR_ARG for n < 1, offsets not ascending, a set with its own
+ * variable's bit or a bit >= n, a duplicate set within a variable, a NaN or
+ * infinite score (sets and scores are checked on the device, by the pass that
+ * scatters them); ULG_ERR_UNSUPPORTED for n > 28 or when tables and lists do not
+ * fit the free device memory -- decided before anything is allocated, the
+ * message names the bytes needed.  Tables: 8 B x (n 2^(n-1) + 2 x 2^n + G 2^(n-1)),
+ * G = 1 gamma table, n with "posterior_keep" (n = 25: 4.0 GB, n = 28: 35 GB);
+ * ulg_get_info("posterior_bytes") gives that figure for the last successful
+ * call.  Neither call touches the context's lists, the search tables, the
+ * pattern database or the .pss state. */
+int ulg_posterior(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
+                  const float *scores, int device_ptrs, double *log_z, double *edge,
+                  double *set_logpost);
+int ulg_posterior_from_scores(ulg_ctx *ctx, double *log_z, double *edge, double *set_logpost);
+int ulg_posterior_table(ulg_ctx *ctx, int which, int var, double *out, int64_t cap, int64_t *count);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the
@@ -687,6 +770,9 @@ int ulg_sweep_leaves(ulg_ctx *ctx, uint8_t *out, int64_t cap, int64_t *count);
  * "disc_prune" (0/1, default 0): ulg_disc_score drops every set that a kept
  * proper subset dominates (the reference's prune(); see ulg_disc_score).
  * "bge_prune" (0/1, default 0): the same pass for ulg_bge_score.
+ * "posterior_keep" (0/1, default 0): ulg_posterior* keep every variable's
+ * gamma table for ulg_posterior_table instead of reusing one (n - 1 more
+ * tables of 2^(n-1) doubles); the outputs are bit-identical either way.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -745,6 +831,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * loaded data; 0 until an fNML call builds it and after every load),
  * "disc_mmpc_tests" / "disc_mmpc_skipped" (G^2 tests the last
  * ulg_disc_mmpc performed / left out by its reliability rule),
+ * "posterior_bytes" (the device bytes of the last successful ulg_posterior*
+ * call's tables, by the formula there; 0 before any),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
  * "lds_image_bytes" (bytes of the last scoring call's launch images),
  * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the

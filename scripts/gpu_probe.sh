@@ -32,6 +32,10 @@
 #   bge         scripts/bge_profile.py (BGe at the C3 shape against cBIC and
 #               the generic ulg_bge_score_sets; RESOURCE_USAGE = the text of
 #               `make resource-usage`, optional)              -> bge.json
+#   posterior   scripts/posterior_profile.py (ulg_posterior at n = 20 and 25,
+#               full lists up to 4 parents, per-kernel split, the numpy
+#               recursion at n = 16 for scale; POSTERIOR_PYTEST_LOG = a
+#               `pytest -s` log of the GPU tests, optional)   -> posterior.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -144,6 +148,10 @@ for step in ${STEPS:-suite smoke bench}; do
       timeout -k 10 300 python3 scripts/bge_profile.py "$OUT/bge.json" \
         ${RESOURCE_USAGE:+--resource-usage $RESOURCE_USAGE} > "$OUT/bge.log" 2>&1
       tail -n 1 "$OUT/bge.log" | cut -c1-900 ;;
+    posterior)
+      timeout -k 10 300 python3 scripts/posterior_profile.py "$OUT/posterior.json" \
+        ${POSTERIOR_PYTEST_LOG:+--pytest-log $POSTERIOR_PYTEST_LOG} > "$OUT/posterior.log" 2>&1
+      tail -n 1 "$OUT/posterior.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

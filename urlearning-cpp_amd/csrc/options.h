@@ -46,6 +46,8 @@ struct Options {
     int64_t disc_prune = 0;          // ulg_disc_score: drop dominated sets (the reference's prune())
     // ---- BGe scorer ----
     int64_t bge_prune = 0;           // ulg_bge_score: the same pass over the BGe slot table
+    // ---- exact model averaging ----
+    int64_t posterior_keep = 0;      // ulg_posterior*: keep every variable's gamma table for ulg_posterior_table
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -88,6 +90,7 @@ constexpr OptionRow kOptionRows[] = {
     {"disc_dense_cells", &Options::disc_dense_cells, 1, 32768, 0, {}, "1..32768"},
     {"disc_prune", &Options::disc_prune, 0, 1, 0, {}, "0 or 1"},
     {"bge_prune", &Options::bge_prune, 0, 1, 0, {}, "0 or 1"},
+    {"posterior_keep", &Options::posterior_keep, 0, 1, 0, {}, "0 or 1"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -156,6 +156,7 @@ ulg_ctx::~ulg_ctx() {
         ulg::graph_reset(this);
     }
     ulg::pss_delete(this);
+    ulg::posterior_delete(this);
     delete search;
 }
 
@@ -279,6 +280,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     // the last ulg_bge_score: sets its prune pass removed (0 with bge_prune off)
     if (std::strcmp(name, "bge_pruned") == 0) {
         *value = c->bge_pruned;
+        return ULG_OK;
+    }
+    // the tables of the last successful ulg_posterior* call (the formula of ulg.h)
+    if (std::strcmp(name, "posterior_bytes") == 0) {
+        *value = c->posterior_bytes;
         return ULG_OK;
     }
     // the fNML regret table of the loaded data (0: not built since the last load)

@@ -23,6 +23,7 @@ constexpr uint32_t kAbsentBits = 0xFFFFFFFFu;  // "not in the FloatMap" sentinel
 
 struct SearchState;
 struct PssState;
+struct PosteriorState;
 
 struct ProfRec {
     std::string name;
@@ -176,6 +177,10 @@ struct ulg_ctx : ulg::CtxStreams {
     // ---- .pss text formatting (pss.hip) ----
     ulg::PssState *pss = nullptr;
 
+    // ---- exact model averaging (posterior.hip): its lists and tables, apart from everything above ----
+    ulg::PosteriorState *posterior = nullptr;
+    int64_t posterior_bytes = 0;  // ulg_get_info("posterior_bytes"): the last successful call's tables
+
     // ---- profiling ----
     bool prof = false;
     std::vector<ulg::ProfRec> pending;
@@ -213,6 +218,7 @@ void prof_end_s(ulg_ctx *c, hipStream_t stream);
 void prof_collect(ulg_ctx *c);  // after a stream sync
 void graph_reset(ulg_ctx *c);   // drop the captured scoring graph (cbic.hip)
 void pss_delete(ulg_ctx *c);   // delete the context's PssState (pss.hip, where the type is complete)
+void posterior_delete(ulg_ctx *c);  // ... and its PosteriorState (posterior.hip)
 
 // binomial table C(a, b), a < 64, b < kBinomK, clamped to uint32
 const std::vector<uint32_t> &host_binom();

@@ -85,6 +85,13 @@ def lib():
         L.ulg_sweep_shard_commit.argtypes = [P, I, P]
         L.ulg_sweep_shard_end.argtypes = [P, P, P, C.POINTER(F), C.POINTER(I64)]
         L.ulg_sweep_leaves.argtypes = [P, P, I64, C.POINTER(I64)]
+        # ULG_LIB may name a build from before the model averaging: A/B runs of bench.py against an older
+        # library load it through this binding, as for the two guards above; calling a method whose
+        # symbol the library lacks still raises
+        if hasattr(L, "ulg_posterior"):
+            L.ulg_posterior.argtypes = [P, I, P, P, P, I, C.POINTER(D), P, P]
+            L.ulg_posterior_from_scores.argtypes = [P, C.POINTER(D), P, P]
+            L.ulg_posterior_table.argtypes = [P, I, I, P, I64, C.POINTER(I64)]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -442,6 +449,58 @@ class Context:
                     "ulg_search_load_scores")
         del keep
         self.search_n = len(o) - 1
+
+    # ---- exact model averaging over the order lattice ------------------------
+    def posterior(self, offsets, sets, scores, device_ptrs=False, want_sets=True):
+        """ulg_posterior on per-variable lists (offsets[n+1] on the host; sets / scores numpy
+        arrays, or device addresses with device_ptrs) under the order-modular prior
+        -> (log_z, edge float64 (n, n) with edge[u, v] = p(u -> v), set_logpost float64 per
+        list entry or None)."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(o) - 1
+        total = int(o[-1] - o[0]) if n >= 0 and len(o) else 0
+        if device_ptrs:
+            sp, cp, keep = C.c_void_p(int(sets)), C.c_void_p(int(scores)), None
+        else:
+            s = np.ascontiguousarray(sets, dtype=np.uint64)
+            c = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.size == 0:
+                s, c = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.float32)
+            sp, cp, keep = _ptr(s), _ptr(c), (s, c)
+        lz = C.c_double()
+        edge = np.zeros((max(n, 1), max(n, 1)), dtype=np.float64)
+        lp = np.zeros(max(total, 1), dtype=np.float64) if want_sets else None
+        self._check(lib().ulg_posterior(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, C.byref(lz), _ptr(edge),
+                                        _ptr(lp) if lp is not None else None), "ulg_posterior")
+        del keep
+        return lz.value, edge, (lp[:max(total, 0)] if lp is not None else None)
+
+    def posterior_from_scores(self, want_sets=True):
+        """ulg_posterior_from_scores: the same from the lists of the last scoring call (every
+        variable scored), scores as they are; set_logpost in variable order."""
+        n = self.n or 1
+        total = 0
+        if want_sets and hasattr(self, "_nv"):  # the list entries: the last offset of the stored lists
+            offs = np.zeros(self._nv + 1, dtype=np.int64)
+            self._check(lib().ulg_cbic_fetch(self._h, None, None, _ptr(offs), 0), "ulg_cbic_fetch")
+            total = int(offs[-1])
+        lz = C.c_double()
+        edge = np.zeros((n, n), dtype=np.float64)
+        lp = np.zeros(max(total, 1), dtype=np.float64) if want_sets else None
+        self._check(lib().ulg_posterior_from_scores(self._h, C.byref(lz), _ptr(edge),
+                                                    _ptr(lp) if lp is not None else None), "ulg_posterior_from_scores")
+        return lz.value, edge, (lp[:total] if lp is not None else None)
+
+    def posterior_table(self, which: int, var: int = 0) -> np.ndarray:
+        """ulg_posterior_table: one table of the last posterior call as float64 -- which = 0: ln
+        alpha_var, 1: ln f, 2: ln b, 3: ln gamma_var (option "posterior_keep" 1 at the call)."""
+        cnt = C.c_int64()
+        self._check(lib().ulg_posterior_table(self._h, int(which), int(var), None, 0, C.byref(cnt)),
+                    "ulg_posterior_table")
+        out = np.empty(cnt.value, dtype=np.float64)
+        self._check(lib().ulg_posterior_table(self._h, int(which), int(var), _ptr(out), out.size, C.byref(cnt)),
+                    "ulg_posterior_table")
+        return out
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

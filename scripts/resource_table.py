@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """The layer kernels' lines of a resource table (profiles/r21/resource_usage.txt)
-from one compile of cbic.hip:
+from one compile each of the files that hold the layer kernels, cbic_layers.hip
+and cbic_layers_cons.hip:
 
     hipcc <the Makefile's HIPFLAGS> --cuda-device-only -S -Rpass-analysis=kernel-resource-usage \
-        -o cbic.s urlearning-cpp_amd/csrc/cbic.hip 2> cbic_ru.log
-    python scripts/resource_table.py cbic_ru.log cbic.s [LAYERS, default 4,5,6]
+        -o cbic_layers.s urlearning-cpp_amd/csrc/cbic_layers.hip 2> cbic_layers_ru.log
+    (the same for cbic_layers_cons)
+    python scripts/resource_table.py cbic_layers_ru.log cbic_layers_cons_ru.log \
+        cbic_layers.s cbic_layers_cons.s [LAYERS, default 4,5,6]
+
+Any number of remark logs and of assembly files (*.s), in any order.
 
 One line per score_layer_kernel / score_layer_cons_kernel instantiation of the
 given layers, the remarks' numbers in profiles/r16's layout; with the assembly,
@@ -68,9 +73,14 @@ def static_counts(path):
 
 
 def main():
-    ru = remarks(sys.argv[1])
-    st = static_counts(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] != "-" else {}
-    layers = [int(x) for x in (sys.argv[3] if len(sys.argv) > 3 else "4,5,6").split(",")]
+    ru, st, layers = {}, {}, [4, 5, 6]
+    for a in sys.argv[1:]:
+        if re.fullmatch(r"\d+(,\d+)*", a):
+            layers = [int(x) for x in a.split(",")]
+        elif a.endswith(".s"):
+            st.update(static_counts(a))
+        elif a != "-":
+            ru.update(remarks(a))
     for name, r in sorted(ru.items(), key=lambda kv: kv[1]["key"]):
         if r["key"][1] not in layers:
             continue

@@ -1,6 +1,6 @@
 // Offline study of the bit-sliced walk launches (round 6, review item 1):
 // replays walk_sliced (cbic_dev.h) on the queues a C3 call dumped
-// (ULG_WALK_CLOCK + ULG_WALK_QUEUE_DUMP, cbic.hip dump_walk_queue), checks the
+// (ULG_WALK_CLOCK + ULG_WALK_QUEUE_DUMP, cbic_walk.hip dump_walk_queue), checks the
 // replay's decisions against the ones the GPU wrote, and prints the union
 // points of the waves of several schedules -- a wave's time is about its union
 // points x ~630 cycles, and a launch lasts as long as its longest wave.

@@ -3,7 +3,7 @@ ULG_UNROLLED_PARENTS_GPU = 8, up to ULG_MAX_PARENTS_GPU = 31).
 
 The reference's default parent limit is n - 1 (score_main.cpp:296-298), so
 config C1 (data/hepatitis.clean.csv, n = 20) scores layers 1..19.  Layers
-above 8 run the runtime-L kernels of cbic.hip (score_wide_kernel +
+above 8 run the runtime-L kernels of cbic_wide.hip (score_wide_kernel +
 walk_wide_kernel, the explicit-stack replay of find_best_subset_score,
 BIC_OLS.cpp:125-172).
 

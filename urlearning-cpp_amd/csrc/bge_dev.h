@@ -80,7 +80,7 @@ __host__ __device__ __forceinline__ float bge_set_score(const double *g, int n, 
     return ok ? (float)val : __builtin_nanf("");
 }
 
-// ulg_cbic_set_constraints' by-variable table in variable masks (cbic.hip
+// ulg_cbic_set_constraints' by-variable table in variable masks (cbic_layer_dev.h
 // cons_violates): words [0, n] prefix the variables' alternatives, then one
 // (required, forbidden) pair per alternative.
 __device__ __forceinline__ bool bge_violates(const uint64_t *ct, int n, int v, uint64_t set) {

@@ -1,5 +1,6 @@
-// cbic_dev.h -- device building blocks of the cBIC scorer's layer kernels
-// (cbic.hip).
+// cbic_dev.h -- device building blocks of the cBIC scorer's layer and walk
+// kernels (cbic_layers.hip, cbic_layers_cons.hip, cbic_walk.hip; what those
+// share above these blocks: cbic_layer_dev.h).
 //
 // Reference semantics (ninalu/urlearning-cpp, urlearning/):
 //   colex rank == Gosper enumeration index    base/typedefs.h:692-697
@@ -814,7 +815,7 @@ __device__ __forceinline__ double clamp_rss(double rss) { return rss < 0.0 ? 0.0
 // y = L^-1 G[P,v], RSS = G[v,v] - |y|^2, score = N ln(RSS / N) + lambda ln(N) L
 // (BIC_OLS.cpp:366), returned as float like the reference.  Every layer kernel
 // uses this one operation order.  pen = lambda ln(N), the device's own rounded
-// product, computed once at ulg_cbic_load (penalty_kernel, cbic.hip): it is a
+// product, computed once at ulg_cbic_load (penalty_kernel, cbic_gram.hip): it is a
 // constant of the context, and its logarithm was ~74 VALU instructions of
 // every lane of every launch.
 template <int L>

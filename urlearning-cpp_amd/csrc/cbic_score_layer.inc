@@ -1,6 +1,6 @@
-// cbic_score_layer.inc -- the body of score_layer_kernel, included by cbic.hip
-// once per form: ULG_CONS 0 is score_layer_kernel, 1 its constrained
-// twin score_layer_cons_kernel (launched while the context holds
+// cbic_score_layer.inc -- the body of score_layer_kernel, included once per
+// form: ULG_CONS 0 (cbic_layers.hip) is score_layer_kernel, 1
+// (cbic_layers_cons.hip) its constrained twin score_layer_cons_kernel (launched while the context holds
 // constraints): a set that violates its variable's constraints takes
 // ts = float(n) (BIC_OLS.cpp:279-283) without a regression, and everything
 // after ts is the same text.  Two kernels from one text, not one template
@@ -51,7 +51,7 @@ score_layer_kernel(ScoreArgs a) {
     };
     const uint4 im0 = piece(0), im1 = piece(1), im2 = piece(2), im3 = piece(3);
     // the wave's variable on the scalar unit, and with it the lane's unrank
-    // table entry, before the fill (wave_variable, cbic.hip)
+    // table entry, before the fill (wave_variable, cbic_layer_dev.h)
     const M gid0 = (M)xcd_block(blockIdx.x, gridDim.x, a.xcd) * kBlock + threadIdx.x;
     const WaveVar wv = wave_variable(a.work, a.lut_off, a.nv, a.total, gid0 - (threadIdx.x & 63u));
     const M wtotal = (M)wv.total, wbase = (M)wv.base;  // wave-uniform; NARROW: below 2^32 with a block to spare
@@ -113,15 +113,11 @@ score_layer_kernel(ScoreArgs a) {
     const bool z = hd.z;
     const M cm = hd.cm;
 
-#ifndef ULG_PROBE_NOSCORE  // ULG_PROBE_*: timing-only builds, see the two-pass section below
 #if ULG_CONS
     float ts = (float)a.n;
     if (!cons_violates(ct, a.nv, vi, cm)) ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
 #else
     const float ts = cbic_set_score<L>(g, a.n, hd.v, hd.gv, a.N, a.pen);
-#endif
-#else
-    const float ts = (float)(-a.N * g[hd.gv[0] * a.n + hd.gv[L - 1]] - (double)(r & 1023));
 #endif
 
     if constexpr (CMP) {
@@ -195,11 +191,6 @@ score_layer_kernel(ScoreArgs a) {
             *slot_ptr(a.table, slot) = out;
             if (a.hsub_out) *slot_ptr(a.hsub, slot) = fmaxf(out, hch);
         }
-// ULG_PROBE_*: timing-only builds (wrong lists, never shipped) that drop one
-// part of the two-pass kernel (scripts/r5_kernel_ab.sh, DESIGN.md §3.1d)
-#ifdef ULG_PROBE_NOCMP  // the undecided sets are left undecided
-        return;
-#endif
         // 2. the rest of the block's sets, compacted in LDS, so the presence
         //    gathers (2^(L+1) reads each) run on dense waves
         unsigned int *cnt = reinterpret_cast<unsigned int *>(smem + lay.cmp);
@@ -258,16 +249,9 @@ score_layer_kernel(ScoreArgs a) {
             // sets the rules leave to the walk (the subset maxima already
             // showed a key >= -ts is present, so the rules need no "any key"
             // test)
-#ifndef ULG_PROBE_NOPART1
             gather_keys<L, PHASE, V, BS, LdPlain, 1>(present, hib, ls, -tk, binom, zk, a.table,
                                                     toff_row<M>(toff, vk, a.S));
-#endif
-#ifndef ULG_PROBE_NORULES
             const bool dom = settle_rules<L, PHASE, BS, true>(present, hib, ls, q);
-#else
-            const bool dom = false;
-            q = false;
-#endif
 #ifdef ULG_GATHER_STATS
             if constexpr (W < 4) {
                 BS p2 = make_bits<BS>(lds_bits), h2 = make_bits<BS>(lds_bits);
@@ -330,3 +314,58 @@ score_layer_kernel(ScoreArgs a) {
 
     one_pass_set<L, PHASE, V>(a, smem, lay, binom, toff, vi, z, cm, hd.rankP, ts);
 }
+
+// This form's kernel for (layer, phase, variant, narrow): the host's dispatch,
+// one text for both forms like the kernel above.
+#if ULG_CONS
+#define ULG_LAYER_KERNEL score_layer_cons_kernel
+#else
+#define ULG_LAYER_KERNEL score_layer_kernel
+#endif
+using LayerFn = TwinFn<ULG_CONS != 0, ScoreArgs>;
+template <int L, int V, bool NARROW = false>
+LayerFn pick_phase(int phase) {
+    return phase == 0 ? ULG_LAYER_KERNEL<L, 0, V, NARROW> : ULG_LAYER_KERNEL<L, 1, V, NARROW>;
+}
+// variants (ulg_set_option "score_variant"): bit 0 unrolled presence gathers
+// (layers <= 6), bit 4 two-pass (settle, queue the rest for a walk launch),
+// bit 5 bit-sliced walk, bit 6 subset maxima.  1: one-pass (also the form for
+// tables of 2^30 slots or more); 65: one-pass with the subset maxima (the
+// small layers of 113); 49: two-pass with the bit-sliced walk (the tests'
+// every-set-gathered reference); 113: the same with the subset maxima (the
+// default).  Gone after measurement: round 4's per-lane walk forms 17 / 81
+// and a variant that walked the open sets inside the scoring kernel (C5 5.05
+// against 3.59 ms: a 64-set union tree repeats work a 256-set one shares);
+// round 1's loop gathers at every layer, stack-machine recursion,
+// decision-only per-lane walk and statistics build.
+// narrow: the launch's 32-bit form (CbicPlan::launch_narrow), built where
+// CbicPlan::narrow_built says so: the default variant's layers 5 and 6
+template <int L>
+LayerFn pick(int phase, int variant, bool narrow) {
+    if constexpr (CbicPlan::narrow_built(L, 241))
+        if (narrow && variant == 241) return pick_phase<L, 209, true>(phase);
+    if (narrow) return nullptr;
+    switch (variant) {
+        case 1: return pick_phase<L, 1>(phase);
+        case 49: return pick_phase<L, 17>(phase);
+        case 65: return pick_phase<L, 65>(phase);
+        case 113: return pick_phase<L, 81>(phase);
+        case 241: return pick_phase<L, 209>(phase);
+        default: return nullptr;
+    }
+}
+LayerFn layer_kernel(int L, int phase, int variant, bool narrow = false) {
+    switch (L) {
+        case 1: return pick<1>(phase, variant, narrow);
+        case 2: return pick<2>(phase, variant, narrow);
+        case 3: return pick<3>(phase, variant, narrow);
+        case 4: return pick<4>(phase, variant, narrow);
+        case 5: return pick<5>(phase, variant, narrow);
+        case 6: return pick<6>(phase, variant, narrow);
+        case 7: return pick<7>(phase, variant, narrow);
+        case 8: return pick<8>(phase, variant, narrow);
+        default: return nullptr;
+    }
+}
+static_assert(kMaxL == 8, "layer_kernel dispatch covers layers 1..8");
+#undef ULG_LAYER_KERNEL

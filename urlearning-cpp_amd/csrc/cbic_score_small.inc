@@ -1,6 +1,6 @@
 // cbic_score_small.inc -- the fused small layers (score_small_kernel and its
-// fused_phase), included by cbic.hip once per form: ULG_CONS 0 is the kernel
-// as it is without constraints, 1 its constrained twin (*_cons_kernel,
+// fused_phase), included once per form: ULG_CONS 0 (cbic_layers.hip) is the kernel
+// as it is without constraints, 1 (cbic_layers_cons.hip) its constrained twin (*_cons_kernel,
 // launched while the context holds constraints); see cbic_score_layer.inc.
 #if ULG_CONS
 #define ULG_FUSED_PHASE fused_phase_cons
@@ -73,3 +73,19 @@ __global__ void __launch_bounds__(kFusedThreads) score_small_kernel(ScoreArgs a,
 #endif
 }
 #undef ULG_FUSED_PHASE
+
+// This form's kernel for the fused layers 1..Lf (the host's dispatch).
+#if ULG_CONS
+#define ULG_SMALL_KERNEL score_small_cons_kernel
+#else
+#define ULG_SMALL_KERNEL score_small_kernel
+#endif
+TwinFn<ULG_CONS != 0, ScoreArgs, const uint64_t *> small_kernel(int Lf) {
+    switch (Lf) {
+        case 1: return ULG_SMALL_KERNEL<1, 65>;
+        case 2: return ULG_SMALL_KERNEL<2, 65>;
+        case 3: return ULG_SMALL_KERNEL<3, 65>;
+        default: return ULG_SMALL_KERNEL<4, 65>;
+    }
+}
+#undef ULG_SMALL_KERNEL

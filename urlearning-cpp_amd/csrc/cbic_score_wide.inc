@@ -1,4 +1,4 @@
-// cbic_score_wide.inc -- included by cbic.hip once per form: ULG_CONS 0 is the kernel as it
+// cbic_score_wide.inc -- included by cbic_wide.hip once per form: ULG_CONS 0 is the kernel as it
 // is without constraints, 1 its constrained twin (*_cons_kernel, launched while
 // the context holds constraints); see cbic_score_layer.inc.
 template <int LMAX, int PHASE>

@@ -30,7 +30,7 @@ int dev_upload(ulg_ctx *c, void *dst, const void *src, size_t bytes);
 template <typename T, bool kPinned>
 struct Buf {
     // 16 bytes of slack on the device: kernels read whole 16-byte chunks (the
-    // uint4 key loads of walk_bucket_count_kernel, cbic.hip), so the last
+    // uint4 key loads of walk_bucket_count_kernel, cbic_walk.hip), so the last
     // chunk of an array may read up to 15 bytes past its end
     static constexpr size_t kSlack = kPinned ? 0 : 16;
 

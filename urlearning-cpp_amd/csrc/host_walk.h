@@ -1,5 +1,5 @@
 // host_walk.h -- walk_wide_lds_kernel's replay of find_best_subset_score
-// (BIC_OLS.cpp:125-172; the reduced form of cbic.hip) on a host
+// (BIC_OLS.cpp:125-172; the reduced form of cbic_wide.hip) on a host
 // core.  Long walks move here from the GPU (ulg_set_option "wide_host"): a
 // walk is one sequential DFS, and one wave issues at most one instruction
 // every 4 cycles.  Plain C++ (no HIP), so host tools can time it too.
@@ -37,7 +37,7 @@ inline const NbrTables &nbr_tables() {
     return t;
 }
 
-constexpr int kStragDepth = 24;                // frames of a replay (cbic.hip's LDS replay has the same)
+constexpr int kStragDepth = 24;                // frames of a replay (cbic_wide.hip's LDS replay has the same)
 constexpr uint64_t kStragIterCap = 1ull << 32;  // iterations before a replay fails loudly
 
 // walk_wide_lds_kernel's walk on a host core, over the same skip / hi

@@ -24,12 +24,12 @@ namespace ulg {
 
 constexpr int kMaxVars = 63;                     // varset = uint64, bit 63 kept free
 constexpr int kMaxL = ULG_UNROLLED_PARENTS_GPU;  // unrolled layers on the device
-constexpr int kWideMax = ULG_MAX_PARENTS_GPU;    // wide layers kMaxL+1 .. kWideMax (cbic.hip)
+constexpr int kWideMax = ULG_MAX_PARENTS_GPU;    // wide layers kMaxL+1 .. kWideMax (cbic_wide.hip)
 
 constexpr int kBlock = 256;
 
 // Constraint tables of at most kConsLdsWords words are copied into LDS behind
-// the block's layout (cbic.hip cons_stage).
+// the block's layout (cbic_layer_dev.h cons_stage).
 constexpr int kConsLdsWords = 256;
 
 // The walk queue of a two-pass launch is cut into nseg = ceil(blocks /
@@ -230,7 +230,7 @@ struct ScoreLists {
 ULG_HD inline int mask_ctz(uint64_t x) { return __builtin_ctzll(x); }
 ULG_HD inline int mask_ctz(uint32_t x) { return __builtin_ctz(x); }
 // The L lowest elements of a mask in increasing order (the mask holds at
-// least L): set_head's walk of a set's members (cbic.hip); child_ranks_t
+// least L): set_head's walk of a set's members (cbic_layer_dev.h); child_ranks_t
 // below walks the same chain, and the compiler shares the two.
 template <int L, class M>
 ULG_HD inline __attribute__((always_inline)) void mask_elements(M mask, int (&el)[L]) {
@@ -362,7 +362,7 @@ struct CbicPlan {
     std::vector<uint64_t> vw;     // [task][L][phase][nv + 1] launch prefixes, only the task's variable counts
     int64_t nb = 0;               // compaction blocks
     // the call's constraint table: the alternatives of the scored variables in
-    // their compact candidate numbering (cbic.hip cons_violates)
+    // their compact candidate numbering (cbic_layer_dev.h cons_violates)
     std::vector<uint64_t> ct;
     int cons_words = 0;  // 0: the call runs the unconstrained kernels
     int cons_lds = 0;    // bytes of LDS the constrained kernels add

@@ -108,7 +108,7 @@ struct ulg_ctx : ulg::CtxStreams {
     ulg::DevBuf<uint64_t> d_queue;                // score_variant bit 4: undecided lanes
     ulg::DevBuf<uint32_t> d_qaux, d_qsidx, d_qoffs;  // walk_bucket: key/rank, sorted index, key bases
     ulg::DevBuf<uint8_t> d_qkey;                            // walk_bucket: each queue entry's walk key
-    ulg::DevBuf<unsigned long long> d_qseg;       // ... their per-segment counters (cbic.hip kSegBlocks)
+    ulg::DevBuf<unsigned long long> d_qseg;       // ... their per-segment counters (score_plan.h kSegBlocks)
     ulg::DevBuf<unsigned long long> d_qcount;
     ulg::DevBuf<uint64_t> d_workg;                // per stream-group work prefixes
     ulg::DevBuf<uint64_t> d_vwork;                // per-variable work prefixes of the wide-layer pool

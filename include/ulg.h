@@ -698,6 +698,64 @@ int ulg_posterior(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *s
 int ulg_posterior_from_scores(ulg_ctx *ctx, double *log_z, double *edge, double *set_logpost);
 int ulg_posterior_table(ulg_ctx *ctx, int which, int var, double *out, int64_t cap, int64_t *count);
 
+/* Sampling: independent (linear order, DAG) draws from the same order-modular
+ * posterior, for the features that do not factor over one parent set (paths,
+ * Markov blankets, v-structures, whole DAGs): any feature is a sample mean,
+ * another structure prior an importance weight.  Backward sampling through the
+ * forward table of the last successful ulg_posterior* call of the context
+ * (its lists, ln alpha_v and ln f stay on the device): exact i.i.d. draws, no
+ * MCMC and no burn-in.  A sample walks from S = V down to the empty set; the
+ * step at |S| = l has position i = l - 1 and makes two choices:
+ *   1. sink:        v in S with probability f(S\v) alpha_v(S\v) / f(S)
+ *   2. parent set:  a stored P subset of S\v of v with probability
+ *                   w_v(P) / alpha_v(S\v);  then S <- S\v.
+ * v is the variable at position i of the order.  The law of the pair is the
+ * order-modular posterior above, so p(Pa_v = P) under it is what set_logpost
+ * reports.
+ * Every choice is made in integers, as the discrete scorer's fixed-point sums
+ * are: no choice depends on a summation order or on the launch geometry.
+ *   weights  sink candidates: v in S ascending,
+ *              x_v = (ln f(S\v) + ln alpha_v(S\v)) - ln f(S), in FP64 in that
+ *              order; set candidates: v's list entries in list order,
+ *              x_i = (double) s_i - ln alpha_v(S\v) for P_i subset of S\v, an
+ *              entry that is not compatible has weight 0.
+ *              q = 0 for x = -inf, else q = (uint64) floor(exp(x) 2^52).
+ *   pick     T = sum of q (about 2^52: it never overflows); t = the high 64
+ *              bits of U T for a 64-bit draw U; the choice is the first
+ *              candidate j with C_j > t, C the running integer sum.  A
+ *              candidate of weight 0 is never chosen.  Each step's
+ *              probabilities are within (number of candidates) 2^-52 of the
+ *              exact ones (the floors), beyond what exp's rounding moves x.
+ *   draws    Philox4x32-10 with key (lo32(seed), hi32(seed)) and counter
+ *              (lo32(k), hi32(k), i, 0) gives (w0 .. w3); k = the global
+ *              sample index, i the step's position; U_sink = w0 | w1 << 32,
+ *              U_set = w2 | w3 << 32.  Sample k depends on (tables, lists,
+ *              seed, k) alone: a range may be split over calls at will.
+ * One definition of all three (csrc/posterior_sample_dev.h) serves every path.
+ * ulg_posterior_sample: samples first .. first + count - 1.  Outputs are host
+ * pointers: parents[k*n + v] = the parent mask of v in sample first + k;
+ * order[k*n + i] = the variable at position i, 0 first (may be NULL);
+ * log_weight[k] = sum over v ascending of (double) s_v(Pa_v) (may be NULL).
+ * count = 0 succeeds and writes nothing, and does no device work; the checks
+ * of first and of the state come before it (ULG_ERR_STATE without a successful
+ * posterior call also for count = 0), the look at ln Z after it.
+ * ulg_posterior_sample_u (tests, in the manner of ulg_posterior_table): the
+ * same kernel with the draws read, not generated: u[(k*n + i)*2] is U_sink and
+ * u[(k*n + i)*2 + 1] U_set of step position i of sample k (host pointer).
+ * Errors: ULG_ERR_STATE without a successful posterior call on the context, or
+ * when its ln Z = -inf; ULG_ERR_ARG for a negative first or count or a NULL
+ * parents (or u) with count > 0; ULG_ERR_UNSUPPORTED, decided before anything
+ * is allocated, when the call's device buffers (8 n bytes per sample, n more
+ * with order, 8 more with log_weight, 16 n more for u) do not fit the free
+ * device memory.  The buffers are kept from one sampling call to the next and
+ * freed by the next ulg_posterior* call before it sizes its tables.  Neither
+ * call changes the tables (ulg_posterior_table), the
+ * context's lists (ulg_cbic_fetch) or the search state. */
+int ulg_posterior_sample(ulg_ctx *ctx, uint64_t seed, int64_t first, int64_t count,
+                         uint64_t *parents, uint8_t *order, double *log_weight);
+int ulg_posterior_sample_u(ulg_ctx *ctx, int64_t count, const uint64_t *u, uint64_t *parents,
+                           uint8_t *order, double *log_weight);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the

@@ -36,6 +36,10 @@
 #               full lists up to 4 parents, per-kernel split, the numpy
 #               recursion at n = 16 for scale; POSTERIOR_PYTEST_LOG = a
 #               `pytest -s` log of the GPU tests, optional)   -> posterior.json
+#   posterior_sample  scripts/posterior_sample_profile.py (ulg_posterior_sample,
+#               K = 10^5 at the same n = 20 and 25 lists: the call, its kernel
+#               and copy-out, list scans against table gathers, the numpy
+#               walk at n = 16 for scale)               -> posterior_sample.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -152,6 +156,10 @@ for step in ${STEPS:-suite smoke bench}; do
       timeout -k 10 300 python3 scripts/posterior_profile.py "$OUT/posterior.json" \
         ${POSTERIOR_PYTEST_LOG:+--pytest-log $POSTERIOR_PYTEST_LOG} > "$OUT/posterior.log" 2>&1
       tail -n 1 "$OUT/posterior.log" | cut -c1-900 ;;
+    posterior_sample)
+      timeout -k 10 300 python3 scripts/posterior_sample_profile.py "$OUT/posterior_sample.json" \
+        > "$OUT/posterior_sample.log" 2>&1
+      tail -n 1 "$OUT/posterior_sample.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

@@ -37,27 +37,10 @@
 #include <cstring>
 
 #include "posterior_dev.h"
+#include "posterior_state.h"
 #include "ulg_internal.h"
 
 namespace ulg {
-
-struct PosteriorState {
-    int n = 0;
-    int64_t total = 0;     // list entries
-    bool ready = false;    // the tables are those of a successful call
-    bool kept = false;     // ... and gamma holds all n tables
-    DevBuf<uint64_t> d_sets;
-    DevBuf<float> d_scores;
-    DevBuf<int64_t> d_offsets;
-    std::vector<int64_t> offsets;  // their host copy (the source of the upload: it outlives the call)
-    DevBuf<double> alpha, f, b, gamma;
-    DevBuf<double> d_logpost, d_edge;
-    DevBuf<unsigned int> d_err;
-    size_t held_bytes() const {
-        return d_sets.cap * 8 + d_scores.cap * 4 + d_offsets.cap * 8 + (alpha.cap + f.cap + b.cap + gamma.cap) * 8 +
-               (d_logpost.cap + d_edge.cap) * 8 + d_err.cap * 4;
-    }
-};
 
 void posterior_delete(ulg_ctx *c) {
     delete c->posterior;
@@ -415,6 +398,7 @@ int refuse_size(ulg_ctx *c, const char *who, int n, int64_t total) {
             std::snprintf(buf, sizeof buf, "%s: n = %d; at most %d variables", who, n, kPostMaxVars);
         return set_err(c, ULG_ERR_UNSUPPORTED, buf);
     }
+    if (c->posterior) c->posterior->drop_samples();  // the sampler's buffers of an earlier call give way to the tables
     size_t free_b = 0, total_b = 0;
     ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
     const double need = table_bytes(n, keep ? n : 1) + 28.0 * (double)total + 8.0 * n * n + 8.0 * (n + 1) + 256.0;

@@ -4,6 +4,7 @@
 // counts once per linear extension; not uniform over DAGs).
 //
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
+//             [--sample K [--seed S] [-g dags.txt]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -13,11 +14,20 @@
 // n rows of n comma-separated "%.6f" values, row u column v = p(u -> v);
 // without -o it goes to standard output after the ln Z line.  -s writes one
 // line per stored set, in the file's order: "<name>: <posterior %.6f> <parent
-// names ...>".  Exit status: 0, 1 for a file or device error, 2 for a bad
-// command line.
+// names ...>".  --sample K draws K independent (order, DAG) pairs from the same
+// posterior (ulg_posterior_sample; --seed S, default 0: sample k of a seed is
+// the same in every run) and writes one line per sample: "%.6f" of the log
+// weight, then "<name><-<parent>,<parent>" for each variable in the sampled
+// order, separated by spaces; to the file of -g, else to standard output after
+// everything above.  Exit status: 0, 1 for a file or device error, 2 for a bad
+// command line (--seed or -g without --sample and a K that is not a positive
+// integer included).
+#include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 #include <string>
 #include <vector>
 
@@ -32,6 +42,9 @@ int main(int argc, char **argv) {
             {"o", "edges", true, "", "Write the edge posteriors here (csv, row u column v = p(u -> v))."},
             {"s", "sets", true, "", "Write the posterior of every stored parent set here."},
             {"d", "device", true, "0", "The GPU to use."},
+            {"", "sample", true, "", "Draw this many (order, DAG) samples from the posterior."},
+            {"", "seed", true, "", "The samples' seed (with --sample; 0 without it)."},
+            {"g", "dags", true, "", "Write the samples here instead of standard output (with --sample)."},
         },
         {"scoreFile"});
     std::string err;
@@ -44,6 +57,32 @@ int main(int argc, char **argv) {
                    "Posterior edge and parent-set probabilities by exact model averaging (order-modular prior) on an MI355X.  "
                    "Example usage: posterior iris.pss -o iris_edges.csv");
         return args.has("help") || argc == 1 ? 0 : 2;
+    }
+    long long samples = 0;
+    unsigned long long seed = 0;
+    if (!args.has("sample") && (args.has("seed") || args.has("dags"))) {
+        std::fprintf(stderr, "posterior: --seed and -g need --sample\n");
+        return 2;
+    }
+    if (args.has("sample")) {
+        const std::string k = args.get("sample");
+        char *end = nullptr;
+        errno = 0;
+        samples = std::strtoll(k.c_str(), &end, 10);
+        if (k.empty() || k.find_first_not_of("0123456789") != std::string::npos || errno || *end || samples < 1) {
+            std::fprintf(stderr, "posterior: --sample takes a positive integer, not '%s'\n", k.c_str());
+            return 2;
+        }
+    }
+    if (args.has("seed")) {
+        const std::string t = args.get("seed");
+        char *end = nullptr;
+        errno = 0;
+        seed = std::strtoull(t.c_str(), &end, 10);
+        if (t.empty() || t.find_first_not_of("0123456789") != std::string::npos || errno || *end) {
+            std::fprintf(stderr, "posterior: --seed takes an unsigned 64-bit integer, not '%s'\n", t.c_str());
+            return 2;
+        }
     }
     ulgio::PssData p;
     if (!ulgio::read_pss(args.get("scoreFile"), p, err)) {
@@ -74,6 +113,46 @@ int main(int argc, char **argv) {
         ulg_destroy(ctx);
         return 1;
     }
+    // the samples' lines, drawn and formatted a block at a time: the host buffers do not grow with K
+    std::string sample_text;
+    try {
+        const long long block = 1 << 16;
+        std::vector<uint64_t> s_par;
+        std::vector<uint8_t> s_ord;
+        std::vector<double> s_lw;
+        char num[64];
+        for (long long first = 0; first < samples; first += block) {
+            const long long cnt = std::min(block, samples - first);
+            s_par.resize((size_t)cnt * n);
+            s_ord.resize((size_t)cnt * n);
+            s_lw.resize((size_t)cnt);
+            if (ulg_posterior_sample(ctx, seed, first, cnt, s_par.data(), s_ord.data(), s_lw.data()) != ULG_OK) {
+                std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+                ulg_destroy(ctx);
+                return 1;
+            }
+            for (long long k = 0; k < cnt; ++k) {
+                std::snprintf(num, sizeof num, "%.6f", s_lw[(size_t)k]);
+                sample_text += num;
+                for (int i = 0; i < n; ++i) {
+                    const int v = s_ord[(size_t)k * n + i];
+                    sample_text += " " + p.names[v] + "<-";
+                    const uint64_t pa = s_par[(size_t)k * n + v];
+                    bool firstp = true;
+                    for (int u = 0; u < n; ++u)
+                        if ((pa >> u) & 1ull) {
+                            sample_text += (firstp ? "" : ",") + p.names[u];
+                            firstp = false;
+                        }
+                }
+                sample_text += "\n";
+            }
+        }
+    } catch (const std::exception &) {  // bad_alloc, length_error: the text of K lines does not fit
+        std::fprintf(stderr, "posterior: out of memory for the lines of %lld samples\n", samples);
+        ulg_destroy(ctx);
+        return 1;
+    }
     ulg_destroy(ctx);
     std::printf("ln Z = %.10f\n", log_z);
     std::string text;
@@ -101,6 +180,15 @@ int main(int argc, char **argv) {
             }
         if (!ulgio::write_text(args.get("sets"), text)) {
             std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("sets").c_str());
+            return 1;
+        }
+    }
+    if (samples) {
+        text.swap(sample_text);
+        if (!args.has("dags")) {
+            std::fputs(text.c_str(), stdout);
+        } else if (!ulgio::write_text(args.get("dags"), text)) {
+            std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("dags").c_str());
             return 1;
         }
     }

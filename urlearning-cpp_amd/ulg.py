@@ -92,6 +92,9 @@ def lib():
             L.ulg_posterior.argtypes = [P, I, P, P, P, I, C.POINTER(D), P, P]
             L.ulg_posterior_from_scores.argtypes = [P, C.POINTER(D), P, P]
             L.ulg_posterior_table.argtypes = [P, I, I, P, I64, C.POINTER(I64)]
+        if hasattr(L, "ulg_posterior_sample"):  # ... or from before the sampler
+            L.ulg_posterior_sample.argtypes = [P, C.c_uint64, I64, I64, P, P, P]
+            L.ulg_posterior_sample_u.argtypes = [P, I64, P, P, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -470,8 +473,10 @@ class Context:
         lz = C.c_double()
         edge = np.zeros((max(n, 1), max(n, 1)), dtype=np.float64)
         lp = np.zeros(max(total, 1), dtype=np.float64) if want_sets else None
+        self._post_n = None  # a refused call leaves nothing to sample
         self._check(lib().ulg_posterior(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, C.byref(lz), _ptr(edge),
                                         _ptr(lp) if lp is not None else None), "ulg_posterior")
+        self._post_n = n
         del keep
         return lz.value, edge, (lp[:max(total, 0)] if lp is not None else None)
 
@@ -487,8 +492,10 @@ class Context:
         lz = C.c_double()
         edge = np.zeros((n, n), dtype=np.float64)
         lp = np.zeros(max(total, 1), dtype=np.float64) if want_sets else None
+        self._post_n = None
         self._check(lib().ulg_posterior_from_scores(self._h, C.byref(lz), _ptr(edge),
                                                     _ptr(lp) if lp is not None else None), "ulg_posterior_from_scores")
+        self._post_n = n
         return lz.value, edge, (lp[:total] if lp is not None else None)
 
     def posterior_table(self, which: int, var: int = 0) -> np.ndarray:
@@ -501,6 +508,52 @@ class Context:
         self._check(lib().ulg_posterior_table(self._h, int(which), int(var), _ptr(out), out.size, C.byref(cnt)),
                     "ulg_posterior_table")
         return out
+
+    def _sample_outputs(self, who, count, want_order, want_weight):
+        """The host arrays of `count` samples, n from the last successful posterior call of this object.
+        None where the library must refuse the call itself (no such call, a negative count); arrays that
+        do not fit the host are the caller's error as much as buffers that do not fit the device."""
+        n = getattr(self, "_post_n", None)
+        if n is None or count < 0:
+            return None
+        try:
+            parents = np.zeros((count, n), dtype=np.uint64)
+            order = np.zeros((count, n), dtype=np.uint8) if want_order else None
+            weight = np.zeros(count, dtype=np.float64) if want_weight else None
+        except (MemoryError, ValueError) as e:
+            raise ULGError(f"{who}: status 4: {count} samples of n = {n} do not fit the host memory ({e})") from None
+        return parents, order, weight
+
+    def posterior_sample(self, count, seed=0, first=0, want_order=True, want_weight=True):
+        """ulg_posterior_sample: samples first .. first + count - 1 of `seed` from the order-modular
+        posterior of the last posterior call -> (parents uint64 (count, n): parents[k, v] = the parent
+        mask of v, order uint8 (count, n): order[k, i] = the variable at position i, or None,
+        log_weight float64 (count): the sum of the chosen sets' scores, or None)."""
+        count, first, seed = int(count), int(first), int(seed)
+        out = self._sample_outputs("ulg_posterior_sample", count, want_order, want_weight)
+        if out is None:  # the library's own refusal: state, or a negative count
+            self._check(lib().ulg_posterior_sample(self._h, seed, first, min(count, 0), None, None, None), "ulg_posterior_sample")
+            raise ULGError("ulg_posterior_sample: status 3: the last posterior call through this object was refused")
+        parents, order, weight = out
+        self._check(lib().ulg_posterior_sample(self._h, seed, first, count, _ptr(parents),
+                                               _ptr(order) if want_order else None, _ptr(weight) if want_weight else None),
+                    "ulg_posterior_sample")
+        return parents, order, weight
+
+    def posterior_sample_u(self, u, want_order=True, want_weight=True):
+        """ulg_posterior_sample_u (tests): the same with the draws given, u uint64 (count, n, 2):
+        u[k, i] = (U_sink, U_set) of step position i of sample k."""
+        u = np.ascontiguousarray(u, dtype=np.uint64)
+        out = self._sample_outputs("ulg_posterior_sample_u", int(u.shape[0]) if u.ndim == 3 else 0, want_order, want_weight)
+        if out is None:
+            self._check(lib().ulg_posterior_sample_u(self._h, 0, None, None, None, None), "ulg_posterior_sample_u")
+            raise ULGError("ulg_posterior_sample_u: status 3: the last posterior call through this object was refused")
+        parents, order, weight = out
+        if u.ndim != 3 or u.shape[1:] != (parents.shape[1], 2):
+            raise ULGError(f"posterior_sample_u: u must be (count, {parents.shape[1]}, 2), not {u.shape}")
+        self._check(lib().ulg_posterior_sample_u(self._h, u.shape[0], _ptr(u), _ptr(parents), _ptr(order) if want_order else None,
+                                                 _ptr(weight) if want_weight else None), "ulg_posterior_sample_u")
+        return parents, order, weight
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

@@ -756,6 +756,45 @@ int ulg_posterior_sample(ulg_ctx *ctx, uint64_t seed, int64_t first, int64_t cou
 int ulg_posterior_sample_u(ulg_ctx *ctx, int64_t count, const uint64_t *u, uint64_t *parents,
                            uint8_t *order, double *log_weight);
 
+/* The importance weight that turns those samples into estimates under the
+ * prior uniform over DAGs: the law of a sampled DAG is ext(G) prod_v w_v(Pa_v)
+ * / Z, ext(G) its number of linear extensions (topological orders), so a
+ * sample weighted by 1 / ext(G) stands for prod_v w_v(Pa_v) alone (Ellis &
+ * Wong 2008).  ulg_dag_linear_extensions counts ext(G) exactly for each of
+ * `count` DAGs by the recursion over the subset lattice
+ *   c(0) = 1,  c(S) = sum over v in S with Pa_v subset of S\v of c(S\v),
+ *   ext(G) = c(V):
+ * c(S) is the number of orderings of S in which every member's parents come
+ * first, 0 when S is not closed under parents; hence ext = 0 for a graph with
+ * a directed cycle, which is an answer and not an error.  ext <= n! < 2^98:
+ * the count is a 128-bit unsigned integer, ext_lo[k] + 2^64 ext_hi[k], and the
+ * device adds in two 64-bit words with carry (csrc/linext_dev.h), so every
+ * output is the exact integer whatever the launch geometry or the batching.
+ * parents[k*n + v] = the parent mask of v in DAG k, the layout
+ * ulg_posterior_sample writes.  All pointers are host pointers; ext_hi and
+ * log_ext may be NULL.  log_ext[k] = (double) logl((long double) hi 2^64 +
+ * (long double) lo), formed on the host from the exact words; -inf for 0.
+ * The call needs no loaded data, lists or posterior state and changes none:
+ * ulg_cbic_fetch, ulg_posterior_table and a following ulg_posterior_sample
+ * give what they gave before.
+ * Device memory: 16 * 2^n bytes of table per DAG (n = 20: 16 MB, 25: 512 MB,
+ * 28: 4 GB) plus 4 n + 16 for its masks and result.  The DAGs are processed
+ * in batches: as many per batch as 2^30 bytes of tables hold (1023 at n = 16,
+ * 63 at n = 20, one from n = 25 on) within seven eighths of the free device
+ * memory, one at least; and at most "linext_batch" of them when that option
+ * is positive.  More per batch buys nothing once a launch fills the card, and
+ * a large allocation costs more than the count.  ulg_get_info
+ * ("linext_batches") gives the batches of the last call (0 for count = 0).
+ * The buffers are the call's own and are freed when it returns.
+ * Errors: ULG_ERR_ARG for n < 1, a negative count, a NULL parents or ext_lo
+ * with count > 0, a mask with the variable's own bit or a bit >= n (every
+ * mask is checked before any device work; nothing is written);
+ * ULG_ERR_UNSUPPORTED for n > 28, or when one DAG's table does not fit the
+ * free device memory, decided before anything is allocated.  count = 0
+ * succeeds without device work. */
+int ulg_dag_linear_extensions(ulg_ctx *ctx, int n, int64_t count, const uint64_t *parents,
+                              uint64_t *ext_lo, uint64_t *ext_hi, double *log_ext);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the
@@ -831,6 +870,9 @@ int ulg_posterior_sample_u(ulg_ctx *ctx, int64_t count, const uint64_t *u, uint6
  * "posterior_keep" (0/1, default 0): ulg_posterior* keep every variable's
  * gamma table for ulg_posterior_table instead of reusing one (n - 1 more
  * tables of 2^(n-1) doubles); the outputs are bit-identical either way.
+ * "linext_batch" (>= 0, default 0): ulg_dag_linear_extensions processes at
+ * most this many DAGs per batch; 0 = as many as fit (the rule there).  The
+ * counts are the same integers either way.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -891,6 +933,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * ulg_disc_mmpc performed / left out by its reliability rule),
  * "posterior_bytes" (the device bytes of the last successful ulg_posterior*
  * call's tables, by the formula there; 0 before any),
+ * "linext_batches" (batches the last ulg_dag_linear_extensions ran, option
+ * "linext_batch"),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
  * "lds_image_bytes" (bytes of the last scoring call's launch images),
  * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the

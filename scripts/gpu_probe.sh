@@ -40,6 +40,10 @@
 #               K = 10^5 at the same n = 20 and 25 lists: the call, its kernel
 #               and copy-out, list scans against table gathers, the numpy
 #               walk at n = 16 for scale)               -> posterior_sample.json
+#   linext      scripts/linext_profile.py (ulg_dag_linear_extensions at n = 16,
+#               20 and 25 on sampler output and the empty graph, with and
+#               without dedupe, batch caps, the Python recursion at n = 16,
+#               `posterior --sample 10000 --uniform` at n = 20)  -> linext.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -160,6 +164,9 @@ for step in ${STEPS:-suite smoke bench}; do
       timeout -k 10 300 python3 scripts/posterior_sample_profile.py "$OUT/posterior_sample.json" \
         > "$OUT/posterior_sample.log" 2>&1
       tail -n 1 "$OUT/posterior_sample.log" | cut -c1-900 ;;
+    linext)
+      timeout -k 10 400 python3 scripts/linext_profile.py "$OUT/linext.json" > "$OUT/linext.log" 2>&1
+      tail -n 1 "$OUT/linext.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

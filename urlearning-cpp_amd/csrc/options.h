@@ -48,6 +48,8 @@ struct Options {
     int64_t bge_prune = 0;           // ulg_bge_score: the same pass over the BGe slot table
     // ---- exact model averaging ----
     int64_t posterior_keep = 0;      // ulg_posterior*: keep every variable's gamma table for ulg_posterior_table
+    // ---- linear extensions ----
+    int64_t linext_batch = 0;        // ulg_dag_linear_extensions: at most this many DAGs per batch (0: as many as fit)
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -91,6 +93,7 @@ constexpr OptionRow kOptionRows[] = {
     {"disc_prune", &Options::disc_prune, 0, 1, 0, {}, "0 or 1"},
     {"bge_prune", &Options::bge_prune, 0, 1, 0, {}, "0 or 1"},
     {"posterior_keep", &Options::posterior_keep, 0, 1, 0, {}, "0 or 1"},
+    {"linext_batch", &Options::linext_batch, 0, kOptMax, 0, {}, ">= 0"},
 };
 
 inline const OptionRow *option_row(const char *name) {

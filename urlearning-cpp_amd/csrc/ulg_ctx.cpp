@@ -287,6 +287,11 @@ int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
         *value = c->posterior_bytes;
         return ULG_OK;
     }
+    // batches the last ulg_dag_linear_extensions ran (option "linext_batch")
+    if (std::strcmp(name, "linext_batches") == 0) {
+        *value = c->linext_batches;
+        return ULG_OK;
+    }
     // the fNML regret table of the loaded data (0: not built since the last load)
     if (std::strcmp(name, "fnml_table_bytes") == 0) {
         *value = c->fnml_bytes;

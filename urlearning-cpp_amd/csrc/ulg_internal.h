@@ -180,6 +180,7 @@ struct ulg_ctx : ulg::CtxStreams {
     // ---- exact model averaging (posterior.hip): its lists and tables, apart from everything above ----
     ulg::PosteriorState *posterior = nullptr;
     int64_t posterior_bytes = 0;  // ulg_get_info("posterior_bytes"): the last successful call's tables
+    int64_t linext_batches = 0;   // ulg_get_info("linext_batches"): batches of the last ulg_dag_linear_extensions (linext.hip)
 
     // ---- profiling ----
     bool prof = false;

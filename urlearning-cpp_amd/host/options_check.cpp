@@ -2,8 +2,8 @@
 // what ulg_set_option accepted, refused and defaulted to before the table
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
-// (score_narrow, bge_prune and posterior_keep, added since, are recorded the
-// same way).
+// (score_narrow, bge_prune, posterior_keep and linext_batch, added since, are
+// recorded the same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +69,7 @@ const std::vector<Want> kWant = {
     {"disc_prune", {0, 1}, 0, 0, 0, "0 or 1"},
     {"bge_prune", {0, 1}, 0, 0, 0, "0 or 1"},
     {"posterior_keep", {0, 1}, 0, 0, 0, "0 or 1"},
+    {"linext_batch", {}, 0, kNoMax, 0, ">= 0"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -104,7 +105,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 29);
+    CHECK(kWant.size() == 30);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

@@ -4,7 +4,7 @@
 // counts once per linear extension; not uniform over DAGs).
 //
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
-//             [--sample K [--seed S] [-g dags.txt]]
+//             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -19,21 +19,47 @@
 // the same in every run) and writes one line per sample: "%.6f" of the log
 // weight, then "<name><-<parent>,<parent>" for each variable in the sampled
 // order, separated by spaces; to the file of -g, else to standard output after
-// everything above.  Exit status: 0, 1 for a file or device error, 2 for a bad
-// command line (--seed or -g without --sample and a K that is not a positive
-// integer included).
+// everything above.  --uniform (with --sample) reweights the samples to the
+// prior uniform over DAGs of the stored families: every sample line gains a
+// second field after the log weight, the exact number of linear extensions of
+// its DAG in decimal (ulg_dag_linear_extensions, per block of 2^16 samples with
+// duplicate DAGs removed), and "uniform-prior ESS = %.1f of K" is printed on
+// standard output right after the ln Z line: the effective sample size
+// (sum r)^2 / sum r^2 of the weights r_k = exp(min log_ext - log_ext_k).
+// --uniform-edges FILE (with --uniform) writes sum_k r_k [u in Pa_v^k] / sum_k
+// r_k in -o's format.  The minimum is known only after the last block, so the
+// counts' logarithms and the parent masks are kept and the sums are formed in a
+// second pass over them, in float64 over k ascending: the summation of
+// ulg.uniform_prior_edges (urlearning-cpp_amd/ulg.py) term by term.
+// Exit status: 0, 1 for a file or device error, 2 for a bad command line
+// (--seed, -g or --uniform without --sample, --uniform-edges without --uniform
+// and a K that is not a positive integer included).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/ulg.h"
 #include "cli_common.h"
 #include "io.h"
+
+namespace {
+
+// lo + 2^64 hi in decimal
+std::string decimal128(uint64_t lo, uint64_t hi) {
+    unsigned __int128 x = ((unsigned __int128)hi << 64) | lo;
+    if (x == 0) return "0";
+    std::string out;
+    for (; x != 0; x /= 10) out.insert(out.begin(), (char)('0' + (int)(x % 10)));
+    return out;
+}
+
+}  // namespace
 
 int main(int argc, char **argv) {
     ulgcli::Args args(
@@ -45,6 +71,9 @@ int main(int argc, char **argv) {
             {"", "sample", true, "", "Draw this many (order, DAG) samples from the posterior."},
             {"", "seed", true, "", "The samples' seed (with --sample; 0 without it)."},
             {"g", "dags", true, "", "Write the samples here instead of standard output (with --sample)."},
+            {"", "uniform", false, "", "Reweight the samples to the prior uniform over DAGs: each sample line gains its DAG's "
+                                       "number of linear extensions, and the effective sample size is printed (with --sample)."},
+            {"", "uniform-edges", true, "", "Write the reweighted edge posteriors here, in -o's format (with --uniform)."},
         },
         {"scoreFile"});
     std::string err;
@@ -62,6 +91,11 @@ int main(int argc, char **argv) {
     unsigned long long seed = 0;
     if (!args.has("sample") && (args.has("seed") || args.has("dags"))) {
         std::fprintf(stderr, "posterior: --seed and -g need --sample\n");
+        return 2;
+    }
+    const bool uniform = args.has("uniform");
+    if ((uniform && !args.has("sample")) || (args.has("uniform-edges") && !uniform)) {
+        std::fprintf(stderr, "posterior: --uniform needs --sample, --uniform-edges needs --uniform\n");
         return 2;
     }
     if (args.has("sample")) {
@@ -115,11 +149,17 @@ int main(int argc, char **argv) {
     }
     // the samples' lines, drawn and formatted a block at a time: the host buffers do not grow with K
     std::string sample_text;
+    std::vector<double> all_le;      // --uniform: log_ext of every sample, and
+    std::vector<uint64_t> all_par;   // its parent masks, for the pass that knows the minimum
     try {
         const long long block = 1 << 16;
         std::vector<uint64_t> s_par;
         std::vector<uint8_t> s_ord;
         std::vector<double> s_lw;
+        // --uniform: the block's distinct DAGs and their counts; every sample's log count and masks for the second pass
+        std::vector<uint64_t> u_par, u_lo, u_hi;
+        std::vector<double> u_le;
+        std::vector<size_t> which;
         char num[64];
         for (long long first = 0; first < samples; first += block) {
             const long long cnt = std::min(block, samples - first);
@@ -131,9 +171,33 @@ int main(int argc, char **argv) {
                 ulg_destroy(ctx);
                 return 1;
             }
+            if (uniform) {
+                std::map<std::vector<uint64_t>, size_t> seen;
+                u_par.clear();
+                which.assign((size_t)cnt, 0);
+                for (long long k = 0; k < cnt; ++k) {
+                    std::vector<uint64_t> row(s_par.begin() + (size_t)k * n, s_par.begin() + (size_t)(k + 1) * n);
+                    const auto at = seen.emplace(std::move(row), seen.size());
+                    if (at.second) u_par.insert(u_par.end(), at.first->first.begin(), at.first->first.end());
+                    which[(size_t)k] = at.first->second;
+                }
+                const size_t distinct = seen.size();
+                u_lo.assign(distinct, 0);
+                u_hi.assign(distinct, 0);
+                u_le.assign(distinct, 0.0);
+                if (ulg_dag_linear_extensions(ctx, n, (int64_t)distinct, u_par.data(), u_lo.data(), u_hi.data(), u_le.data()) !=
+                    ULG_OK) {
+                    std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+                    ulg_destroy(ctx);
+                    return 1;
+                }
+                for (long long k = 0; k < cnt; ++k) all_le.push_back(u_le[which[(size_t)k]]);
+                all_par.insert(all_par.end(), s_par.begin(), s_par.end());
+            }
             for (long long k = 0; k < cnt; ++k) {
                 std::snprintf(num, sizeof num, "%.6f", s_lw[(size_t)k]);
                 sample_text += num;
+                if (uniform) sample_text += " " + decimal128(u_lo[which[(size_t)k]], u_hi[which[(size_t)k]]);
                 for (int i = 0; i < n; ++i) {
                     const int v = s_ord[(size_t)k * n + i];
                     sample_text += " " + p.names[v] + "<-";
@@ -157,6 +221,37 @@ int main(int argc, char **argv) {
     std::printf("ln Z = %.10f\n", log_z);
     std::string text;
     char buf[64];
+    if (uniform) {
+        // r_k = exp(min log_ext - log_ext_k); every sum in float64 over k ascending (ulg.uniform_prior_edges)
+        double least = INFINITY;
+        for (double x : all_le) least = std::min(least, x);
+        if (!(least > -INFINITY)) {  // a count of 0: not a sampled DAG
+            std::fprintf(stderr, "posterior: a sample without a linear extension\n");
+            return 1;
+        }
+        double tot = 0.0, tot2 = 0.0;
+        std::vector<double> acc((size_t)n * n, 0.0);
+        for (size_t k = 0; k < all_le.size(); ++k) {
+            const double r = std::exp(least - all_le[k]);
+            tot += r;
+            tot2 += r * r;
+            for (int v = 0; v < n; ++v)
+                for (uint64_t pa = all_par[k * n + v]; pa; pa &= pa - 1) acc[(size_t)__builtin_ctzll(pa) * n + v] += r;
+        }
+        std::printf("uniform-prior ESS = %.1f of %lld\n", tot * tot / tot2, samples);
+        if (args.has("uniform-edges")) {
+            for (int u = 0; u < n; ++u)
+                for (int v = 0; v < n; ++v) {
+                    std::snprintf(buf, sizeof buf, "%.6f%s", acc[(size_t)u * n + v] / tot, v + 1 < n ? "," : "\n");
+                    text += buf;
+                }
+            if (!ulgio::write_text(args.get("uniform-edges"), text)) {
+                std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("uniform-edges").c_str());
+                return 1;
+            }
+            text.clear();
+        }
+    }
     for (int u = 0; u < n; ++u)
         for (int v = 0; v < n; ++v) {
             std::snprintf(buf, sizeof buf, "%.6f%s", edge[(size_t)u * n + v], v + 1 < n ? "," : "\n");

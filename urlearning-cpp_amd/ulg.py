@@ -95,6 +95,8 @@ def lib():
         if hasattr(L, "ulg_posterior_sample"):  # ... or from before the sampler
             L.ulg_posterior_sample.argtypes = [P, C.c_uint64, I64, I64, P, P, P]
             L.ulg_posterior_sample_u.argtypes = [P, I64, P, P, P, P]
+        if hasattr(L, "ulg_dag_linear_extensions"):  # ... or from before the linear-extension count
+            L.ulg_dag_linear_extensions.argtypes = [P, I, I64, P, P, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -120,6 +122,32 @@ def _ptr(a):
 def chi2_log_sf(x: float, dof: float) -> float:
     """ulg_chi2_log_sf: ln of the chi-square survival function (pure host, no GPU)."""
     return lib().ulg_chi2_log_sf(float(x), float(dof))
+
+
+def uniform_prior_edges(parents, log_ext):
+    """Edge posteriors under the prior uniform over DAGs (of the stored families) from samples of
+    the order-modular posterior: the self-normalised importance-sampling estimate with weights
+    1 / ext(G_k).  parents uint64 (K, n) as Context.posterior_sample returns them, log_ext float64
+    (K) from Context.dag_linear_extensions -> (edge float64 (n, n), ess).
+    r_k = exp(min log_ext - log_ext_k); edge[u, v] = sum_k r_k [u in Pa_v^k] / sum_k r_k;
+    ess = (sum r)^2 / sum r^2.  Every sum is a float64 sum over k ascending (np.cumsum, not
+    np.sum's pairwise order), which `posterior --uniform-edges` repeats term by term.  A count of 0
+    (log_ext = -inf) cannot come from the sampler: it raises."""
+    p = np.ascontiguousarray(parents, dtype=np.uint64)
+    le = np.ascontiguousarray(log_ext, dtype=np.float64)
+    if p.ndim != 2 or le.ndim != 1 or p.shape[0] != le.shape[0] or p.shape[0] < 1:
+        raise ULGError(f"uniform_prior_edges: parents (K, n) and log_ext (K) with K >= 1, not {p.shape} and {le.shape}")
+    if not np.all(np.isfinite(le)):
+        raise ULGError("uniform_prior_edges: a sample without a linear extension (log_ext not finite): not a sampled DAG")
+    n = p.shape[1]
+    r = np.exp(le.min() - le)
+    tot = np.cumsum(r)[-1]
+    edge = np.zeros((n, n), dtype=np.float64)
+    for v in range(n):
+        for u in range(n):
+            has = ((p[:, v] >> np.uint64(u)) & np.uint64(1)).astype(np.float64)
+            edge[u, v] = np.cumsum(r * has)[-1] / tot  # r * 0 = 0 and x + 0 = x: the terms of the members alone
+    return edge, float(tot * tot / np.cumsum(r * r)[-1])
 
 
 class Context:
@@ -554,6 +582,30 @@ class Context:
         self._check(lib().ulg_posterior_sample_u(self._h, u.shape[0], _ptr(u), _ptr(parents), _ptr(order) if want_order else None,
                                                  _ptr(weight) if want_weight else None), "ulg_posterior_sample_u")
         return parents, order, weight
+
+    def dag_linear_extensions(self, parents, dedupe=True):
+        """ulg_dag_linear_extensions on parents uint64 (count, n), parents[k, v] = the parent mask of v
+        in DAG k (what posterior_sample returns) -> (ext: a list of Python ints, the exact number of
+        linear extensions of each DAG, 0 for a cyclic one; log_ext float64 (count), -inf for 0).
+        dedupe: the distinct rows only go to the library and their results are scattered back (a
+        peaked posterior repeats DAGs); False is the raw call."""
+        p = np.ascontiguousarray(parents, dtype=np.uint64)
+        if p.ndim != 2 or p.shape[1] < 1:
+            raise ULGError(f"dag_linear_extensions: parents must be (count, n) with n >= 1, not {p.shape}")
+        count, n = p.shape
+        inverse = None
+        if dedupe and count > 1:
+            p, inverse = np.unique(p, axis=0, return_inverse=True)
+            p, inverse = np.ascontiguousarray(p), np.asarray(inverse).reshape(-1)
+        lo = np.zeros(p.shape[0], dtype=np.uint64)
+        hi = np.zeros(p.shape[0], dtype=np.uint64)
+        le = np.zeros(p.shape[0], dtype=np.float64)
+        self._check(lib().ulg_dag_linear_extensions(self._h, n, p.shape[0], _ptr(p), _ptr(lo), _ptr(hi), _ptr(le)),
+                    "ulg_dag_linear_extensions")
+        ext = [(int(h) << 64) | int(l) for l, h in zip(lo, hi)]
+        if inverse is not None:
+            ext, le = [ext[i] for i in inverse], le[inverse]
+        return ext, le
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

@@ -795,6 +795,56 @@ int ulg_posterior_sample_u(ulg_ctx *ctx, int64_t count, const uint64_t *u, uint6
 int ulg_dag_linear_extensions(ulg_ctx *ctx, int n, int64_t count, const uint64_t *parents,
                               uint64_t *ext_lo, uint64_t *ext_hi, double *log_ext);
 
+/* What the samples are for: the features that do not factor over one parent
+ * set, as posterior sample means.  ulg_dag_features reduces a batch of `count`
+ * DAGs (parents[k*n + v] = the parent mask of v in DAG k, the layout above) to
+ * tables of exact integer sums over the ACYCLIC graphs G_k of the batch, each
+ * graph weighted by the integer q_k = weight[k] (weight NULL: every q_k = 1):
+ *   edge[u*n + v]       sum of q_k over the G_k with u in Pa_v
+ *   ancestor[u*n + v]   ... with a directed path of at least one edge from u
+ *                       to v (diagonal 0)
+ *   blanket[u*n + v]    ... with u != v a parent, a child or a parent of a
+ *                       child of v (symmetric)
+ *   compelled[u*n + v]  ... with u in Pa_v and u -> v directed in the
+ *                       essential graph (CPDAG) of G_k: every DAG with G_k's
+ *                       skeleton and v-structures has the edge in this
+ *                       direction.  For a score-equivalent score (BGe, BDeu)
+ *                       the data cannot tell the members of such a class
+ *                       apart, so this, not edge, is the directed statement
+ *                       the data supports.
+ *   vstruct[(v*n + u)*n + w], u < w   ... with u -> v <- w and u, w not
+ *                       adjacent; every other entry 0
+ *   total               sum of q_k over the acyclic graphs
+ *   cyclic              the number (not the weight) of graphs with a directed
+ *                       cycle.  Such a graph contributes to nothing else: an
+ *                       answer, not an error.
+ * A caller divides by total.  The essential graph starts from the edges that
+ * take part in a v-structure and is closed under Meek's rules R1-R3 (R4 is
+ * not needed from a DAG's own v-structures); csrc/dagfeat_dev.h states the
+ * rules row by row and host/dagfeat_check.cpp runs them against the
+ * definition.  One wave64 per DAG, lane v holding row v; the sums are 64-bit
+ * integer adds, so every output is the same to the bit whatever the launch
+ * geometry, the batching or the order of the atomics.
+ * All pointers are host pointers.  Each of edge, ancestor, blanket, compelled
+ * (n*n values) and vstruct (n*n*n) may be NULL: what is not asked for is not
+ * computed.  cyclic may be NULL; total may not.
+ * n <= 63: the call needs no lattice, so the sampler's n <= 28 does not bind
+ * it.  The call needs no loaded data, lists or posterior state and changes
+ * none.  Its device buffers (8 n bytes per DAG in chunks of at most 2^28
+ * bytes, 8 per weight, 8 (4 n^2 + n^3 + 2) of tables) are its own and are
+ * freed when it returns.  Option "dagfeat_grid" sets the workgroups of its
+ * launches; ulg_get_info("dagfeat_grid") gives those of the last call.
+ * Errors: ULG_ERR_ARG for n < 1, a negative count, a NULL parents with
+ * count > 0, a NULL total, a mask with the variable's own bit or a bit >= n,
+ * weights that sum to 2^63 or more (every mask and the sum are checked on the
+ * host before any device work; nothing is written); ULG_ERR_UNSUPPORTED for
+ * n > 63.  count = 0 succeeds without device work and zero-fills the outputs
+ * that were given. */
+int ulg_dag_features(ulg_ctx *ctx, int n, int64_t count, const uint64_t *parents,
+                     const uint64_t *weight, uint64_t *edge, uint64_t *ancestor,
+                     uint64_t *blanket, uint64_t *compelled, uint64_t *vstruct,
+                     uint64_t *total, int64_t *cyclic);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the
@@ -873,6 +923,9 @@ int ulg_dag_linear_extensions(ulg_ctx *ctx, int n, int64_t count, const uint64_t
  * "linext_batch" (>= 0, default 0): ulg_dag_linear_extensions processes at
  * most this many DAGs per batch; 0 = as many as fit (the rule there).  The
  * counts are the same integers either way.
+ * "dagfeat_grid" (0..65536, default 0): the workgroups (of four waves, a DAG
+ * per wave at a time) of ulg_dag_features' launches; 0 = one per four DAGs,
+ * at most 2048.  The tables are the same integers either way.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -935,6 +988,9 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * call's tables, by the formula there; 0 before any),
  * "linext_batches" (batches the last ulg_dag_linear_extensions ran, option
  * "linext_batch"),
+ * "dagfeat_grid" (the workgroups the last ulg_dag_features launched, 0 when
+ * it launched nothing: under this one name the read-back is the last call's
+ * grid, not the option of the same name that asks for it),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
  * "lds_image_bytes" (bytes of the last scoring call's launch images),
  * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the

@@ -44,6 +44,10 @@
 #               20 and 25 on sampler output and the empty graph, with and
 #               without dedupe, batch caps, the Python recursion at n = 16,
 #               `posterior --sample 10000 --uniform` at n = 20)  -> linext.json
+#   dagfeat     scripts/dagfeat_profile.py (ulg_dag_features at n = 16, 20 and
+#               25 on 10^5 sampler draws beside the sampling call itself, the
+#               kernel by events, weights, compelled alone, the grid sweep,
+#               the Python reference on 1,000 DAGs, n = 63 once)  -> dagfeat.json
 # (round 5's scripts/r5_*.sh and r4_probe.sh are these steps now)
 set -eu
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -167,6 +171,9 @@ for step in ${STEPS:-suite smoke bench}; do
     linext)
       timeout -k 10 400 python3 scripts/linext_profile.py "$OUT/linext.json" > "$OUT/linext.log" 2>&1
       tail -n 1 "$OUT/linext.log" | cut -c1-900 ;;
+    dagfeat)
+      timeout -k 10 400 python3 scripts/dagfeat_profile.py "$OUT/dagfeat.json" > "$OUT/dagfeat.log" 2>&1
+      tail -n 1 "$OUT/dagfeat.log" | cut -c1-900 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

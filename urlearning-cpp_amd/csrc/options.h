@@ -50,6 +50,8 @@ struct Options {
     int64_t posterior_keep = 0;      // ulg_posterior*: keep every variable's gamma table for ulg_posterior_table
     // ---- linear extensions ----
     int64_t linext_batch = 0;        // ulg_dag_linear_extensions: at most this many DAGs per batch (0: as many as fit)
+    // ---- structural features ----
+    int64_t dagfeat_grid = 0;        // ulg_dag_features: workgroups of its launches (0: the default rule)
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -94,6 +96,7 @@ constexpr OptionRow kOptionRows[] = {
     {"bge_prune", &Options::bge_prune, 0, 1, 0, {}, "0 or 1"},
     {"posterior_keep", &Options::posterior_keep, 0, 1, 0, {}, "0 or 1"},
     {"linext_batch", &Options::linext_batch, 0, kOptMax, 0, {}, ">= 0"},
+    {"dagfeat_grid", &Options::dagfeat_grid, 0, 65536, 0, {}, "0..65536"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -181,6 +181,7 @@ struct ulg_ctx : ulg::CtxStreams {
     ulg::PosteriorState *posterior = nullptr;
     int64_t posterior_bytes = 0;  // ulg_get_info("posterior_bytes"): the last successful call's tables
     int64_t linext_batches = 0;   // ulg_get_info("linext_batches"): batches of the last ulg_dag_linear_extensions (linext.hip)
+    int64_t dagfeat_grid = 0;     // ulg_get_info("dagfeat_grid"): workgroups of the last ulg_dag_features' first launch (dagfeat.hip)
 
     // ---- profiling ----
     bool prof = false;

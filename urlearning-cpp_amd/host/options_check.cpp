@@ -2,8 +2,8 @@
 // what ulg_set_option accepted, refused and defaulted to before the table
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
-// (score_narrow, bge_prune, posterior_keep and linext_batch, added since, are
-// recorded the same way).
+// (score_narrow, bge_prune, posterior_keep, linext_batch and dagfeat_grid,
+// added since, are recorded the same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +70,7 @@ const std::vector<Want> kWant = {
     {"bge_prune", {0, 1}, 0, 0, 0, "0 or 1"},
     {"posterior_keep", {0, 1}, 0, 0, 0, "0 or 1"},
     {"linext_batch", {}, 0, kNoMax, 0, ">= 0"},
+    {"dagfeat_grid", {}, 0, 65536, 0, "0..65536"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -105,7 +106,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 30);
+    CHECK(kWant.size() == 31);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

@@ -4,7 +4,8 @@
 // counts once per linear extension; not uniform over DAGs).
 //
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
-//             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]]
+//             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]
+//              [--paths FILE] [--blankets FILE] [--compelled FILE] [--vstructs FILE]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -31,9 +32,21 @@
 // counts' logarithms and the parent masks are kept and the sums are formed in a
 // second pass over them, in float64 over k ascending: the summation of
 // ulg.uniform_prior_edges (urlearning-cpp_amd/ulg.py) term by term.
+// --paths, --blankets, --compelled FILE (with --sample) write the sample means
+// of the features that do not factor over one parent set, each in -o's
+// format: row u column v = the estimate of p(u ~> v) (a directed path), of
+// p(u in the Markov blanket of v), and of p(u -> v is compelled: directed in
+// the essential graph of the sampled DAG, the directed statement a
+// score-equivalent score supports).  --vstructs FILE writes one line
+// "<name_u> -> <name_v> <- <name_w> %.6f" per v-structure that occurs, sorted
+// by (v, u, w).  All four come from one ulg_dag_features call over all K
+// samples: exact integer tables, divided by their total as doubles.  Without
+// --uniform every sample weighs 1; with it sample k weighs the integer
+// floor(r_k 2^B), B = min(52, 62 - ceil(log2 K)): ulg.uniform_prior_weights
+// term by term.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
-// (--seed, -g or --uniform without --sample, --uniform-edges without --uniform
-// and a K that is not a positive integer included).
+// (--seed, -g, --uniform or a feature file without --sample, --uniform-edges
+// without --uniform and a K that is not a positive integer included).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -42,6 +55,7 @@
 #include <exception>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ulg.h"
@@ -74,6 +88,12 @@ int main(int argc, char **argv) {
             {"", "uniform", false, "", "Reweight the samples to the prior uniform over DAGs: each sample line gains its DAG's "
                                        "number of linear extensions, and the effective sample size is printed (with --sample)."},
             {"", "uniform-edges", true, "", "Write the reweighted edge posteriors here, in -o's format (with --uniform)."},
+            {"", "paths", true, "", "Write the sampled p(u ~> v), a directed path from u to v, here in -o's format (with --sample)."},
+            {"", "blankets", true, "", "Write the sampled p(u in the Markov blanket of v) here in -o's format (with --sample)."},
+            {"", "compelled", true, "", "Write the sampled p(u -> v is directed in the essential graph) here in -o's format "
+                                        "(with --sample)."},
+            {"", "vstructs", true, "", "Write the sampled p(u -> v <- w, u and w not adjacent) here, a line per triple that "
+                                       "occurs (with --sample)."},
         },
         {"scoreFile"});
     std::string err;
@@ -96,6 +116,13 @@ int main(int argc, char **argv) {
     const bool uniform = args.has("uniform");
     if ((uniform && !args.has("sample")) || (args.has("uniform-edges") && !uniform)) {
         std::fprintf(stderr, "posterior: --uniform needs --sample, --uniform-edges needs --uniform\n");
+        return 2;
+    }
+    const char *const feature_flags[4] = {"paths", "blankets", "compelled", "vstructs"};
+    bool features = false;
+    for (const char *f : feature_flags) features = features || args.has(f);
+    if (features && !args.has("sample")) {
+        std::fprintf(stderr, "posterior: --paths, --blankets, --compelled and --vstructs need --sample\n");
         return 2;
     }
     if (args.has("sample")) {
@@ -150,7 +177,10 @@ int main(int argc, char **argv) {
     // the samples' lines, drawn and formatted a block at a time: the host buffers do not grow with K
     std::string sample_text;
     std::vector<double> all_le;      // --uniform: log_ext of every sample, and
-    std::vector<uint64_t> all_par;   // its parent masks, for the pass that knows the minimum
+    std::vector<uint64_t> all_par;   // its parent masks, for the pass that knows the minimum; also kept for the feature files
+    // the feature files: tables of ulg_dag_features over all K samples (ancestor, blanket, compelled: n x n; v-structures: n^3)
+    std::vector<uint64_t> f_anc, f_blanket, f_compelled, f_vs;
+    uint64_t f_total = 0;
     try {
         const long long block = 1 << 16;
         std::vector<uint64_t> s_par;
@@ -192,8 +222,8 @@ int main(int argc, char **argv) {
                     return 1;
                 }
                 for (long long k = 0; k < cnt; ++k) all_le.push_back(u_le[which[(size_t)k]]);
-                all_par.insert(all_par.end(), s_par.begin(), s_par.end());
             }
+            if (uniform || features) all_par.insert(all_par.end(), s_par.begin(), s_par.end());
             for (long long k = 0; k < cnt; ++k) {
                 std::snprintf(num, sizeof num, "%.6f", s_lw[(size_t)k]);
                 sample_text += num;
@@ -210,6 +240,33 @@ int main(int argc, char **argv) {
                         }
                 }
                 sample_text += "\n";
+            }
+        }
+        if (features) {
+            // --uniform: q_k = floor(exp(min log_ext - log_ext_k) 2^B), ulg.uniform_prior_weights; a count of 0 is
+            // refused below, after the ln Z line, as without the feature files
+            std::vector<uint64_t> q;
+            double least = INFINITY;
+            for (double x : all_le) least = std::min(least, x);
+            if (uniform && least > -INFINITY) {
+                int ceil_log2 = 0;
+                while ((1ull << ceil_log2) < (unsigned long long)samples) ++ceil_log2;
+                const int bits = std::min(52, 62 - ceil_log2);
+                for (double x : all_le) q.push_back((uint64_t)std::floor(std::ldexp(std::exp(least - x), bits)));
+            }
+            if (!uniform || !q.empty()) {
+                if (args.has("paths")) f_anc.resize((size_t)n * n);
+                if (args.has("blankets")) f_blanket.resize((size_t)n * n);
+                if (args.has("compelled")) f_compelled.resize((size_t)n * n);
+                if (args.has("vstructs")) f_vs.resize((size_t)n * n * n);
+                if (ulg_dag_features(ctx, n, samples, all_par.data(), uniform ? q.data() : nullptr, nullptr,
+                                     f_anc.empty() ? nullptr : f_anc.data(), f_blanket.empty() ? nullptr : f_blanket.data(),
+                                     f_compelled.empty() ? nullptr : f_compelled.data(), f_vs.empty() ? nullptr : f_vs.data(),
+                                     &f_total, nullptr) != ULG_OK) {
+                    std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+                    ulg_destroy(ctx);
+                    return 1;
+                }
             }
         }
     } catch (const std::exception &) {  // bad_alloc, length_error: the text of K lines does not fit
@@ -276,6 +333,39 @@ int main(int argc, char **argv) {
         if (!ulgio::write_text(args.get("sets"), text)) {
             std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("sets").c_str());
             return 1;
+        }
+    }
+    if (features) {
+        const double tot = (double)f_total;
+        const std::pair<const char *, const std::vector<uint64_t> *> square[3] = {
+            {"paths", &f_anc}, {"blankets", &f_blanket}, {"compelled", &f_compelled}};
+        for (const auto &t : square) {
+            if (!args.has(t.first)) continue;
+            text.clear();
+            for (int u = 0; u < n; ++u)
+                for (int v = 0; v < n; ++v) {
+                    std::snprintf(buf, sizeof buf, "%.6f%s", (double)(*t.second)[(size_t)u * n + v] / tot, v + 1 < n ? "," : "\n");
+                    text += buf;
+                }
+            if (!ulgio::write_text(args.get(t.first), text)) {
+                std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get(t.first).c_str());
+                return 1;
+            }
+        }
+        if (args.has("vstructs")) {
+            text.clear();
+            for (int v = 0; v < n; ++v)
+                for (int u = 0; u < n; ++u)
+                    for (int w = u + 1; w < n; ++w) {
+                        const uint64_t x = f_vs[((size_t)v * n + u) * n + w];
+                        if (!x) continue;
+                        std::snprintf(buf, sizeof buf, " %.6f\n", (double)x / tot);
+                        text += p.names[u] + " -> " + p.names[v] + " <- " + p.names[w] + buf;
+                    }
+            if (!ulgio::write_text(args.get("vstructs"), text)) {
+                std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("vstructs").c_str());
+                return 1;
+            }
         }
     }
     if (samples) {

@@ -97,6 +97,8 @@ def lib():
             L.ulg_posterior_sample_u.argtypes = [P, I64, P, P, P, P]
         if hasattr(L, "ulg_dag_linear_extensions"):  # ... or from before the linear-extension count
             L.ulg_dag_linear_extensions.argtypes = [P, I, I64, P, P, P, P]
+        if hasattr(L, "ulg_dag_features"):  # ... or from before the structural features
+            L.ulg_dag_features.argtypes = [P, I, I64, P, P, P, P, P, P, P, C.POINTER(C.c_uint64), C.POINTER(I64)]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -148,6 +150,25 @@ def uniform_prior_edges(parents, log_ext):
             has = ((p[:, v] >> np.uint64(u)) & np.uint64(1)).astype(np.float64)
             edge[u, v] = np.cumsum(r * has)[-1] / tot  # r * 0 = 0 and x + 0 = x: the terms of the members alone
     return edge, float(tot * tot / np.cumsum(r * r)[-1])
+
+
+def uniform_prior_weights(log_ext):
+    """The integer form of uniform_prior_edges' weights, for Context.dag_features: log_ext float64 (K)
+    from Context.dag_linear_extensions -> q uint64 (K), q_k = floor(r_k 2^B) with
+    r_k = exp(min log_ext - log_ext_k) <= 1 and B = min(52, 62 - ceil(log2 K)), so that
+    sum q <= K 2^B < 2^63, the limit of ulg_dag_features.  A sample whose weight is below 2^-B of
+    the largest gets q = 0 and drops out of every table and of `total`.  A count of 0
+    (log_ext not finite) cannot come from the sampler: it raises."""
+    le = np.ascontiguousarray(log_ext, dtype=np.float64)
+    if le.ndim != 1 or le.shape[0] < 1:
+        raise ULGError(f"uniform_prior_weights: log_ext (K) with K >= 1, not {le.shape}")
+    if not np.all(np.isfinite(le)):
+        raise ULGError("uniform_prior_weights: a sample without a linear extension (log_ext not finite): not a sampled DAG")
+    bits = min(52, 62 - (le.shape[0] - 1).bit_length())  # (K - 1).bit_length() = ceil(log2 K)
+    return np.floor(np.ldexp(np.exp(le.min() - le), bits)).astype(np.uint64)
+
+
+DAG_FEATURES = ("edge", "ancestor", "blanket", "compelled", "vstruct")
 
 
 class Context:
@@ -606,6 +627,33 @@ class Context:
         if inverse is not None:
             ext, le = [ext[i] for i in inverse], le[inverse]
         return ext, le
+
+    def dag_features(self, parents, weight=None, want=DAG_FEATURES):
+        """ulg_dag_features on parents uint64 (count, n) (what posterior_sample returns) and integer
+        weights uint64 (count) (None: every weight 1; uniform_prior_weights gives those of the uniform
+        prior) -> dict: for each name of `want`, the exact sum over the acyclic graphs of the batch as a
+        uint64 array -- "edge", "ancestor", "blanket", "compelled" (n, n), entry [u, v]; "vstruct"
+        (n, n, n), entry [v, u, w] with u < w -- plus "total" (the weight of the acyclic graphs) and
+        "cyclic" (the number of cyclic ones) as Python ints.  An estimate is table / total."""
+        p = np.ascontiguousarray(parents, dtype=np.uint64)
+        if p.ndim != 2 or p.shape[1] < 1:
+            raise ULGError(f"dag_features: parents must be (count, n) with n >= 1, not {p.shape}")
+        count, n = p.shape
+        w = None
+        if weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.uint64)
+            if w.shape != (count,):
+                raise ULGError(f"dag_features: weight must be ({count},), not {w.shape}")
+        unknown = [name for name in want if name not in DAG_FEATURES]
+        if unknown:
+            raise ULGError(f"dag_features: unknown features {unknown}; known: {DAG_FEATURES}")
+        out = {name: np.zeros((n, n, n) if name == "vstruct" else (n, n), dtype=np.uint64) for name in want}
+        total, cyclic = C.c_uint64(0), C.c_int64(0)
+        self._check(lib().ulg_dag_features(self._h, n, count, _ptr(p), None if w is None else _ptr(w),
+                                           *[_ptr(out[name]) if name in out else None for name in DAG_FEATURES],
+                                           C.byref(total), C.byref(cyclic)), "ulg_dag_features")
+        out["total"], out["cyclic"] = int(total.value), int(cyclic.value)
+        return out
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

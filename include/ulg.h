@@ -845,6 +845,112 @@ int ulg_dag_features(ulg_ctx *ctx, int n, int64_t count, const uint64_t *parents
                      uint64_t *blanket, uint64_t *compelled, uint64_t *vstruct,
                      uint64_t *total, int64_t *cyclic);
 
+/* Order MCMC (Friedman & Koller 2003): the same posterior past the lattice's
+ * n <= 28.  A Metropolis-Hastings chain over linear orders whose stationary
+ * law is the order marginal of the model above,
+ *   p(<) proportional to prod_v A_v(pred_<(v)),  A_v(U) = sum_{stored P subset of U} w_v(P),
+ * and, given an order, the sampler's second step: P with probability
+ * w_v(P) / A_v(U).  A record is then an (order, DAG) pair from the
+ * order-modular posterior in ulg_posterior_sample's layout, approximately and
+ * with correlation along a chain -- what R-hat and the acceptance rate are
+ * read for -- where ulg_posterior_sample's draws are exact and independent.
+ * No table: memory is the lists plus O(n) per chain, 1 <= n <= 63.
+ * Input: per-variable lists (offsets[n+1], sets, scores), ulg_posterior's
+ * layout and validation (device_ptrs as there).
+ *   order term  for variable v with predecessor set U, a_v(U) = ln A_v(U), a
+ *              fixed function of (v's list, U) made in integers:
+ *              m = the maximum of (double) s_i over the compatible entries
+ *              (P_i subset of U); none: a = -inf.  q_i = floor(exp((double) s_i
+ *              - m) 2^52) for a compatible entry (the sampler's weight,
+ *              csrc/posterior_sample_dev.h), 0 otherwise.  T = sum q_i as an
+ *              exact 128-bit integer, two 64-bit words with carry
+ *              (csrc/linext_dev.h's add): more than 4096 near-maximal entries
+ *              pass 2^64.  y = ldexp((double) T_hi, 12) + ldexp((double) T_lo,
+ *              -52), a = m + log(y).  A single compatible entry gives exactly
+ *              (double) s.  Integer sums have no order: a term does not
+ *              depend on lanes, waves or grid.
+ *   draws      Philox4x32-10 as above, key (lo32(seed), hi32(seed)), counter
+ *              (lo32(t), hi32(t), c, d): c the chain, t the global step index
+ *              (steps are 1, 2, ...), d a domain.
+ *              initial order (none given): t = 0.  From the identity, for
+ *                p = n-1 down to 1: the draw with d = p, r = mulhi32(w0, p+1)
+ *                (the high 32 bits of the product), positions p and r swapped.
+ *              move of step t: d = 0.  i = mulhi32(w0, n), j' = mulhi32(w1,
+ *                n-1), j = j' + (j' >= i); U_acc = w2 | w3 << 32.  The
+ *                proposal swaps positions i and j (symmetric).  n = 1: nothing
+ *                is proposed, the step counts as rejected.
+ *              parent set of position p of a record at step t: d = 1 + p,
+ *                U_set = w0 | w1 << 32.
+ *   acceptance lo = min(i, j), hi = max(i, j); the terms of positions lo..hi
+ *              are recomputed as a'_p.  delta = (sum_{p = lo..hi ascending}
+ *              a'_p) - (sum_{p = lo..hi ascending} a_p), FP64 in that order.
+ *              Rejected if any a'_p = -inf (delta is then -inf); else
+ *              accepted if delta >= 0; else iff (U_acc >> 12) <
+ *              floor(exp(delta) 2^52).
+ *   records    after every step t with t mod thin = 0 a chain records its
+ *              order, log_score = sum_{p ascending} a_p (the full sum) and,
+ *              if asked, a DAG: for the variable v at each position p,
+ *              x_i = (double) s_i - a_p over v's entries in list order, 0 for
+ *              an incompatible one, q = floor(exp(x_i) 2^52), then the
+ *              sampler's pick with U_set.  log_weight = sum over v ascending
+ *              of (double) s_v(Pa_v).  Record r (0-based within the call) of
+ *              chain c has index idx = r chains + c: order[idx n + p],
+ *              log_score[idx], parents[idx n + v], log_weight[idx].
+ * Hence chain c depends on (lists, seed, c, its initial order) alone -- not
+ * on the number of chains, the launch geometry (option "mcmc_waves"), the
+ * steps per launch ("mcmc_launch_steps") or how steps are split over calls:
+ * run(a); run(b) equals run(a + b) bit for bit, records included (whether a
+ * record is taken depends on the global t).
+ * ulg_order_mcmc_begin copies the lists to the device, checks them there,
+ * sets every chain's order (init_order: chains*n bytes, row c = chain c's
+ * order, position 0 first; NULL: the shuffle above) and terms, step = 0.
+ * ulg_order_mcmc_begin_from_scores: the lists of the last scoring call, as
+ * ulg_posterior_from_scores takes them.
+ * ulg_order_mcmc_run advances every chain by `steps`.  With t0 the steps done
+ * before the call, *records = floor((t0 + steps) / thin) - floor(t0 / thin)
+ * records per chain; the caller sizes order (records chains n bytes),
+ * log_score and log_weight (records chains doubles) and parents (records
+ * chains n masks) by it (t0: ulg_order_mcmc_state).  accepted[c] = chain c's
+ * accepted moves since begin.  trace_delta / trace_accept (tests): delta and
+ * the decision (1 accepted) of step t at [(t - t0 - 1) chains + c], steps x
+ * chains entries; for n = 1 delta reads -inf.  Every output is a host
+ * pointer and may be NULL (what is not asked for is not computed; log_weight
+ * without parents is ULG_ERR_ARG).
+ * ulg_order_mcmc_state: order (chains n bytes), terms (chains n doubles,
+ * terms[c n + p] = a of position p) and *step as they stand; each may be NULL.
+ * ulg_order_score: terms[k n + p] = a of position p of order k (orders: count
+ * n bytes, each a permutation) on the lists of the last begin -- the same
+ * device function, the same bits.
+ * The state -- the lists' device copy and per chain the order, terms and
+ * accepted count, a struct of its own beside the model averaging's -- is kept
+ * until the next begin; a ulg_posterior* call frees it before it sizes its
+ * tables, as it frees the sampler's buffers.  Every begin ends the chains of
+ * the one before, a refused begin too, whatever it is refused for: after it
+ * run, state and score are ULG_ERR_STATE until a begin succeeds (a refused run
+ * or score leaves the chains as they were).  None of these calls touches the
+ * posterior tables, the context's lists or the search state.
+ * Errors: ULG_ERR_UNSUPPORTED for n > 63, and, decided before anything is
+ * allocated, when the buffers (lists 12 B per entry and 16 B per entry for
+ * the duplicate check, 9 n + 8 B per chain; a run's records and traces) do
+ * not fit the free device memory.  ULG_ERR_ARG for n < 1, chains outside
+ * 1..2^20, offsets not ascending, a set with its own variable's bit or a bit
+ * >= n, a duplicate set, a NaN or infinite score, an init_order (or orders)
+ * row that is not a permutation, a chain whose initial order has a -inf term
+ * (an order of probability 0; the message names the chain), steps < 0,
+ * thin < 1.  ULG_ERR_STATE for run, state or score without a successful
+ * begin before it. */
+int ulg_order_mcmc_begin(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
+                         const float *scores, int device_ptrs, int64_t chains, uint64_t seed,
+                         const uint8_t *init_order);
+int ulg_order_mcmc_begin_from_scores(ulg_ctx *ctx, int64_t chains, uint64_t seed,
+                                     const uint8_t *init_order);
+int ulg_order_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *order,
+                       double *log_score, uint64_t *parents, double *log_weight,
+                       int64_t *accepted, double *trace_delta, uint8_t *trace_accept,
+                       int64_t *records);
+int ulg_order_mcmc_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *step);
+int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the
@@ -926,6 +1032,11 @@ int ulg_dag_features(ulg_ctx *ctx, int n, int64_t count, const uint64_t *parents
  * "dagfeat_grid" (0..65536, default 0): the workgroups (of four waves, a DAG
  * per wave at a time) of ulg_dag_features' launches; 0 = one per four DAGs,
  * at most 2048.  The tables are the same integers either way.
+ * "mcmc_waves" (1, 2, 4 or 8; default 4): the waves of the workgroup that
+ * runs one chain of ulg_order_mcmc_run; they share the positions a move
+ * affects.  "mcmc_launch_steps" (>= 1, default 4096): the steps one launch of
+ * it runs at most; the host loops launches over the chains' device state, so
+ * no launch is unbounded.  Neither changes a bit of any output.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU

@@ -52,6 +52,9 @@ struct Options {
     int64_t linext_batch = 0;        // ulg_dag_linear_extensions: at most this many DAGs per batch (0: as many as fit)
     // ---- structural features ----
     int64_t dagfeat_grid = 0;        // ulg_dag_features: workgroups of its launches (0: the default rule)
+    // ---- order MCMC ----
+    int64_t mcmc_waves = 4;          // ulg_order_mcmc_run: waves of the workgroup that runs one chain
+    int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -97,6 +100,8 @@ constexpr OptionRow kOptionRows[] = {
     {"posterior_keep", &Options::posterior_keep, 0, 1, 0, {}, "0 or 1"},
     {"linext_batch", &Options::linext_batch, 0, kOptMax, 0, {}, ">= 0"},
     {"dagfeat_grid", &Options::dagfeat_grid, 0, 65536, 0, {}, "0..65536"},
+    {"mcmc_waves", &Options::mcmc_waves, 0, 0, 4, {1, 2, 4, 8}, "1, 2, 4 or 8"},
+    {"mcmc_launch_steps", &Options::mcmc_launch_steps, 1, kOptMax, 0, {}, ">= 1"},
 };
 
 inline const OptionRow *option_row(const char *name) {

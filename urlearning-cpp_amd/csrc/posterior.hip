@@ -399,6 +399,7 @@ int refuse_size(ulg_ctx *c, const char *who, int n, int64_t total) {
         return set_err(c, ULG_ERR_UNSUPPORTED, buf);
     }
     if (c->posterior) c->posterior->drop_samples();  // the sampler's buffers of an earlier call give way to the tables
+    order_mcmc_delete(c);                            // ... as does the order MCMC's state (order_mcmc.hip)
     size_t free_b = 0, total_b = 0;
     ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
     const double need = table_bytes(n, keep ? n : 1) + 28.0 * (double)total + 8.0 * n * n + 8.0 * (n + 1) + 256.0;

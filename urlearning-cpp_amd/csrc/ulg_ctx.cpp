@@ -157,6 +157,7 @@ ulg_ctx::~ulg_ctx() {
     }
     ulg::pss_delete(this);
     ulg::posterior_delete(this);
+    ulg::order_mcmc_delete(this);
     delete search;
 }
 

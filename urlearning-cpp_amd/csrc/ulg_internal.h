@@ -24,6 +24,7 @@ constexpr uint32_t kAbsentBits = 0xFFFFFFFFu;  // "not in the FloatMap" sentinel
 struct SearchState;
 struct PssState;
 struct PosteriorState;
+struct OrderMcmcState;
 
 struct ProfRec {
     std::string name;
@@ -183,6 +184,9 @@ struct ulg_ctx : ulg::CtxStreams {
     int64_t linext_batches = 0;   // ulg_get_info("linext_batches"): batches of the last ulg_dag_linear_extensions (linext.hip)
     int64_t dagfeat_grid = 0;     // ulg_get_info("dagfeat_grid"): workgroups of the last ulg_dag_features' first launch (dagfeat.hip)
 
+    // ---- order MCMC (order_mcmc.hip): its lists and chains, apart from the model averaging's ----
+    ulg::OrderMcmcState *mcmc = nullptr;
+
     // ---- profiling ----
     bool prof = false;
     std::vector<ulg::ProfRec> pending;
@@ -221,6 +225,7 @@ void prof_collect(ulg_ctx *c);  // after a stream sync
 void graph_reset(ulg_ctx *c);   // drop the captured scoring graph (cbic.hip)
 void pss_delete(ulg_ctx *c);   // delete the context's PssState (pss.hip, where the type is complete)
 void posterior_delete(ulg_ctx *c);  // ... and its PosteriorState (posterior.hip)
+void order_mcmc_delete(ulg_ctx *c);  // ... and its OrderMcmcState (order_mcmc.hip)
 
 // binomial table C(a, b), a < 64, b < kBinomK, clamped to uint32
 const std::vector<uint32_t> &host_binom();

@@ -2,8 +2,8 @@
 // what ulg_set_option accepted, refused and defaulted to before the table
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
-// (score_narrow, bge_prune, posterior_keep, linext_batch and dagfeat_grid,
-// added since, are recorded the same way).
+// (score_narrow, bge_prune, posterior_keep, linext_batch, dagfeat_grid,
+// mcmc_waves and mcmc_launch_steps, added since, are recorded the same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
 #include <cstdlib>
@@ -71,6 +71,8 @@ const std::vector<Want> kWant = {
     {"posterior_keep", {0, 1}, 0, 0, 0, "0 or 1"},
     {"linext_batch", {}, 0, kNoMax, 0, ">= 0"},
     {"dagfeat_grid", {}, 0, 65536, 0, "0..65536"},
+    {"mcmc_waves", {1, 2, 4, 8}, 0, 0, 4, "1, 2, 4 or 8"},
+    {"mcmc_launch_steps", {}, 1, kNoMax, 4096, ">= 1"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -106,7 +108,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 31);
+    CHECK(kWant.size() == 33);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

@@ -5,7 +5,8 @@
 //
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
 //             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]
-//              [--paths FILE] [--blankets FILE] [--compelled FILE] [--vstructs FILE]]
+//              [--paths FILE] [--blankets FILE] [--compelled FILE] [--vstructs FILE]
+//              [--mcmc [--chains C] [--burn B] [--thin T]]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -44,9 +45,27 @@
 // --uniform every sample weighs 1; with it sample k weighs the integer
 // floor(r_k 2^B), B = min(52, 62 - ceil(log2 K)): ulg.uniform_prior_weights
 // term by term.
+// --mcmc (with --sample) takes the K samples from order MCMC
+// (ulg_order_mcmc_*) and not from the exact tables, which end at 28
+// variables: no exact call is made and no ln Z line printed; n <= 63.  C chains
+// (--chains, default 256) run B steps unrecorded (--burn, default 5000), then
+// on until each has R = ceil(K / C) records, one after every step t that is a
+// multiple of T (--thin, default 100; t counts from the start, so a chain makes
+// T (floor(B / T) + R) steps in all); record r of chain c is sample r C + c and
+// the first K are used.  The defaults are untuned starting points: the line
+//   order MCMC: C chains, <steps> steps each, acceptance = %.3f, R-hat(log score) = %.3f
+// printed in the ln Z line's place is what to read (R-hat: Gelman-Rubin over
+// the recorded chains' log scores, ulg.order_rhat term by term; "n/a" for
+// fewer than 2 records or chains).  The sample lines, -g, --uniform (its own
+// n <= 28 still holds) and the feature files are as above; the edge matrix
+// (-o, else standard output) is then the samples' mean edge frequency from
+// the same ulg_dag_features call, weighted as the feature files are.  -s has
+// no counterpart and is refused with --mcmc.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
-// (--seed, -g, --uniform or a feature file without --sample, --uniform-edges
-// without --uniform and a K that is not a positive integer included).
+// (--seed, -g, --uniform, --mcmc or a feature file without --sample,
+// --uniform-edges without --uniform, --chains, --burn or --thin without
+// --mcmc, -s with it, a K that is not a positive integer, and --thin, --burn
+// and K / C that together pass 2^62 steps per chain included).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -54,6 +73,7 @@
 #include <cstdlib>
 #include <exception>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -79,7 +99,8 @@ int main(int argc, char **argv) {
     ulgcli::Args args(
         {
             {"h", "help", false, "", "Show this help message."},
-            {"o", "edges", true, "", "Write the edge posteriors here (csv, row u column v = p(u -> v))."},
+            {"o", "edges", true, "", "Write the edge posteriors here (csv, row u column v = p(u -> v)); with --mcmc, the "
+                                     "samples' mean edge frequencies."},
             {"s", "sets", true, "", "Write the posterior of every stored parent set here."},
             {"d", "device", true, "0", "The GPU to use."},
             {"", "sample", true, "", "Draw this many (order, DAG) samples from the posterior."},
@@ -94,6 +115,12 @@ int main(int argc, char **argv) {
                                         "(with --sample)."},
             {"", "vstructs", true, "", "Write the sampled p(u -> v <- w, u and w not adjacent) here, a line per triple that "
                                        "occurs (with --sample)."},
+            {"", "mcmc", false, "", "Take the samples from order MCMC instead of the exact tables: up to 63 variables, no ln Z "
+                                    "(with --sample; not with -s)."},
+            {"", "chains", true, "", "The number of chains, 1..1048576 (with --mcmc; default 256, an untuned starting point: "
+                                     "read the R-hat that is printed)."},
+            {"", "burn", true, "", "Steps every chain makes before its first record (with --mcmc; default 5000, untuned)."},
+            {"", "thin", true, "", "A record after every this many steps (with --mcmc; default 100, untuned)."},
         },
         {"scoreFile"});
     std::string err;
@@ -125,6 +152,34 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "posterior: --paths, --blankets, --compelled and --vstructs need --sample\n");
         return 2;
     }
+    const bool mcmc = args.has("mcmc");
+    if (mcmc && (!args.has("sample") || args.has("sets"))) {
+        std::fprintf(stderr, "posterior: --mcmc needs --sample and does not go with -s\n");
+        return 2;
+    }
+    if (!mcmc && (args.has("chains") || args.has("burn") || args.has("thin"))) {
+        std::fprintf(stderr, "posterior: --chains, --burn and --thin need --mcmc\n");
+        return 2;
+    }
+    long long chains = 256, burn = 5000, thin = 100;
+    {
+        const struct {
+            const char *name;
+            long long *value, least, most;
+        } ints[3] = {{"chains", &chains, 1, 1 << 20}, {"burn", &burn, 0, 1ll << 40}, {"thin", &thin, 1, 1ll << 40}};
+        for (const auto &o : ints) {
+            if (!args.has(o.name)) continue;
+            const std::string t = args.get(o.name);
+            char *end = nullptr;
+            errno = 0;
+            *o.value = std::strtoll(t.c_str(), &end, 10);
+            if (t.empty() || t.find_first_not_of("0123456789") != std::string::npos || errno || *end || *o.value < o.least ||
+                *o.value > o.most) {
+                std::fprintf(stderr, "posterior: --%s takes an integer %lld..%lld, not '%s'\n", o.name, o.least, o.most, t.c_str());
+                return 2;
+            }
+        }
+    }
     if (args.has("sample")) {
         const std::string k = args.get("sample");
         char *end = nullptr;
@@ -144,6 +199,12 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "posterior: --seed takes an unsigned 64-bit integer, not '%s'\n", t.c_str());
             return 2;
         }
+    }
+    // --mcmc: every chain makes thin (floor(burn / thin) + ceil(samples / chains)) steps; kept below 2^62
+    const long long mcmc_recs = samples / chains + (samples % chains != 0 ? 1 : 0);
+    if (mcmc && mcmc_recs > (1ll << 62) / thin - burn / thin) {
+        std::fprintf(stderr, "posterior: %lld records per chain at --thin %lld after --burn %lld pass 2^62 steps\n", mcmc_recs, thin, burn);
+        return 2;
     }
     ulgio::PssData p;
     if (!ulgio::read_pss(args.get("scoreFile"), p, err)) {
@@ -169,17 +230,85 @@ int main(int argc, char **argv) {
     }
     double log_z = 0.0;
     std::vector<double> edge((size_t)n * n), lp(scores.size());
-    if (ulg_posterior(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, &log_z, edge.data(), lp.data()) != ULG_OK) {
-        std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
-        ulg_destroy(ctx);
-        return 1;
+    // --mcmc: every chain's records, sample r * chains + c = record r of chain c; the line that stands for ln Z
+    std::vector<uint64_t> m_par;
+    std::vector<uint8_t> m_ord;
+    std::vector<double> m_lw;
+    std::string mcmc_line;
+    if (!mcmc) {
+        if (ulg_posterior(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, &log_z, edge.data(), lp.data()) != ULG_OK) {
+            std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+            ulg_destroy(ctx);
+            return 1;
+        }
+    } else {
+        const long long recs = mcmc_recs;
+        const long long steps = thin * (burn / thin + recs);  // the step of the last record; >= burn + 1, < 2^62 (checked above)
+        int64_t got = 0;
+        std::vector<double> m_ls;
+        std::vector<int64_t> m_acc((size_t)chains);
+        try {
+            if (recs > (1ll << 46) / (chains * n)) throw std::length_error("records");  // the products below stay far inside size_t
+            m_par.resize((size_t)recs * chains * n);
+            m_ord.resize((size_t)recs * chains * n);
+            m_lw.resize((size_t)recs * chains);
+            m_ls.resize((size_t)recs * chains);
+        } catch (const std::exception &) {
+            std::fprintf(stderr, "posterior: out of memory for %lld records of %lld chains\n", recs, chains);
+            ulg_destroy(ctx);
+            return 1;
+        }
+        if (ulg_order_mcmc_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, seed, nullptr) != ULG_OK ||
+            ulg_order_mcmc_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != ULG_OK ||
+            ulg_order_mcmc_run(ctx, steps - burn, thin, m_ord.data(), m_ls.data(), m_par.data(), m_lw.data(), m_acc.data(), nullptr,
+                               nullptr, &got) != ULG_OK) {
+            std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+            ulg_destroy(ctx);
+            return 1;
+        }
+        if (got != recs) {
+            std::fprintf(stderr, "posterior: %lld records per chain, not %lld\n", (long long)got, recs);
+            ulg_destroy(ctx);
+            return 1;
+        }
+        long long accepted = 0;
+        for (int64_t a : m_acc) accepted += a;
+        // Gelman-Rubin over the (recs, chains) log scores: ulg.order_rhat, every sum over its index ascending
+        double rhat = NAN;
+        if (recs >= 2 && chains >= 2) {
+            const double R = (double)recs, C = (double)chains;
+            std::vector<double> mc((size_t)chains, 0.0), ss((size_t)chains, 0.0);
+            for (long long r = 0; r < recs; ++r)
+                for (long long c = 0; c < chains; ++c) mc[(size_t)c] += m_ls[(size_t)(r * chains + c)];
+            for (double &x : mc) x /= R;
+            double m = 0.0;
+            for (double x : mc) m += x;
+            m /= C;
+            for (long long r = 0; r < recs; ++r)
+                for (long long c = 0; c < chains; ++c) {
+                    const double d = m_ls[(size_t)(r * chains + c)] - mc[(size_t)c];
+                    ss[(size_t)c] += d * d;
+                }
+            double W = 0.0, B = 0.0;
+            for (double x : ss) W += x / (R - 1);
+            W /= C;
+            for (double x : mc) B += (x - m) * (x - m);
+            B = R * B / (C - 1);
+            if (W > 0) rhat = std::sqrt(((R - 1) / R * W + B / R) / W);
+        }
+        char line[256], rh[32];
+        if (std::isnan(rhat)) std::snprintf(rh, sizeof rh, "n/a");
+        else std::snprintf(rh, sizeof rh, "%.3f", rhat);
+        std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
+                      steps, (double)accepted / ((double)chains * (double)steps), rh);
+        mcmc_line = line;
     }
     // the samples' lines, drawn and formatted a block at a time: the host buffers do not grow with K
     std::string sample_text;
     std::vector<double> all_le;      // --uniform: log_ext of every sample, and
     std::vector<uint64_t> all_par;   // its parent masks, for the pass that knows the minimum; also kept for the feature files
     // the feature files: tables of ulg_dag_features over all K samples (ancestor, blanket, compelled: n x n; v-structures: n^3)
-    std::vector<uint64_t> f_anc, f_blanket, f_compelled, f_vs;
+    std::vector<uint64_t> f_anc, f_blanket, f_compelled, f_vs, f_edge;  // f_edge: --mcmc's edge matrix
     uint64_t f_total = 0;
     try {
         const long long block = 1 << 16;
@@ -196,7 +325,11 @@ int main(int argc, char **argv) {
             s_par.resize((size_t)cnt * n);
             s_ord.resize((size_t)cnt * n);
             s_lw.resize((size_t)cnt);
-            if (ulg_posterior_sample(ctx, seed, first, cnt, s_par.data(), s_ord.data(), s_lw.data()) != ULG_OK) {
+            if (mcmc) {
+                std::copy(m_par.begin() + (size_t)first * n, m_par.begin() + (size_t)(first + cnt) * n, s_par.begin());
+                std::copy(m_ord.begin() + (size_t)first * n, m_ord.begin() + (size_t)(first + cnt) * n, s_ord.begin());
+                std::copy(m_lw.begin() + (size_t)first, m_lw.begin() + (size_t)(first + cnt), s_lw.begin());
+            } else if (ulg_posterior_sample(ctx, seed, first, cnt, s_par.data(), s_ord.data(), s_lw.data()) != ULG_OK) {
                 std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
                 ulg_destroy(ctx);
                 return 1;
@@ -223,7 +356,7 @@ int main(int argc, char **argv) {
                 }
                 for (long long k = 0; k < cnt; ++k) all_le.push_back(u_le[which[(size_t)k]]);
             }
-            if (uniform || features) all_par.insert(all_par.end(), s_par.begin(), s_par.end());
+            if (uniform || features || mcmc) all_par.insert(all_par.end(), s_par.begin(), s_par.end());
             for (long long k = 0; k < cnt; ++k) {
                 std::snprintf(num, sizeof num, "%.6f", s_lw[(size_t)k]);
                 sample_text += num;
@@ -242,7 +375,7 @@ int main(int argc, char **argv) {
                 sample_text += "\n";
             }
         }
-        if (features) {
+        if (features || mcmc) {
             // --uniform: q_k = floor(exp(min log_ext - log_ext_k) 2^B), ulg.uniform_prior_weights; a count of 0 is
             // refused below, after the ln Z line, as without the feature files
             std::vector<uint64_t> q;
@@ -259,7 +392,8 @@ int main(int argc, char **argv) {
                 if (args.has("blankets")) f_blanket.resize((size_t)n * n);
                 if (args.has("compelled")) f_compelled.resize((size_t)n * n);
                 if (args.has("vstructs")) f_vs.resize((size_t)n * n * n);
-                if (ulg_dag_features(ctx, n, samples, all_par.data(), uniform ? q.data() : nullptr, nullptr,
+                if (mcmc) f_edge.resize((size_t)n * n);
+                if (ulg_dag_features(ctx, n, samples, all_par.data(), uniform ? q.data() : nullptr, f_edge.empty() ? nullptr : f_edge.data(),
                                      f_anc.empty() ? nullptr : f_anc.data(), f_blanket.empty() ? nullptr : f_blanket.data(),
                                      f_compelled.empty() ? nullptr : f_compelled.data(), f_vs.empty() ? nullptr : f_vs.data(),
                                      &f_total, nullptr) != ULG_OK) {
@@ -275,7 +409,8 @@ int main(int argc, char **argv) {
         return 1;
     }
     ulg_destroy(ctx);
-    std::printf("ln Z = %.10f\n", log_z);
+    if (mcmc) std::fputs(mcmc_line.c_str(), stdout);
+    else std::printf("ln Z = %.10f\n", log_z);
     std::string text;
     char buf[64];
     if (uniform) {
@@ -309,6 +444,8 @@ int main(int argc, char **argv) {
             text.clear();
         }
     }
+    if (mcmc)  // the samples' mean edge frequencies (with --uniform: under its weights)
+        for (size_t i = 0; i < f_edge.size(); ++i) edge[i] = (double)f_edge[i] / (double)f_total;
     for (int u = 0; u < n; ++u)
         for (int v = 0; v < n; ++v) {
             std::snprintf(buf, sizeof buf, "%.6f%s", edge[(size_t)u * n + v], v + 1 < n ? "," : "\n");

@@ -99,6 +99,12 @@ def lib():
             L.ulg_dag_linear_extensions.argtypes = [P, I, I64, P, P, P, P]
         if hasattr(L, "ulg_dag_features"):  # ... or from before the structural features
             L.ulg_dag_features.argtypes = [P, I, I64, P, P, P, P, P, P, P, C.POINTER(C.c_uint64), C.POINTER(I64)]
+        if hasattr(L, "ulg_order_mcmc_begin"):  # ... or from before the order MCMC
+            L.ulg_order_mcmc_begin.argtypes = [P, I, P, P, P, I, I64, C.c_uint64, P]
+            L.ulg_order_mcmc_begin_from_scores.argtypes = [P, I64, C.c_uint64, P]
+            L.ulg_order_mcmc_run.argtypes = [P, I64, I64, P, P, P, P, P, P, P, C.POINTER(I64)]
+            L.ulg_order_mcmc_state.argtypes = [P, P, P, C.POINTER(I64)]
+            L.ulg_order_score.argtypes = [P, I64, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -166,6 +172,29 @@ def uniform_prior_weights(log_ext):
         raise ULGError("uniform_prior_weights: a sample without a linear extension (log_ext not finite): not a sampled DAG")
     bits = min(52, 62 - (le.shape[0] - 1).bit_length())  # (K - 1).bit_length() = ceil(log2 K)
     return np.floor(np.ldexp(np.exp(le.min() - le), bits)).astype(np.uint64)
+
+
+def order_rhat(log_score):
+    """Gelman-Rubin's potential scale reduction of Context.order_mcmc_run's "log_score", float64
+    (records R, chains C) -> float; NaN for R < 2 or C < 2, or when no chain moved (W = 0).
+    m_c = (sum_r x[r, c]) / R, m = (sum_c m_c) / C, W = (sum_c (sum_r (x[r, c] - m_c)^2) / (R - 1)) / C,
+    B = R (sum_c (m_c - m)^2) / (C - 1), R-hat = sqrt(((R - 1) / R W + B / R) / W).  Every sum is a
+    float64 sum over its index ascending (np.cumsum, not np.sum's pairwise order), which
+    `posterior --mcmc` repeats term by term."""
+    x = np.ascontiguousarray(log_score, dtype=np.float64)
+    if x.ndim != 2:
+        raise ULGError(f"order_rhat: log_score must be (records, chains), not {x.shape}")
+    R, Cn = x.shape
+    if R < 2 or Cn < 2:
+        return float("nan")
+    mc = np.cumsum(x, axis=0)[-1] / R
+    m = np.cumsum(mc)[-1] / Cn
+    d = x - mc
+    W = np.cumsum(np.cumsum(d * d, axis=0)[-1] / (R - 1))[-1] / Cn
+    B = R * np.cumsum((mc - m) * (mc - m))[-1] / (Cn - 1)
+    if not W > 0:
+        return float("nan")
+    return float(np.sqrt(((R - 1) / R * W + B / R) / W))
 
 
 DAG_FEATURES = ("edge", "ancestor", "blanket", "compelled", "vstruct")
@@ -654,6 +683,113 @@ class Context:
                                            C.byref(total), C.byref(cyclic)), "ulg_dag_features")
         out["total"], out["cyclic"] = int(total.value), int(cyclic.value)
         return out
+
+    # ---- order MCMC ----------------------------------------------------------
+    def _mcmc_init_arg(self, who, init_order, chains, n):
+        if init_order is None:
+            return None, None
+        o = np.ascontiguousarray(init_order, dtype=np.uint8)
+        if o.shape != (chains, n):
+            raise ULGError(f"{who}: init_order must be ({chains}, {n}), not {o.shape}")
+        return o, _ptr(o)
+
+    def order_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_order=None, device_ptrs=False):
+        """ulg_order_mcmc_begin on per-variable lists (as Context.posterior takes them): `chains` chains of
+        seed `seed`, each from its row of init_order uint8 (chains, n) or, with None, from the contract's
+        shuffle; step 0."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, chains = len(o) - 1, int(chains)
+        if device_ptrs:
+            sp, cp, keep = C.c_void_p(int(sets)), C.c_void_p(int(scores)), None
+        else:
+            s = np.ascontiguousarray(sets, dtype=np.uint64)
+            c = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.size == 0:
+                s, c = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.float32)
+            sp, cp, keep = _ptr(s), _ptr(c), (s, c)
+        init, ip = self._mcmc_init_arg("order_mcmc_begin", init_order, chains, n)
+        self._mcmc = None  # a refused call leaves no chains
+        self._check(lib().ulg_order_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip),
+                    "ulg_order_mcmc_begin")
+        self._mcmc = (n, chains)
+        del keep, init
+
+    def order_mcmc_begin_from_scores(self, chains, seed=0, init_order=None):
+        """ulg_order_mcmc_begin_from_scores: the same on the lists of the last scoring call (every
+        variable scored), scores as they are."""
+        n, chains = self.n or 1, int(chains)
+        init, ip = self._mcmc_init_arg("order_mcmc_begin_from_scores", init_order, chains, n)
+        self._mcmc = None
+        self._check(lib().ulg_order_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_order_mcmc_begin_from_scores")
+        self._mcmc = (n, chains)
+        del init
+
+    def _mcmc_shape(self, who):
+        """(n, chains) of the chains this object began; without them the library's own refusal is raised."""
+        if getattr(self, "_mcmc", None) is None:
+            self._check(lib().ulg_order_mcmc_state(self._h, None, None, None), who)
+            raise ULGError(f"{who}: status 3: the last order_mcmc_begin through this object was refused")
+        return self._mcmc
+
+    def order_mcmc_state(self):
+        """ulg_order_mcmc_state -> (order uint8 (chains, n), terms float64 (chains, n): terms[c, p] = the
+        term of position p, step: the steps every chain has made since begin)."""
+        n, chains = self._mcmc_shape("ulg_order_mcmc_state")
+        order = np.zeros((chains, n), dtype=np.uint8)
+        terms = np.zeros((chains, n), dtype=np.float64)
+        step = C.c_int64()
+        self._check(lib().ulg_order_mcmc_state(self._h, _ptr(order), _ptr(terms), C.byref(step)), "ulg_order_mcmc_state")
+        return order, terms, step.value
+
+    def order_mcmc_run(self, steps, thin=1, want_order=True, want_score=True, want_parents=True, want_weight=True, trace=False):
+        """ulg_order_mcmc_run: every chain `steps` steps on, a record after each step t with t % thin == 0
+        (t counts from begin) -> dict: "records" (per chain, R = (t0 + steps) // thin - t0 // thin),
+        "order" uint8 (R, chains, n), "log_score" float64 (R, chains), "parents" uint64 (R, chains, n),
+        "log_weight" float64 (R, chains) -- each present if wanted (want_weight needs want_parents) --
+        "accepted" int64 (chains): accepted moves since begin, "step": the steps made since begin; with
+        trace also "trace_delta" float64 and "trace_accept" uint8 (steps, chains)."""
+        n, chains = self._mcmc_shape("ulg_order_mcmc_run")
+        steps, thin = int(steps), int(thin)
+        t0 = C.c_int64()
+        self._check(lib().ulg_order_mcmc_state(self._h, None, None, C.byref(t0)), "ulg_order_mcmc_state")
+        ok = steps >= 0 and thin >= 1
+        R = (t0.value + steps) // thin - t0.value // thin if ok else 0
+        want_weight = want_weight and want_parents
+        out = {}
+        try:
+            if want_order:
+                out["order"] = np.zeros((R, chains, n), dtype=np.uint8)
+            if want_score:
+                out["log_score"] = np.zeros((R, chains), dtype=np.float64)
+            if want_parents:
+                out["parents"] = np.zeros((R, chains, n), dtype=np.uint64)
+            if want_weight:
+                out["log_weight"] = np.zeros((R, chains), dtype=np.float64)
+            if trace:
+                out["trace_delta"] = np.zeros((max(steps, 0), chains), dtype=np.float64)
+                out["trace_accept"] = np.zeros((max(steps, 0), chains), dtype=np.uint8)
+        except (MemoryError, ValueError) as e:
+            raise ULGError(f"ulg_order_mcmc_run: status 4: {R} records of {chains} chains do not fit the host memory ({e})") from None
+        out["accepted"] = np.zeros(chains, dtype=np.int64)
+        recs = C.c_int64()
+        arg = lambda name: _ptr(out[name]) if name in out else None  # noqa: E731
+        self._check(lib().ulg_order_mcmc_run(self._h, steps, thin, arg("order"), arg("log_score"), arg("parents"), arg("log_weight"),
+                                             _ptr(out["accepted"]), arg("trace_delta"), arg("trace_accept"), C.byref(recs)),
+                    "ulg_order_mcmc_run")
+        assert recs.value == R
+        out["records"], out["step"] = R, t0.value + steps
+        return out
+
+    def order_score(self, orders):
+        """ulg_order_score: orders uint8 (count, n), each a permutation -> terms float64 (count, n),
+        terms[k, p] = the term of position p of order k on the lists of the last order_mcmc_begin."""
+        n, _ = self._mcmc_shape("ulg_order_score")
+        o = np.ascontiguousarray(orders, dtype=np.uint8)
+        if o.ndim != 2 or o.shape[1] != n:
+            raise ULGError(f"order_score: orders must be (count, {n}), not {o.shape}")
+        terms = np.zeros(o.shape, dtype=np.float64)
+        self._check(lib().ulg_order_score(self._h, o.shape[0], _ptr(o), _ptr(terms)), "ulg_order_score")
+        return terms
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

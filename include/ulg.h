@@ -951,6 +951,52 @@ int ulg_order_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *order
 int ulg_order_mcmc_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *step);
 int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms);
 
+/* Rao-Blackwellised edge posteriors of given orders (Friedman & Koller's
+ * estimator): given an order <, the edge posterior has a closed form over the
+ * very entries the order's term scans,
+ *   p(u -> v | <) = sum_{stored P subset of pred(v), u in P} w_v(P) / A_v(pred(v)),
+ * and its mean over orders recorded by ulg_order_mcmc_run estimates
+ * p(u -> v | D) of the same order-modular posterior with a variance that is
+ * never above that of the sampled DAGs' 0/1 indicator.  It does not mend a
+ * chain that has not mixed.  On the lists of the last successful
+ * ulg_order_mcmc_begin*, as ulg_order_score.
+ *   orders     count n bytes, each row a permutation, position 0 first.
+ *   edge       groups n n values; order k adds into group k mod groups at
+ *              [g n n + u n + v].  groups = 1: the batch sum; groups = chains
+ *              on ulg_order_mcmc_run's record layout (idx = r chains + c):
+ *              per-chain sums; groups = count: a matrix per order.
+ *   zero       (may be NULL) the number of orders with a term of -inf (an
+ *              order of probability 0).  Such an order adds nothing to any
+ *              table: an answer, not an error.
+ *   edge term  one order's contribution.  For position p, v = order[p], U the
+ *              predecessors: m, the compatible entries, q_i = floor(exp((double)
+ *              s_i - m) 2^52) and T = sum q_i exactly as in the order term
+ *              above.  For u in U, N_u = sum of q_i over the compatible
+ *              entries with u in P_i, an exact 128-bit integer (two words with
+ *              carry).  y(X) = ldexp((double) X_hi, 12) + ldexp((double) X_lo,
+ *              -52), the order term's conversion.  g(u -> v) = (uint64)
+ *              floor(ldexp(y(N_u) / y(T), 40)): FP64, one IEEE division.
+ *              Hence g <= 2^40, g = 2^40 when every compatible entry of
+ *              positive weight holds u (N_u = T; beyond that only where y
+ *              rounds N_u and T to one double), g = 0 for u outside U and on
+ *              the diagonal.  A group's value is the 64-bit integer sum of
+ *              its orders' g.
+ * Every output is therefore the same bits whatever the lanes, waves, grid
+ * (option "edges_grid"), batching or the split of `count` over calls: the sum
+ * of two calls' tables equals one call's.  A caller divides by 2^40 (orders in
+ * the group - its zero orders).
+ * Errors: ULG_ERR_STATE without a successful begin.  ULG_ERR_ARG for
+ * count < 0, count > 2^22 (a sum stays below 2^62), groups < 1 or groups >
+ * max(count, 1), NULL orders with count > 0, NULL edge, a row that is not a
+ * permutation: checked on the host before any device work, nothing is
+ * written.  ULG_ERR_UNSUPPORTED, decided before anything is allocated, when
+ * the call's buffers (count (n + 1) + 8 groups n^2 + n bytes) do not fit
+ * the free device memory.  count = 0 zero-fills the tables and succeeds.  The
+ * device buffers are the call's own and freed when it returns; it touches
+ * neither the chains, the posterior tables nor the context's lists. */
+int ulg_order_edges(ulg_ctx *ctx, int64_t count, const uint8_t *orders, int64_t groups,
+                    uint64_t *edge, int64_t *zero);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the
@@ -1037,6 +1083,10 @@ int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *
  * affects.  "mcmc_launch_steps" (>= 1, default 4096): the steps one launch of
  * it runs at most; the host loops launches over the chains' device state, so
  * no launch is unbounded.  Neither changes a bit of any output.
+ * "edges_grid" (0..65536, default 0): the workgroups (of four waves, an
+ * (order, position) pair per wave at a time) of ulg_order_edges' launches;
+ * 0 = one per four pairs, at most 65536.  The tables are the same integers
+ * either way.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU
@@ -1102,6 +1152,8 @@ int ulg_set_option(ulg_ctx *ctx, const char *name, int64_t value);
  * "dagfeat_grid" (the workgroups the last ulg_dag_features launched, 0 when
  * it launched nothing: under this one name the read-back is the last call's
  * grid, not the option of the same name that asks for it),
+ * "edges_grid" (likewise the workgroups the last ulg_order_edges launched, 0
+ * when it launched nothing),
  * "unrank_lut_entries" (entries of the unrank tables the context holds),
  * "lds_image_bytes" (bytes of the last scoring call's launch images),
  * "narrow_launches" (layer launches of the last ulg_cbic_score that ran the

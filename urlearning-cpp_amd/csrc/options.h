@@ -55,6 +55,7 @@ struct Options {
     // ---- order MCMC ----
     int64_t mcmc_waves = 4;          // ulg_order_mcmc_run: waves of the workgroup that runs one chain
     int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most
+    int64_t edges_grid = 0;          // ulg_order_edges: workgroups of its launches (0: the default rule)
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -102,6 +103,7 @@ constexpr OptionRow kOptionRows[] = {
     {"dagfeat_grid", &Options::dagfeat_grid, 0, 65536, 0, {}, "0..65536"},
     {"mcmc_waves", &Options::mcmc_waves, 0, 0, 4, {1, 2, 4, 8}, "1, 2, 4 or 8"},
     {"mcmc_launch_steps", &Options::mcmc_launch_steps, 1, kOptMax, 0, {}, ">= 1"},
+    {"edges_grid", &Options::edges_grid, 0, 65536, 0, {}, "0..65536"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -224,9 +224,13 @@ int ulg_set_option(ulg_ctx *c, const char *name, int64_t value) {
 int ulg_get_info(ulg_ctx *c, const char *name, int64_t *value) {
     if (!c || !name || !value) return ULG_ERR_ARG;
     // the grid the last ulg_dag_features ran, which the option of that name asks for (0: no launch
-    // yet); the one option name that does not read back the option
+    // yet); one of the two option names that do not read back the option
     if (std::strcmp(name, "dagfeat_grid") == 0) {
         *value = c->dagfeat_grid;
+        return ULG_OK;
+    }
+    if (std::strcmp(name, "edges_grid") == 0) {  // ... and the second: the last ulg_order_edges' grid
+        *value = c->edges_grid;
         return ULG_OK;
     }
     if (options_get(c->opt, name, value)) return ULG_OK;  // any option, as it stands

@@ -186,6 +186,7 @@ struct ulg_ctx : ulg::CtxStreams {
 
     // ---- order MCMC (order_mcmc.hip): its lists and chains, apart from the model averaging's ----
     ulg::OrderMcmcState *mcmc = nullptr;
+    int64_t edges_grid = 0;       // ulg_get_info("edges_grid"): workgroups the last ulg_order_edges launched (order_edges.hip)
 
     // ---- profiling ----
     bool prof = false;

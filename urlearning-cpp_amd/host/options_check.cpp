@@ -3,7 +3,8 @@
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
 // (score_narrow, bge_prune, posterior_keep, linext_batch, dagfeat_grid,
-// mcmc_waves and mcmc_launch_steps, added since, are recorded the same way).
+// mcmc_waves, mcmc_launch_steps and edges_grid, added since, are recorded the
+// same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
 #include <cstdlib>
@@ -73,6 +74,7 @@ const std::vector<Want> kWant = {
     {"dagfeat_grid", {}, 0, 65536, 0, "0..65536"},
     {"mcmc_waves", {1, 2, 4, 8}, 0, 0, 4, "1, 2, 4 or 8"},
     {"mcmc_launch_steps", {}, 1, kNoMax, 4096, ">= 1"},
+    {"edges_grid", {}, 0, 65536, 0, "0..65536"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -108,7 +110,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 33);
+    CHECK(kWant.size() == 34);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

@@ -6,7 +6,7 @@
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
 //             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]
 //              [--paths FILE] [--blankets FILE] [--compelled FILE] [--vstructs FILE]
-//              [--mcmc [--chains C] [--burn B] [--thin T]]]
+//              [--mcmc [--chains C] [--burn B] [--thin T] [--rb-edges FILE]]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -61,11 +61,25 @@
 // (-o, else standard output) is then the samples' mean edge frequency from
 // the same ulg_dag_features call, weighted as the feature files are.  -s has
 // no counterpart and is refused with --mcmc.
+// --rb-edges FILE (with --mcmc) writes, in -o's format, the Rao-Blackwellised
+// edge matrix of the very K orders the run recorded (ulg_order_edges): the mean
+// over the orders of the closed form p(u -> v | order), an estimate of the same
+// order-modular posterior as -o's sample mean with a variance that is never
+// larger; it does not mend a chain that has not mixed (R-hat stays the thing to
+// read).  One table per chain (groups = C) when C >= 2, K >= C and the tables
+// fit 2^28 bytes, else one table; at most 2^22 samples.  The line
+//   Rao-Blackwell edges: K orders, Z of probability 0, largest standard error = %.6f
+// follows the order MCMC line: the standard error of the mean across chains
+// (ulg.order_edge_posterior term by term), or "standard error not computed"
+// with one table, and also with a table per chain when Z > 0: which chain an
+// order of probability 0 belongs to is not reported, so the chains' counts
+// are not known (a chain never records such an order; Z is then 0).  -o's file is the same with and without it.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
 // (--seed, -g, --uniform, --mcmc or a feature file without --sample,
 // --uniform-edges without --uniform, --chains, --burn or --thin without
-// --mcmc, -s with it, a K that is not a positive integer, and --thin, --burn
-// and K / C that together pass 2^62 steps per chain included).
+// --mcmc, --rb-edges without --mcmc or with more than 2^22 samples, -s with
+// --mcmc, a K that is not a positive integer, and --thin, --burn and K / C that
+// together pass 2^62 steps per chain included).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -121,6 +135,8 @@ int main(int argc, char **argv) {
                                      "read the R-hat that is printed)."},
             {"", "burn", true, "", "Steps every chain makes before its first record (with --mcmc; default 5000, untuned)."},
             {"", "thin", true, "", "A record after every this many steps (with --mcmc; default 100, untuned)."},
+            {"", "rb-edges", true, "", "Write the Rao-Blackwellised edge posteriors of the recorded orders here, in -o's format "
+                                       "(with --mcmc; at most 4194304 samples)."},
         },
         {"scoreFile"});
     std::string err;
@@ -159,6 +175,11 @@ int main(int argc, char **argv) {
     }
     if (!mcmc && (args.has("chains") || args.has("burn") || args.has("thin"))) {
         std::fprintf(stderr, "posterior: --chains, --burn and --thin need --mcmc\n");
+        return 2;
+    }
+    const bool rb = args.has("rb-edges");
+    if (rb && !mcmc) {
+        std::fprintf(stderr, "posterior: --rb-edges needs --mcmc\n");
         return 2;
     }
     long long chains = 256, burn = 5000, thin = 100;
@@ -206,6 +227,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "posterior: %lld records per chain at --thin %lld after --burn %lld pass 2^62 steps\n", mcmc_recs, thin, burn);
         return 2;
     }
+    if (rb && samples > (1ll << 22)) {
+        std::fprintf(stderr, "posterior: --rb-edges takes at most 4194304 samples, not %lld\n", samples);
+        return 2;
+    }
     ulgio::PssData p;
     if (!ulgio::read_pss(args.get("scoreFile"), p, err)) {
         std::fprintf(stderr, "posterior: %s\n", err.c_str());
@@ -235,6 +260,7 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> m_ord;
     std::vector<double> m_lw;
     std::string mcmc_line;
+    std::vector<double> rb_mean;  // --rb-edges: the matrix
     if (!mcmc) {
         if (ulg_posterior(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, &log_z, edge.data(), lp.data()) != ULG_OK) {
             std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
@@ -302,6 +328,55 @@ int main(int argc, char **argv) {
         std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
                       steps, (double)accepted / ((double)chains * (double)steps), rh);
         mcmc_line = line;
+        if (rb) {
+            // a table per chain where that gives a standard error and fits; sample k = record k / chains of chain k % chains
+            const long long groups = chains >= 2 && samples >= chains && 8 * chains * n * n <= (1ll << 28) ? chains : 1;
+            std::vector<uint64_t> tab((size_t)groups * n * n);
+            int64_t dead = 0;
+            if (ulg_order_edges(ctx, samples, m_ord.data(), groups, tab.data(), &dead) != ULG_OK) {
+                std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+                ulg_destroy(ctx);
+                return 1;
+            }
+            if (dead >= samples) {  // a recorded order has a finite term: not reached
+                std::fprintf(stderr, "posterior: every recorded order has probability 0\n");
+                ulg_destroy(ctx);
+                return 1;
+            }
+            // ulg.order_edge_posterior: the integer sum over the groups, one division; the standard error over g ascending
+            const double unit = 1099511627776.0;  // 2^40
+            const size_t nn = (size_t)n * n;
+            rb_mean.assign(nn, 0.0);
+            for (size_t i = 0; i < nn; ++i) {
+                uint64_t tot = 0;
+                for (long long g = 0; g < groups; ++g) tot += tab[(size_t)g * nn + i];
+                rb_mean[i] = (double)tot / (unit * (double)(samples - dead));
+            }
+            char se_text[64];
+            std::snprintf(se_text, sizeof se_text, "standard error not computed");
+            if (groups >= 2 && dead == 0) {  // which chain an order of probability 0 belongs to is not reported
+                const double G = (double)groups;
+                double worst = 0.0;
+                for (size_t i = 0; i < nn; ++i) {
+                    double mbar = 0.0, ss = 0.0;
+                    for (long long g = 0; g < groups; ++g) {
+                        const double cnt = (double)(samples / groups + (g < samples % groups ? 1 : 0));
+                        mbar += (double)tab[(size_t)g * nn + i] / (unit * cnt);
+                    }
+                    mbar /= G;
+                    for (long long g = 0; g < groups; ++g) {
+                        const double cnt = (double)(samples / groups + (g < samples % groups ? 1 : 0));
+                        const double d = (double)tab[(size_t)g * nn + i] / (unit * cnt) - mbar;
+                        ss += d * d;
+                    }
+                    worst = std::max(worst, std::sqrt(ss / (G * (G - 1))));
+                }
+                std::snprintf(se_text, sizeof se_text, "largest standard error = %.6f", worst);
+            }
+            std::snprintf(line, sizeof line, "Rao-Blackwell edges: %lld orders, %lld of probability 0, %s\n", samples, (long long)dead,
+                          se_text);
+            mcmc_line += line;
+        }
     }
     // the samples' lines, drawn and formatted a block at a time: the host buffers do not grow with K
     std::string sample_text;
@@ -443,6 +518,18 @@ int main(int argc, char **argv) {
             }
             text.clear();
         }
+    }
+    if (rb) {
+        for (int u = 0; u < n; ++u)
+            for (int v = 0; v < n; ++v) {
+                std::snprintf(buf, sizeof buf, "%.6f%s", rb_mean[(size_t)u * n + v], v + 1 < n ? "," : "\n");
+                text += buf;
+            }
+        if (!ulgio::write_text(args.get("rb-edges"), text)) {
+            std::fprintf(stderr, "posterior: cannot write '%s'\n", args.get("rb-edges").c_str());
+            return 1;
+        }
+        text.clear();
     }
     if (mcmc)  // the samples' mean edge frequencies (with --uniform: under its weights)
         for (size_t i = 0; i < f_edge.size(); ++i) edge[i] = (double)f_edge[i] / (double)f_total;

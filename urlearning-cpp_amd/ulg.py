@@ -105,6 +105,8 @@ def lib():
             L.ulg_order_mcmc_run.argtypes = [P, I64, I64, P, P, P, P, P, P, P, C.POINTER(I64)]
             L.ulg_order_mcmc_state.argtypes = [P, P, P, C.POINTER(I64)]
             L.ulg_order_score.argtypes = [P, I64, P, P]
+        if hasattr(L, "ulg_order_edges"):  # ... or from before the Rao-Blackwellised edges
+            L.ulg_order_edges.argtypes = [P, I64, P, I64, P, C.POINTER(I64)]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -195,6 +197,42 @@ def order_rhat(log_score):
     if not W > 0:
         return float("nan")
     return float(np.sqrt(((R - 1) / R * W + B / R) / W))
+
+
+EDGE_BITS = 40  # ulg_order_edges: an order's edge posterior p is the integer floor(p 2^40)
+
+
+def order_edge_posterior(edge, counts):
+    """The Rao-Blackwellised edge matrix from Context.order_edges' tables: edge uint64 (groups, n, n),
+    counts (groups) or a scalar: the orders of each group that count, i.e. those added to it minus its
+    orders of probability 0 -> mean float64 (n, n) for one group, (mean, stderr) for two or more.
+    mean[u, v] = (sum_g edge[g, u, v]) / (2^40 sum_g counts[g]), the integer sum exact (below 2^62 by the
+    call's limit on count), one float64 division.  stderr: with m_g = edge[g] / (2^40 counts[g]) over the
+    G >= 2 groups that counted an order, sqrt(sum_g (m_g - mbar)^2 / (G (G - 1))), mbar their plain mean,
+    float64 sums over g ascending (np.cumsum), which `posterior --rb-edges` repeats term by term: the
+    standard error of the mean across groups (chains), NaN with fewer than two such groups."""
+    e = np.ascontiguousarray(edge, dtype=np.uint64)
+    if e.ndim == 2:
+        e = e[None]
+    if e.ndim != 3 or e.shape[1] != e.shape[2]:
+        raise ULGError(f"order_edge_posterior: edge must be (groups, n, n), not {e.shape}")
+    G, n = e.shape[0], e.shape[1]
+    cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(counts, dtype=np.int64), (G,)) if np.ndim(counts) == 0 else counts, dtype=np.int64)
+    if cnt.shape != (G,) or np.any(cnt < 0) or cnt.sum() < 1:
+        raise ULGError(f"order_edge_posterior: counts must be ({G},), none negative and not all 0")
+    if np.any((cnt == 0) & (e.reshape(G, -1).max(axis=1) > 0)):
+        raise ULGError("order_edge_posterior: a group without a counted order has a nonzero table")
+    total = e.sum(axis=0, dtype=np.uint64)
+    mean = total.astype(np.float64) / (float(1 << EDGE_BITS) * float(cnt.sum()))
+    if G < 2:
+        return mean
+    live = np.flatnonzero(cnt > 0)
+    if len(live) < 2:
+        return mean, np.full((n, n), np.nan)
+    m = e[live].astype(np.float64) / (float(1 << EDGE_BITS) * cnt[live].astype(np.float64))[:, None, None]
+    mbar = np.cumsum(m, axis=0)[-1] / len(live)
+    d = m - mbar
+    return mean, np.sqrt(np.cumsum(d * d, axis=0)[-1] / (len(live) * (len(live) - 1)))
 
 
 DAG_FEATURES = ("edge", "ancestor", "blanket", "compelled", "vstruct")
@@ -790,6 +828,25 @@ class Context:
         terms = np.zeros(o.shape, dtype=np.float64)
         self._check(lib().ulg_order_score(self._h, o.shape[0], _ptr(o), _ptr(terms)), "ulg_order_score")
         return terms
+
+    def order_edges(self, orders, groups=1):
+        """ulg_order_edges: orders uint8 (count, n), each a permutation -> (edge uint64 (groups, n, n), zero):
+        order k adds g(u -> v) = floor(p(u -> v | order k) 2^40) into edge[k % groups, u, v]; zero = the orders
+        of probability 0 (a term of -inf), which add nothing.  ulg.order_edge_posterior turns the tables into
+        the mean matrix."""
+        n, _ = self._mcmc_shape("ulg_order_edges")
+        o = np.ascontiguousarray(orders, dtype=np.uint8)
+        if o.ndim != 2 or o.shape[1] != n:
+            raise ULGError(f"order_edges: orders must be (count, {n}), not {o.shape}")
+        groups = int(groups)
+        tables = groups if 1 <= groups <= max(o.shape[0], 1) else 1  # a number of groups the library refuses: it writes nothing
+        try:
+            edge = np.zeros((tables, n, n), dtype=np.uint64)
+        except (MemoryError, ValueError) as e:
+            raise ULGError(f"ulg_order_edges: status 4: {groups} tables of n = {n} do not fit the host memory ({e})") from None
+        zero = C.c_int64()
+        self._check(lib().ulg_order_edges(self._h, o.shape[0], _ptr(o), groups, _ptr(edge), C.byref(zero)), "ulg_order_edges")
+        return edge, zero.value
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

@@ -686,13 +686,24 @@ bool HostHuge::reserve(size_t want, bool pin) {
     release();
     const size_t huge = (size_t)2 << 20;
     const size_t b = (want + huge - 1) / huge * huge;
+    if (pin) {
+        // page-locked memory comes from the runtime: registering a mapping of
+        // our own (hipHostRegister) is refused on virtualised GPUs
+        void *h = nullptr;
+        if (hipHostMalloc(&h, b, hipHostMallocDefault) == hipSuccess) {
+            p = h;
+            bytes = b;
+            pinned = true;
+            return true;
+        }
+        (void)hipGetLastError();  // else pageable copies; the refusal must not meet the next launch's check
+    }
     void *q = mmap(nullptr, b, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
     if (q == MAP_FAILED) return false;
     (void)madvise(q, b, MADV_HUGEPAGE);
     p = q;
     bytes = b;
     pinned = false;
-    if (pin) pinned = hipHostRegister(p, b, hipHostRegisterDefault) == hipSuccess;  // else pageable copies
     return true;
 }
 
@@ -702,8 +713,10 @@ void HostHuge::zero_prefix(size_t n) {
 
 void HostHuge::release() {
     if (!p) return;
-    if (pinned) (void)hipHostUnregister(p);
-    munmap(p, bytes);
+    if (pinned)
+        (void)hipHostFree(p);
+    else
+        munmap(p, bytes);
     p = nullptr;
     bytes = 0;
     pinned = false;

@@ -183,8 +183,10 @@ __device__ inline float pdb_h(const SearchDev &d, uint64_t S, int *complete) {
 // ---- host memory for the exact-order search -------------------------------------
 // Anonymous mapping with transparent huge pages requested (the replay's
 // random reads into GB-sized arrays would otherwise miss the TLB on almost
-// every access); optionally page-locked for the device copies.  Pages are
-// zero until touched.
+// every access).  Pages are zero until touched.  With `pin` the block is
+// page-locked memory of the runtime's (hipHostMalloc) for the device copies
+// instead, its contents undefined; the mapping is the fallback when the
+// runtime refuses.
 struct HostHuge {
     void *p = nullptr;
     size_t bytes = 0;

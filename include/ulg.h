@@ -951,6 +951,84 @@ int ulg_order_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *order
 int ulg_order_mcmc_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *step);
 int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms);
 
+/* Metropolis-coupled order MCMC (MC^3, parallel tempering; Geyer 1991): the
+ * order MCMC above in ladders of replicas whose neighbours exchange states, so
+ * that a chain can leave the mode it started in.  Rung r of a ladder targets
+ * p(<)^beta_r; rung 0 (beta = 1) is an exact sampler of the same law, and it
+ * alone is recorded.  The term, the weight floor(exp(x) 2^52), the Philox draw
+ * layout, the proposal, a record's parent-set pick and log_weight are those
+ * of "Order MCMC"; what differs:
+ *   ladders    L >= 1 ladders of R rungs, 1 <= R <= 16, L R <= 2^20.
+ *              betas[R], FP64: betas[0] == 1.0 exactly, strictly descending,
+ *              finite, > 0.  A replica is one order with its terms; replica
+ *              k = l R + r0 is the one that starts on rung r0 of ladder l, and
+ *              the index stays with the state when the state changes rung.
+ *              Every draw about a replica's own state has c = k: the initial
+ *              shuffle (t = 0, d = p), the move of step t (d = 0), the parent
+ *              sets of a record (d = 1 + p).
+ *   move       on rung r: i, j, U_acc, lo, hi, the recomputed terms and delta
+ *              as above.  Rejected on a -inf term, accepted if delta >= 0,
+ *              else iff (U_acc >> 12) < floor(exp(beta_r delta) 2^52), the
+ *              product one FP64 multiply.  beta = 1 gives delta's own bits:
+ *              rung 0 applies the chains' rule to the bit.
+ *   exchange   swap_every = E >= 1, fixed at begin.  After the moves of every
+ *              step t with t mod E = 0, and before a record at t, round
+ *              x = t / E considers the pairs (r, r + 1) with r = x (mod 2) and
+ *              r + 1 < R.  S_r = the sum of the terms of the replica now on
+ *              rung r over p ascending in FP64 (a record's log_score).
+ *              d = (beta_r - beta_{r+1}) (S_{r+1} - S_r): two subtractions and
+ *              one multiply, each rounded once.  Accepted if d >= 0, else iff
+ *              (U >> 12) < floor(exp(d) 2^52) with U = w0 | w1 << 32 of the
+ *              draw (t, c = l R + r, d = 64): the domains 0..63 are the moves'
+ *              and parent sets'.  On acceptance the two replicas trade rungs.
+ *              The pairs of a round are disjoint: no order among them.
+ *   records    at t mod thin = 0 a ladder records the replica on rung 0: its
+ *              order, log_score and, if asked, DAG and log_weight, at index
+ *              rec L + l -- the chains' layout with "chain" read as "ladder".
+ * Ladder l is a fixed function of (lists, seed, l, R, betas, E, its initial
+ * orders): not of the number of ladders, the launch geometry (option
+ * "mc3_waves"), the steps per launch ("mcmc_launch_steps") or the split of
+ * steps over calls; rounds and records go by the global t.  With R = 1 and
+ * betas = {1.0} every output equals ulg_order_mcmc_begin/run/state with
+ * chains = L, bit for bit.
+ * ulg_order_mc3_begin / _begin_from_scores: as the chains' begins; init_order
+ * is L R n bytes, row l R + r the order of the replica that starts on rung r
+ * (NULL: the shuffle).
+ * ulg_order_mc3_run: order, log_score, parents, log_weight and *records as in
+ * ulg_order_mcmc_run, over ladders.  accepted[l R + r] = the moves accepted on
+ * rung r since begin (by rung, not by replica: what tuning a ladder reads);
+ * swaps[l (R-1) + r] = the accepted exchanges of pair (r, r+1) since begin.
+ * trace_delta / trace_accept (tests) at [(t - t0 - 1) L R + l R + r]: the
+ * untempered delta and the decision of the replica that stood on rung r
+ * during step t's move.  trace_swap_d / trace_swap_accept at
+ * [((x - floor(t0 / E) - 1) L + l) (R-1) + r], floor((t0 + steps) / E) -
+ * floor(t0 / E) rounds: d and the decision, -inf / 0 for a pair the round does
+ * not consider.  Every output is a host pointer and may be NULL.
+ * ulg_order_mc3_state: order (L R n bytes) and terms by rung,
+ * replica[l R + r] = the index of the replica now on rung r, *step.
+ * One state serves both kinds: a begin of either ends the chains or ladders
+ * of the one before (a refused one too), ulg_order_mcmc_run/state are
+ * ULG_ERR_STATE on ladders and ulg_order_mc3_run/state on chains;
+ * ulg_order_score and ulg_order_edges serve the lists of the last successful
+ * begin of either kind.  A ulg_posterior* call frees the state.
+ * Errors: as for ulg_order_mcmc_*, and ULG_ERR_ARG for rungs outside 1..16,
+ * ladders < 1 or L R > 2^20, betas NULL, betas[0] != 1, not strictly
+ * descending, <= 0 or not finite, swap_every < 1, a replica whose initial
+ * order has a -inf term (the message names the replica); a replica holds 9 B
+ * more than a chain.  Sizes are refused before anything is allocated. */
+int ulg_order_mc3_begin(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
+                        const float *scores, int device_ptrs, int64_t ladders, int rungs,
+                        const double *betas, int64_t swap_every, uint64_t seed,
+                        const uint8_t *init_order);
+int ulg_order_mc3_begin_from_scores(ulg_ctx *ctx, int64_t ladders, int rungs, const double *betas,
+                                    int64_t swap_every, uint64_t seed, const uint8_t *init_order);
+int ulg_order_mc3_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *order, double *log_score,
+                      uint64_t *parents, double *log_weight, int64_t *accepted, int64_t *swaps,
+                      double *trace_delta, uint8_t *trace_accept, double *trace_swap_d,
+                      uint8_t *trace_swap_accept, int64_t *records);
+int ulg_order_mc3_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *replica,
+                        int64_t *step);
+
 /* Rao-Blackwellised edge posteriors of given orders (Friedman & Koller's
  * estimator): given an order <, the edge posterior has a closed form over the
  * very entries the order's term scans,
@@ -1083,6 +1161,10 @@ int ulg_order_edges(ulg_ctx *ctx, int64_t count, const uint8_t *orders, int64_t 
  * affects.  "mcmc_launch_steps" (>= 1, default 4096): the steps one launch of
  * it runs at most; the host loops launches over the chains' device state, so
  * no launch is unbounded.  Neither changes a bit of any output.
+ * "mc3_waves" (1, 2, 4, 8 or 16; default 16, the measured best): the waves of the workgroup that
+ * runs one ladder of ulg_order_mc3_run; they share the pooled positions of the
+ * ladder's moves ("mcmc_launch_steps" bounds its launches too).  No output bit
+ * depends on it.
  * "edges_grid" (0..65536, default 0): the workgroups (of four waves, an
  * (order, position) pair per wave at a time) of ulg_order_edges' launches;
  * 0 = one per four pairs, at most 65536.  The tables are the same integers

@@ -54,7 +54,8 @@ struct Options {
     int64_t dagfeat_grid = 0;        // ulg_dag_features: workgroups of its launches (0: the default rule)
     // ---- order MCMC ----
     int64_t mcmc_waves = 4;          // ulg_order_mcmc_run: waves of the workgroup that runs one chain
-    int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most
+    int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most (ulg_order_mc3_run's too)
+    int64_t mc3_waves = 16;          // ulg_order_mc3_run: waves of the workgroup that runs one ladder
     int64_t edges_grid = 0;          // ulg_order_edges: workgroups of its launches (0: the default rule)
 };
 
@@ -103,6 +104,7 @@ constexpr OptionRow kOptionRows[] = {
     {"dagfeat_grid", &Options::dagfeat_grid, 0, 65536, 0, {}, "0..65536"},
     {"mcmc_waves", &Options::mcmc_waves, 0, 0, 4, {1, 2, 4, 8}, "1, 2, 4 or 8"},
     {"mcmc_launch_steps", &Options::mcmc_launch_steps, 1, kOptMax, 0, {}, ">= 1"},
+    {"mc3_waves", &Options::mc3_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
     {"edges_grid", &Options::edges_grid, 0, 65536, 0, {}, "0..65536"},
 };
 

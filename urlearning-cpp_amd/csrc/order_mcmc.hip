@@ -339,6 +339,218 @@ __global__ void __launch_bounds__(kWave *W) mcmc_run_kernel(const RunArgs a) {
     if (tid == 0) a.accepted[c] = acc;
 }
 
+// ---- tempered ladders (ulg_order_mc3_*): one workgroup of W waves per ladder.
+// LDS holds every replica's ord, pre, term and fresh by slot (1600 B each, the
+// launch's dynamic LDS).  Lane r < R of EVERY wave holds rung r's scalars --
+// the slot on the rung, beta, the step's move -- so a wave reads another
+// rung's by readlane and nothing of it needs LDS or a barrier: an exchange
+// trades two lanes' slot numbers, in every wave alike.
+//   move      lane r forms rung r's draw (one Philox per wave and step, R
+//             lanes busy); the spans hi - lo + 1 are prefix-summed across the
+//             lanes into the ladder's item table: item q belongs to the last
+//             rung whose start is <= q (a ballot), at position lo + q - start;
+//   terms     wave w takes items w, w + W, ..: one wave_term each.  A rung
+//             with a short span leaves its share of the waves to the others;
+//             the barrier waits for the pooled items, not for R separate maxima;
+//   decision  lane r adds rung r's new and old terms in ascending order and
+//             applies mc3_accept; the ballot of the decisions is the same in
+//             every wave.  Barrier; wave r, r + W, .. writes an accepted
+//             rung's state, lane = position; barrier;
+//   exchange  at t mod E = 0 lane r adds its replica's n terms, takes the
+//             next rung's sum by a shuffle, decides pair (r, r + 1) and both
+//             lanes take the other's slot.  No barrier, no LDS write;
+//   record    rung 0's replica, by the chains' code with its slot's arrays.
+// The arguments are one struct in device memory (Mc3Args).
+__device__ __forceinline__ int lane_get(int x, int r) { return __builtin_amdgcn_readlane(x, r); }
+
+constexpr int kMc3SlotBytes = kWave * 25;  // pre, term, fresh: 8 B a position; ord: 1
+
+template <int W>
+__global__ void __launch_bounds__(kWave *W) mc3_run_kernel(const Mc3Args *g, int64_t t_begin, int64_t nsteps) {
+    extern __shared__ double mc3_lds[];
+    __shared__ double picked[kWave];  // a record's chosen scores, by variable
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const int n = g->n, R = g->rungs;
+    const int64_t L = g->ladders, l = (int64_t)blockIdx.x;  // ladders <= 2^20
+    uint64_t *pre = reinterpret_cast<uint64_t *>(mc3_lds);  // [R][64] each, by slot
+    double *term = mc3_lds + R * kWave, *fresh = mc3_lds + 2 * R * kWave;
+    uint8_t *ord = reinterpret_cast<uint8_t *>(mc3_lds + 3 * R * kWave);
+    const uint64_t *sets = g->sets;
+    const float *scores = g->scores;
+    const int64_t *offsets = g->offsets;
+    const uint64_t seed = g->seed;
+    const int64_t t_call = g->t_call, thin = g->thin, E = g->swap_every;
+    uint8_t *g_order = g->order + l * R * n;
+    double *g_terms = g->terms + l * R * n;
+    for (int idx = tid; idx < R * kWave; idx += kWave * W) {
+        const int p = idx & (kWave - 1);
+        if (p < n) {
+            ord[idx] = g_order[(idx >> 6) * n + p];
+            term[idx] = g_terms[(idx >> 6) * n + p];
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < R * kWave; idx += kWave * W) {
+        const int p = idx & (kWave - 1);
+        if (p < n) {
+            uint64_t U = 0;
+            for (int q = 0; q < p; ++q) U |= 1ull << ord[(idx & ~(kWave - 1)) + q];
+            pre[idx] = U;
+        }
+    }
+    const bool rung = lane < R;
+    int slot = rung ? g->perm[l * R + lane] : 0;
+    const double beta = rung ? g->betas[lane] : 0.0;
+    const double beta_next = __shfl_down(beta, 1, kWave);
+    unsigned long long acc = rung ? g->accepted[l * R + lane] : 0ull;
+    unsigned long long swp = lane < R - 1 ? g->swaps[l * (R - 1) + lane] : 0ull;
+    __syncthreads();
+    for (int64_t s = 0; s < nsteps; ++s) {
+        const int64_t t = t_begin + s + 1;
+        double delta = neg_inf();
+        bool take = false;
+        if (n > 1) {
+            int lo = 0, hi = -1, va = 0, vb = 0;
+            uint64_t u_acc = 0;
+            if (rung) {
+                uint32_t w[4];
+                mcmc_draw(seed, (uint64_t)t, (uint32_t)(l * R + slot), 0u, w);
+                const McmcMove mv = mcmc_move(w, n);
+                lo = mv.i < mv.j ? mv.i : mv.j, hi = mv.i < mv.j ? mv.j : mv.i;
+                va = ord[slot * kWave + lo], vb = ord[slot * kWave + hi];
+                u_acc = mv.u_acc;
+            }
+            const int span = hi - lo + 1;  // 0 beyond the rungs
+            int incl = span;
+            for (int d = 1; d < kMc3MaxRungs; d <<= 1) {
+                const int y = __shfl_up(incl, d, kWave);
+                if (lane >= d) incl += y;
+            }
+            const int start = incl - span, total = lane_get(incl, R - 1);
+            for (int q = wave; q < total; q += W) {
+                const int r = __popcll(__ballot(rung && start <= q)) - 1;
+                const int rlo = lane_get(lo, r), rhi = lane_get(hi, r), rva = lane_get(va, r), rvb = lane_get(vb, r);
+                const int base = lane_get(slot, r) * kWave, p = rlo + q - lane_get(start, r);
+                const uint64_t flip = (1ull << rva) ^ (1ull << rvb);
+                const int v = p == rlo ? rvb : p == rhi ? rva : ord[base + p];
+                const uint64_t U = p == rlo ? pre[base + rlo] : pre[base + p] ^ flip;
+                const double x = wave_term(sets, scores, offsets[v], offsets[v + 1], U, lane);
+                if (lane == 0) fresh[base + p] = x;
+            }
+            __syncthreads();
+            if (rung) {
+                double now = 0.0, was = 0.0;
+                bool none = false;
+                for (int p = lo; p <= hi; ++p) {
+                    const double x = fresh[slot * kWave + p];
+                    none = none || !(x > neg_inf());
+                    now += x;
+                    was += term[slot * kWave + p];
+                }
+                if (!none) delta = now - was;
+                take = mc3_accept(beta, delta, u_acc);
+            }
+            const unsigned long long takes = __ballot(take);
+            __syncthreads();  // every wave has read the old terms
+            for (int r = wave; r < R; r += W) {
+                if (!((takes >> r) & 1ull)) continue;
+                const int rlo = lane_get(lo, r), rhi = lane_get(hi, r), rva = lane_get(va, r), rvb = lane_get(vb, r);
+                const int at = lane_get(slot, r) * kWave + lane;
+                if (lane >= rlo && lane <= rhi) {
+                    term[at] = fresh[at];
+                    if (lane > rlo) pre[at] ^= (1ull << rva) ^ (1ull << rvb);
+                    if (lane == rlo) ord[at] = (uint8_t)rvb;
+                    if (lane == rhi) ord[at] = (uint8_t)rva;
+                }
+            }
+            if (take) ++acc;
+            __syncthreads();
+        }
+        if (wave == 0 && rung) {
+            const int64_t at = ((t - t_call - 1) * L + l) * R + lane;
+            if (g->t_delta) g->t_delta[at] = delta;
+            if (g->t_accept) g->t_accept[at] = take ? 1 : 0;
+        }
+        if (R > 1 && t % E == 0) {
+            const int64_t x = t / E;
+            double S = 0.0;
+            if (rung)
+                for (int p = 0; p < n; ++p) S += term[slot * kWave + p];
+            const double S_next = __shfl_down(S, 1, kWave);
+            double d = neg_inf();
+            bool sw = false;
+            if (rung && mc3_pair_considered(x, lane, R)) {
+                uint32_t w[4];
+                mcmc_draw(seed, (uint64_t)t, (uint32_t)(l * R + lane), kMc3SwapDomain, w);
+                d = mc3_swap_d(beta, beta_next, S, S_next);
+                sw = mc3_swap_accept(d, (uint64_t)w[0] | ((uint64_t)w[1] << 32));
+            }
+            const unsigned long long sws = __ballot(sw);
+            const int above = __shfl_down(slot, 1, kWave), below = __shfl_up(slot, 1, kWave);
+            if (sw) slot = above;
+            else if (lane > 0 && ((sws >> (lane - 1)) & 1ull)) slot = below;
+            if (wave == 0 && lane < R - 1) {
+                const int64_t at = ((x - t_call / E - 1) * L + l) * (R - 1) + lane;
+                if (g->t_swap_d) g->t_swap_d[at] = d;
+                if (g->t_swap_accept) g->t_swap_accept[at] = sw ? 1 : 0;
+                if (sw) ++swp;
+            }
+        }
+        if (t % thin == 0) {
+            const int cold = lane_get(slot, 0), base = cold * kWave;
+            const uint32_t c = (uint32_t)(l * R + cold);
+            const int64_t idx = (t / thin - t_call / thin - 1) * L + l;
+            uint8_t *r_order = g->r_order;
+            double *r_score = g->r_score, *r_weight = g->r_weight;
+            uint64_t *r_parents = g->r_parents;
+            if (r_order && tid < n) r_order[idx * n + tid] = ord[base + tid];
+            if (r_score && tid == 0) {
+                double sum = 0.0;
+                for (int p = 0; p < n; ++p) sum += term[base + p];
+                r_score[idx] = sum;
+            }
+            if (r_parents) {
+                for (int p = wave; p < n; p += W) {
+                    uint32_t w[4];
+                    mcmc_draw(seed, (uint64_t)t, c, (uint32_t)(1 + p), w);
+                    const uint64_t u_set = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+                    const int v = ord[base + p];
+                    const int64_t e = wave_pick(sets, scores, offsets[v], offsets[v + 1], pre[base + p], term[base + p], u_set, lane);
+                    if (lane == 0) {
+                        if (e < 0) {
+                            atomicOr(g->err, kErrPick);  // as in mcmc_run_kernel
+                            r_parents[idx * n + v] = 0;
+                            picked[v] = 0.0;
+                        } else {
+                            r_parents[idx * n + v] = sets[e];
+                            picked[v] = (double)scores[e];
+                        }
+                    }
+                }
+                __syncthreads();
+                if (r_weight && tid == 0) {
+                    double sum = 0.0;
+                    for (int v = 0; v < n; ++v) sum += picked[v];
+                    r_weight[idx] = sum;
+                }
+                __syncthreads();  // before the next record's picks
+            }
+        }
+    }
+    for (int idx = tid; idx < R * kWave; idx += kWave * W) {
+        const int p = idx & (kWave - 1);
+        if (p < n) {
+            g_order[(idx >> 6) * n + p] = ord[idx];
+            g_terms[(idx >> 6) * n + p] = term[idx];
+        }
+    }
+    if (wave == 0 && rung) {
+        g->perm[l * R + lane] = (uint8_t)slot;
+        g->accepted[l * R + lane] = acc;
+    }
+    if (wave == 0 && lane < R - 1) g->swaps[l * (R - 1) + lane] = swp;
+}
+
 // ---- host
 OrderMcmcState &state(ulg_ctx *c) {
     if (!c->mcmc) c->mcmc = new OrderMcmcState();
@@ -371,24 +583,24 @@ int launch_score(ulg_ctx *c, OrderMcmcState &s, const uint8_t *d_orders, int64_t
 }
 
 // The arguments that need no device, for both begins
-int check_begin_args(ulg_ctx *c, const std::string &who, int n, int64_t chains, const uint8_t *init_order) {
+int check_begin_args(ulg_ctx *c, const std::string &who, int n, int64_t chains, const uint8_t *init_order, const char *what = "chain") {
     if (n < 1) return set_err(c, ULG_ERR_ARG, who + ": n < 1");
     if (n > kMcmcMaxVars) return set_err(c, ULG_ERR_UNSUPPORTED, who + ": n = " + std::to_string(n) + "; at most 63 variables");
     if (chains < 1 || chains > kMcmcMaxChains) return set_err(c, ULG_ERR_ARG, who + ": chains must be 1..2^20");
     if (init_order)
         for (int64_t k = 0; k < chains; ++k)
             if (!is_permutation(init_order + k * n, n))
-                return set_err(c, ULG_ERR_ARG, who + ": the initial order of chain " + std::to_string(k) + " is not a permutation");
+                return set_err(c, ULG_ERR_ARG, who + ": the initial order of " + what + " " + std::to_string(k) + " is not a permutation");
     return ULG_OK;
 }
 
 // Lists and chains beyond the free device memory (what the state already
 // holds counts as free: its buffers are reused or replaced).  Nothing has
 // been allocated yet.
-int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_t chains) {
+int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_t chains, double per_chain = 0.0) {
     size_t free_b = 0, total_b = 0;
     ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
-    const double need = 12.0 * (double)total + 8.0 * (n + 1) + 8.0 * (double)table_slots(total) + (9.0 * n + 8.0) * (double)chains + 8.0 * 16 + 256.0;
+    const double need = 12.0 * (double)total + 8.0 * (n + 1) + 8.0 * (double)table_slots(total) + (9.0 * n + 8.0 + per_chain) * (double)chains + 8.0 * 16 + 256.0;
     const double have = (double)free_b + (c->mcmc ? (double)c->mcmc->held_bytes() : 0.0);
     if (need > have) {
         char buf[256];
@@ -401,7 +613,8 @@ int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_
 
 // The lists are on the device in s (variable order) with s.n and s.total set,
 // s.offsets their offsets on the host: the checks, the initial orders, the terms.
-int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains, uint64_t seed, const uint8_t *init_order) {
+int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains, uint64_t seed, const uint8_t *init_order,
+          const char *what = "chain") {
     const std::vector<int64_t> &offs = s.offsets;
     const int n = s.n;
     s.ready = false;
@@ -452,9 +665,10 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
     prof_collect(c);
     if (err[1] != 0xFFFFFFFFu)
         return set_err(c, ULG_ERR_ARG,
-                       who + ": the initial order of chain " + std::to_string(err[1]) +
+                       who + ": the initial order of " + what + " " + std::to_string(err[1]) +
                            " has a variable without a stored parent set among its predecessors (a term of -inf: probability 0)");
     s.chains = chains;
+    s.rungs = 0;
     s.seed = seed;
     s.step = 0;
     s.ready = true;
@@ -466,23 +680,19 @@ void launch_run(ulg_ctx *c, const RunArgs &a) {
     mcmc_run_kernel<W><<<dim3((unsigned)a.chains), kWave * W, 0, c->stream>>>(a);
 }
 
-}  // namespace
-
-extern "C" {
-
-int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_t *sets, const float *scores, int device_ptrs,
-                         int64_t chains, uint64_t seed, const uint8_t *init_order) {
-    if (!c) return ULG_ERR_ARG;
-    const std::string who = "ulg_order_mcmc_begin";
-    if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
+// Both kinds of begin on the caller's lists (`chains` chains, or as many
+// replicas of ladders: `what` names them in a refusal, per_chain is what a
+// ladder's replica holds beyond a chain's bytes)
+int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
+                   int device_ptrs, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what, double per_chain) {
     if (!offsets) return set_err(c, ULG_ERR_ARG, who + ": bad arguments");
-    if (int rc = check_begin_args(c, who, n, chains, init_order)) return rc;
+    if (int rc = check_begin_args(c, who, n, chains, init_order, what)) return rc;
     for (int v = 0; v < n; ++v)
         if (offsets[v + 1] < offsets[v]) return set_err(c, ULG_ERR_ARG, who + ": offsets not ascending");
     const int64_t total = offsets[n] - offsets[0];
     if (total && (!sets || !scores)) return set_err(c, ULG_ERR_ARG, who + ": bad arguments");
     ULG_HIP(c, hipSetDevice(c->device));
-    if (int rc = refuse_size(c, who, n, total, chains)) return rc;
+    if (int rc = refuse_size(c, who, n, total, chains, per_chain)) return rc;
     OrderMcmcState &s = state(c);
     s.ready = false;
     int rc;
@@ -500,13 +710,12 @@ int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64
         ULG_HIP(c, hipMemcpyAsync(s.d_scores.p, scores + offsets[0], (size_t)total * 4, kind, c->stream));
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order);
+    return begin(c, who, s, chains, seed, init_order, what);
 }
 
-int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
-    if (!c) return ULG_ERR_ARG;
-    const std::string who = "ulg_order_mcmc_begin_from_scores";
-    if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
+// ... and on the lists of the last scoring call
+int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what,
+                    double per_chain) {
     if (int rc0 = finish_pending(c)) return rc0;
     if (!c->scored) return set_err(c, ULG_ERR_STATE, who + ": no scoring call yet");
     const int n = c->n;
@@ -518,13 +727,13 @@ int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, 
         if (all) where[v] = i;
     }
     if (!all) return set_err(c, ULG_ERR_STATE, who + ": every variable must be scored in this context");
-    if (int rc = check_begin_args(c, who, n, chains, init_order)) return rc;
+    if (int rc = check_begin_args(c, who, n, chains, init_order, what)) return rc;
     ULG_HIP(c, hipSetDevice(c->device));
     std::vector<int64_t> src((size_t)n + 1);
     ULG_HIP(c, hipMemcpyAsync(src.data(), c->out_offsets.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     const int64_t total = src[n];
-    if (int rc = refuse_size(c, who, n, total, chains)) return rc;
+    if (int rc = refuse_size(c, who, n, total, chains, per_chain)) return rc;
     OrderMcmcState &s = state(c);
     s.ready = false;
     int rc;
@@ -547,14 +756,72 @@ int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, 
         }
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order);
+    return begin(c, who, s, chains, seed, init_order, what);
+}
+
+// ---- ladders
+constexpr double kMc3ReplicaBytes = 9.0;  // beyond a chain's: the rung's slot byte and the pair's count
+
+// What ulg_order_mc3_begin* refuse before any device work
+int mc3_check_args(ulg_ctx *c, const std::string &who, int64_t ladders, int rungs, const double *betas, int64_t swap_every) {
+    if (rungs < 1 || rungs > kMc3MaxRungs) return set_err(c, ULG_ERR_ARG, who + ": rungs must be 1..16");
+    if (ladders < 1 || ladders > kMcmcMaxChains / rungs) return set_err(c, ULG_ERR_ARG, who + ": ladders x rungs must be 1..2^20");
+    if (!betas || betas[0] != 1.0) return set_err(c, ULG_ERR_ARG, who + ": betas[0] must be 1");
+    for (int r = 1; r < rungs; ++r)  // false for a NaN too; below 1, so finite
+        if (!(betas[r] > 0.0) || !(betas[r] < betas[r - 1]))
+            return set_err(c, ULG_ERR_ARG, who + ": betas must be strictly descending and > 0");
+    if (swap_every < 1) return set_err(c, ULG_ERR_ARG, who + ": swap_every must be >= 1");
+    return ULG_OK;
+}
+
+// After begin() made ladders x rungs replicas as chains: the rungs' slots, the
+// pairs' counts, and the state's reading as ladders.
+int mc3_make_ladders(ulg_ctx *c, int64_t ladders, int rungs, const double *betas, int64_t swap_every) {
+    OrderMcmcState &s = *c->mcmc;
+    s.ready = false;
+    const size_t reps = (size_t)ladders * (size_t)rungs, pairs = (size_t)ladders * (size_t)(rungs - 1);
+    int rc;
+    if ((rc = ensure(c, s.d_perm, reps)) || (rc = ensure(c, s.d_swaps, pairs)) || (rc = ensure(c, s.d_args, 1))) return rc;
+    std::vector<uint8_t> perm(reps);
+    for (size_t k = 0; k < reps; ++k) perm[k] = (uint8_t)(k % (size_t)rungs);
+    ULG_HIP(c, hipMemcpyAsync(s.d_perm.p, perm.data(), reps, hipMemcpyHostToDevice, c->stream));
+    ULG_HIP(c, hipMemsetAsync(s.d_swaps.p, 0, std::max<size_t>(pairs, 1) * 8, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));  // perm is read until here
+    s.chains = ladders;
+    s.rungs = rungs;
+    s.swap_every = swap_every;
+    for (int r = 0; r < kMc3MaxRungs; ++r) s.betas[r] = r < rungs ? betas[r] : 0.0;
+    s.ready = true;
+    return ULG_OK;
+}
+
+template <int W>
+void launch_mc3(ulg_ctx *c, const OrderMcmcState &s, int64_t t_begin, int64_t nsteps) {
+    mc3_run_kernel<W><<<dim3((unsigned)s.chains), kWave * W, (size_t)s.rungs * kMc3SlotBytes, c->stream>>>(s.d_args.p, t_begin, nsteps);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_t *sets, const float *scores, int device_ptrs,
+                         int64_t chains, uint64_t seed, const uint8_t *init_order) {
+    if (!c) return ULG_ERR_ARG;
+    if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
+    return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0);
+}
+
+int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
+    if (!c) return ULG_ERR_ARG;
+    if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
+    return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0);
 }
 
 int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, double *log_score, uint64_t *parents,
                        double *log_weight, int64_t *accepted, double *trace_delta, uint8_t *trace_accept, int64_t *records) {
     if (!c) return ULG_ERR_ARG;
     const std::string who = "ulg_order_mcmc_run";
-    if (!c->mcmc || !c->mcmc->ready) return set_err(c, ULG_ERR_STATE, who + ": no ulg_order_mcmc_begin");
+    if (!c->mcmc || !c->mcmc->ready || c->mcmc->rungs) return set_err(c, ULG_ERR_STATE, who + ": no ulg_order_mcmc_begin");
     OrderMcmcState &s = *c->mcmc;
     if (steps < 0 || thin < 1) return set_err(c, ULG_ERR_ARG, who + ": steps must be >= 0 and thin >= 1");
     if (steps > INT64_MAX - s.step) return set_err(c, ULG_ERR_ARG, who + ": the step count passes 2^63");
@@ -632,7 +899,7 @@ int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, 
 
 int ulg_order_mcmc_state(ulg_ctx *c, uint8_t *order, double *terms, int64_t *step) {
     if (!c) return ULG_ERR_ARG;
-    if (!c->mcmc || !c->mcmc->ready) return set_err(c, ULG_ERR_STATE, "ulg_order_mcmc_state: no ulg_order_mcmc_begin");
+    if (!c->mcmc || !c->mcmc->ready || c->mcmc->rungs) return set_err(c, ULG_ERR_STATE, "ulg_order_mcmc_state: no ulg_order_mcmc_begin");
     OrderMcmcState &s = *c->mcmc;
     const size_t cells = (size_t)s.chains * (size_t)s.n;
     ULG_HIP(c, hipSetDevice(c->device));
@@ -675,6 +942,144 @@ int ulg_order_score(ulg_ctx *c, int64_t count, const uint8_t *orders, double *te
     ULG_HIP(c, hipMemcpyAsync(terms, s.r_score.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    return ULG_OK;
+}
+
+int ulg_order_mc3_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_t *sets, const float *scores, int device_ptrs,
+                        int64_t ladders, int rungs, const double *betas, int64_t swap_every, uint64_t seed, const uint8_t *init_order) {
+    if (!c) return ULG_ERR_ARG;
+    const std::string who = "ulg_order_mc3_begin";
+    if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin: a refused begin leaves neither chains nor ladders
+    if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;
+    if (int rc = begin_on_lists(c, who, n, offsets, sets, scores, device_ptrs, ladders * rungs, seed, init_order, "replica",
+                                kMc3ReplicaBytes))
+        return rc;
+    return mc3_make_ladders(c, ladders, rungs, betas, swap_every);
+}
+
+int ulg_order_mc3_begin_from_scores(ulg_ctx *c, int64_t ladders, int rungs, const double *betas, int64_t swap_every, uint64_t seed,
+                                    const uint8_t *init_order) {
+    if (!c) return ULG_ERR_ARG;
+    const std::string who = "ulg_order_mc3_begin_from_scores";
+    if (c->mcmc) c->mcmc->ready = false;
+    if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;
+    if (int rc = begin_on_scored(c, who, ladders * rungs, seed, init_order, "replica", kMc3ReplicaBytes)) return rc;
+    return mc3_make_ladders(c, ladders, rungs, betas, swap_every);
+}
+
+int ulg_order_mc3_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, double *log_score, uint64_t *parents, double *log_weight,
+                      int64_t *accepted, int64_t *swaps, double *trace_delta, uint8_t *trace_accept, double *trace_swap_d,
+                      uint8_t *trace_swap_accept, int64_t *records) {
+    if (!c) return ULG_ERR_ARG;
+    const std::string who = "ulg_order_mc3_run";
+    if (!c->mcmc || !c->mcmc->ready || !c->mcmc->rungs) return set_err(c, ULG_ERR_STATE, who + ": no ulg_order_mc3_begin");
+    OrderMcmcState &s = *c->mcmc;
+    if (steps < 0 || thin < 1) return set_err(c, ULG_ERR_ARG, who + ": steps must be >= 0 and thin >= 1");
+    if (steps > INT64_MAX - s.step) return set_err(c, ULG_ERR_ARG, who + ": the step count passes 2^63");
+    if (log_weight && !parents) return set_err(c, ULG_ERR_ARG, who + ": log_weight needs parents");
+    const int n = s.n, R = s.rungs;
+    const int64_t L = s.chains, t0 = s.step, E = s.swap_every;
+    const int64_t recs = (t0 + steps) / thin - t0 / thin, rounds = (t0 + steps) / E - t0 / E;
+    ULG_HIP(c, hipSetDevice(c->device));
+    const double cells = (double)recs * (double)L, moves = (double)steps * (double)L * R, pairs = (double)rounds * (double)L * (R - 1);
+    {
+        const double need = cells * ((order ? n : 0) + (log_score ? 8.0 : 0.0) + (parents ? 8.0 * n : 0.0) + (log_weight ? 8.0 : 0.0)) +
+                            moves * ((trace_delta ? 8.0 : 0.0) + (trace_accept ? 1.0 : 0.0)) +
+                            pairs * ((trace_swap_d ? 8.0 : 0.0) + (trace_swap_accept ? 1.0 : 0.0)) + 8 * 16.0 + 256.0;
+        size_t free_b = 0, total_b = 0;
+        ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
+        const double have = (double)free_b + (double)s.run_bytes();
+        if (need > have) {
+            char buf[256];
+            std::snprintf(buf, sizeof buf, "%s: %lld records and %lld steps of %lld ladders need %.0f bytes of device memory, %.0f are free",
+                          who.c_str(), (long long)recs, (long long)steps, (long long)L, need, have);
+            return set_err(c, ULG_ERR_UNSUPPORTED, buf);
+        }
+    }
+    const size_t ncell = (size_t)recs * (size_t)L, nmove = (size_t)steps * (size_t)L * R, npair = (size_t)rounds * (size_t)L * (R - 1);
+    int rc;
+    if ((order && (rc = ensure(c, s.r_order, ncell * n))) || (log_score && (rc = ensure(c, s.r_score, ncell))) ||
+        (parents && (rc = ensure(c, s.r_parents, ncell * n))) || (log_weight && (rc = ensure(c, s.r_weight, ncell))) ||
+        (trace_delta && (rc = ensure(c, s.r_tdelta, nmove))) || (trace_accept && (rc = ensure(c, s.r_taccept, nmove))) ||
+        (trace_swap_d && (rc = ensure(c, s.r_tswapd, npair))) || (trace_swap_accept && (rc = ensure(c, s.r_tswapacc, npair))))
+        return rc;
+    ULG_HIP(c, hipMemsetAsync(s.d_err.p, 0, sizeof(unsigned int), c->stream));
+    Mc3Args &a = s.args;
+    a.sets = s.d_sets.p, a.scores = s.d_scores.p, a.offsets = s.d_offsets.p;
+    a.order = s.d_order.p, a.terms = s.d_terms.p, a.perm = s.d_perm.p, a.accepted = s.d_accepted.p, a.swaps = s.d_swaps.p;
+    a.n = n, a.rungs = R, a.ladders = L, a.seed = s.seed, a.swap_every = E;
+    a.t_call = t0, a.thin = thin;
+    a.r_order = order ? s.r_order.p : nullptr;
+    a.r_score = log_score ? s.r_score.p : nullptr;
+    a.r_parents = parents ? s.r_parents.p : nullptr;
+    a.r_weight = log_weight ? s.r_weight.p : nullptr;
+    a.t_delta = trace_delta ? s.r_tdelta.p : nullptr;
+    a.t_accept = trace_accept ? s.r_taccept.p : nullptr;
+    a.t_swap_d = trace_swap_d ? s.r_tswapd.p : nullptr;
+    a.t_swap_accept = trace_swap_accept ? s.r_tswapacc.p : nullptr;
+    a.err = s.d_err.p;
+    for (int r = 0; r < kMc3MaxRungs; ++r) a.betas[r] = s.betas[r];
+    ULG_HIP(c, hipMemcpyAsync(s.d_args.p, &a, sizeof a, hipMemcpyHostToDevice, c->stream));
+    const int64_t cap = c->opt.mcmc_launch_steps;
+    for (int64_t done = 0; done < steps;) {
+        const int64_t now = std::min(cap, steps - done);
+        prof_begin(c, "mc3_run");
+        switch (c->opt.mc3_waves) {
+            case 1: launch_mc3<1>(c, s, t0 + done, now); break;
+            case 2: launch_mc3<2>(c, s, t0 + done, now); break;
+            case 4: launch_mc3<4>(c, s, t0 + done, now); break;
+            case 8: launch_mc3<8>(c, s, t0 + done, now); break;
+            default: launch_mc3<16>(c, s, t0 + done, now); break;
+        }
+        prof_end(c);
+        ULG_HIP(c, hipGetLastError());
+        done += now;
+    }
+    unsigned int err = 0;
+    ULG_HIP(c, hipMemcpyAsync(&err, s.d_err.p, sizeof err, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    s.step = t0 + steps;  // the ladders have moved, whatever becomes of the copies below
+    if (err) return set_err(c, ULG_ERR_STATE, who + ": a record's parent-set step found no entry of positive weight");
+    if (order && ncell) ULG_HIP(c, hipMemcpyAsync(order, s.r_order.p, ncell * n, hipMemcpyDeviceToHost, c->stream));
+    if (log_score && ncell) ULG_HIP(c, hipMemcpyAsync(log_score, s.r_score.p, ncell * 8, hipMemcpyDeviceToHost, c->stream));
+    if (parents && ncell) ULG_HIP(c, hipMemcpyAsync(parents, s.r_parents.p, ncell * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (log_weight && ncell) ULG_HIP(c, hipMemcpyAsync(log_weight, s.r_weight.p, ncell * 8, hipMemcpyDeviceToHost, c->stream));
+    if (trace_delta && nmove) ULG_HIP(c, hipMemcpyAsync(trace_delta, s.r_tdelta.p, nmove * 8, hipMemcpyDeviceToHost, c->stream));
+    if (trace_accept && nmove) ULG_HIP(c, hipMemcpyAsync(trace_accept, s.r_taccept.p, nmove, hipMemcpyDeviceToHost, c->stream));
+    if (trace_swap_d && npair) ULG_HIP(c, hipMemcpyAsync(trace_swap_d, s.r_tswapd.p, npair * 8, hipMemcpyDeviceToHost, c->stream));
+    if (trace_swap_accept && npair)
+        ULG_HIP(c, hipMemcpyAsync(trace_swap_accept, s.r_tswapacc.p, npair, hipMemcpyDeviceToHost, c->stream));
+    if (accepted) ULG_HIP(c, hipMemcpyAsync(accepted, s.d_accepted.p, (size_t)L * R * 8, hipMemcpyDeviceToHost, c->stream));
+    if (swaps && R > 1) ULG_HIP(c, hipMemcpyAsync(swaps, s.d_swaps.p, (size_t)L * (R - 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    ULG_HIP(c, hipStreamSynchronize(c->stream));
+    if (records) *records = recs;
+    return ULG_OK;
+}
+
+int ulg_order_mc3_state(ulg_ctx *c, uint8_t *order, double *terms, int64_t *replica, int64_t *step) {
+    if (!c) return ULG_ERR_ARG;
+    if (!c->mcmc || !c->mcmc->ready || !c->mcmc->rungs) return set_err(c, ULG_ERR_STATE, "ulg_order_mc3_state: no ulg_order_mc3_begin");
+    OrderMcmcState &s = *c->mcmc;
+    const int n = s.n, R = s.rungs;
+    const size_t reps = (size_t)s.chains * (size_t)R, cells = reps * (size_t)n;
+    if (order || terms || replica) {
+        // the device keeps the state by replica; the caller reads it by rung
+        std::vector<uint8_t> perm(reps), ord(order ? cells : 0);
+        std::vector<double> trm(terms ? cells : 0);
+        ULG_HIP(c, hipSetDevice(c->device));
+        ULG_HIP(c, hipMemcpyAsync(perm.data(), s.d_perm.p, reps, hipMemcpyDeviceToHost, c->stream));
+        if (order) ULG_HIP(c, hipMemcpyAsync(ord.data(), s.d_order.p, cells, hipMemcpyDeviceToHost, c->stream));
+        if (terms) ULG_HIP(c, hipMemcpyAsync(trm.data(), s.d_terms.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
+        ULG_HIP(c, hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k < reps; ++k) {
+            const size_t from = k - k % (size_t)R + perm[k];
+            if (replica) replica[k] = (int64_t)from;
+            if (order) std::copy(ord.begin() + from * n, ord.begin() + (from + 1) * n, order + k * n);
+            if (terms) std::copy(trm.begin() + from * n, trm.begin() + (from + 1) * n, terms + k * n);
+        }
+    }
+    if (step) *step = s.step;
     return ULG_OK;
 }
 

@@ -61,6 +61,32 @@ ULG_POST_HD bool mcmc_accept(double delta, uint64_t u_acc) {
     return (u_acc >> 12) < post_weight_q(delta);
 }
 
+// ---- tempered ladders (ulg_order_mc3_*; contract: include/ulg.h, "Metropolis-coupled order MCMC")
+constexpr int kMc3MaxRungs = 16;
+constexpr uint32_t kMc3SwapDomain = 64;  // moves and parent sets take the domains 0 .. 63 (n <= 63)
+
+// The move's rule on rung r: beta times delta is one FP64 multiply, and
+// beta = 1 gives delta's own bits, so rung 0 decides as mcmc_accept does.
+ULG_POST_HD bool mc3_accept(double beta, double delta, uint64_t u_acc) {
+    if (!(delta > -INFINITY)) return false;
+    if (delta >= 0.0) return true;
+    return (u_acc >> 12) < post_weight_q(beta * delta);
+}
+
+// Round x considers the pairs (r, r + 1) with r = x (mod 2) and r + 1 < R: disjoint
+ULG_POST_HD bool mc3_pair_considered(int64_t x, int r, int rungs) { return r + 1 < rungs && (((int64_t)r ^ x) & 1) == 0; }
+
+// The exchange of rungs r and r + 1 whose replicas' full sums are S_r and S_next:
+// two subtractions and one multiply, each rounded on its own.
+ULG_POST_HD double mc3_swap_d(double beta_r, double beta_next, double S_r, double S_next) {
+    const double db = beta_r - beta_next, ds = S_next - S_r;
+    return db * ds;
+}
+ULG_POST_HD bool mc3_swap_accept(double d, uint64_t u) {
+    if (d >= 0.0) return true;
+    return (u >> 12) < post_weight_q(d);
+}
+
 // sum of q[0 .. count) as lo + 2^64 hi
 ULG_POST_HD LxCount mcmc_sum_q(const uint64_t *q, int64_t count) {
     LxCount T{0, 0};

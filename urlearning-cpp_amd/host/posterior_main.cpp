@@ -74,8 +74,19 @@
 // with one table, and also with a table per chain when Z > 0: which chain an
 // order of probability 0 belongs to is not reported, so the chains' counts
 // are not known (a chain never records such an order; Z is then 0).  -o's file is the same with and without it.
+// --temper R (with --mcmc; 2 <= R <= 16) runs the chains as Metropolis-coupled
+// ladders (ulg_order_mc3_*): --chains then counts ladders of R rungs with the
+// geometric inverse temperatures beta_r = B^(r / (R - 1)) (--beta-min B,
+// 0 < B < 1, default 0.1) and an exchange round after every E steps
+// (--swap-every E, default 10); B and E are untuned starting points.  Only the
+// cold rung is recorded, so everything downstream is as without it; the
+// acceptance printed is the cold rung's, and the line gains
+//   , R rungs, swap acceptance = a01/a12/...
+// the accepted share of each pair's rounds, averaged over the ladders.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
-// (--seed, -g, --uniform, --mcmc or a feature file without --sample,
+// (--temper without --mcmc or outside 2..16, --beta-min or --swap-every without
+// --temper or with a bad value;
+// --seed, -g, --uniform, --mcmc or a feature file without --sample,
 // --uniform-edges without --uniform, --chains, --burn or --thin without
 // --mcmc, --rb-edges without --mcmc or with more than 2^22 samples, -s with
 // --mcmc, a K that is not a positive integer, and --thin, --burn and K / C that
@@ -135,6 +146,11 @@ int main(int argc, char **argv) {
                                      "read the R-hat that is printed)."},
             {"", "burn", true, "", "Steps every chain makes before its first record (with --mcmc; default 5000, untuned)."},
             {"", "thin", true, "", "A record after every this many steps (with --mcmc; default 100, untuned)."},
+            {"", "temper", true, "", "Run every chain as a ladder of this many tempered rungs, 2..16, that exchange states "
+                                     "(with --mcmc; --chains then counts ladders and only the cold rung is recorded)."},
+            {"", "beta-min", true, "", "The hottest rung's inverse temperature, between 0 and 1; the rungs are geometric "
+                                       "(with --temper; default 0.1, untuned)."},
+            {"", "swap-every", true, "", "An exchange round after every this many steps (with --temper; default 10, untuned)."},
             {"", "rb-edges", true, "", "Write the Rao-Blackwellised edge posteriors of the recorded orders here, in -o's format "
                                        "(with --mcmc; at most 4194304 samples)."},
         },
@@ -182,12 +198,29 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "posterior: --rb-edges needs --mcmc\n");
         return 2;
     }
-    long long chains = 256, burn = 5000, thin = 100;
+    const bool temper = args.has("temper");
+    if ((temper && !mcmc) || (!temper && (args.has("beta-min") || args.has("swap-every")))) {
+        std::fprintf(stderr, "posterior: --temper needs --mcmc, --beta-min and --swap-every need --temper\n");
+        return 2;
+    }
+    long long chains = 256, burn = 5000, thin = 100, rungs = 1, swap_every = 10;
+    double beta_min = 0.1;
+    if (args.has("beta-min")) {
+        const std::string t = args.get("beta-min");
+        char *end = nullptr;
+        errno = 0;
+        beta_min = std::strtod(t.c_str(), &end);
+        if (t.empty() || errno || *end || !(beta_min > 0.0) || !(beta_min < 1.0)) {
+            std::fprintf(stderr, "posterior: --beta-min takes a number between 0 and 1, not '%s'\n", t.c_str());
+            return 2;
+        }
+    }
     {
         const struct {
             const char *name;
             long long *value, least, most;
-        } ints[3] = {{"chains", &chains, 1, 1 << 20}, {"burn", &burn, 0, 1ll << 40}, {"thin", &thin, 1, 1ll << 40}};
+        } ints[5] = {{"chains", &chains, 1, 1 << 20}, {"burn", &burn, 0, 1ll << 40}, {"thin", &thin, 1, 1ll << 40},
+                     {"temper", &rungs, 2, 16}, {"swap-every", &swap_every, 1, 1ll << 40}};
         for (const auto &o : ints) {
             if (!args.has(o.name)) continue;
             const std::string t = args.get(o.name);
@@ -200,6 +233,10 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+    }
+    if (chains * rungs > (1 << 20)) {
+        std::fprintf(stderr, "posterior: --chains x --temper is at most 1048576\n");
+        return 2;
     }
     if (args.has("sample")) {
         const std::string k = args.get("sample");
@@ -272,7 +309,9 @@ int main(int argc, char **argv) {
         const long long steps = thin * (burn / thin + recs);  // the step of the last record; >= burn + 1, < 2^62 (checked above)
         int64_t got = 0;
         std::vector<double> m_ls;
-        std::vector<int64_t> m_acc((size_t)chains);
+        std::vector<int64_t> m_acc((size_t)(chains * rungs)), m_swaps((size_t)(chains * (rungs - 1)));
+        std::vector<double> betas((size_t)rungs, 1.0);
+        for (long long r = 1; r < rungs; ++r) betas[(size_t)r] = std::pow(beta_min, (double)r / (double)(rungs - 1));  // ulg.geometric_betas
         try {
             if (recs > (1ll << 46) / (chains * n)) throw std::length_error("records");  // the products below stay far inside size_t
             m_par.resize((size_t)recs * chains * n);
@@ -284,10 +323,19 @@ int main(int argc, char **argv) {
             ulg_destroy(ctx);
             return 1;
         }
-        if (ulg_order_mcmc_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, seed, nullptr) != ULG_OK ||
-            ulg_order_mcmc_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != ULG_OK ||
-            ulg_order_mcmc_run(ctx, steps - burn, thin, m_ord.data(), m_ls.data(), m_par.data(), m_lw.data(), m_acc.data(), nullptr,
-                               nullptr, &got) != ULG_OK) {
+        const bool ran =
+            temper ? ulg_order_mc3_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, (int)rungs, betas.data(),
+                                         swap_every, seed, nullptr) == ULG_OK &&
+                         ulg_order_mc3_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr, nullptr) == ULG_OK &&
+                         ulg_order_mc3_run(ctx, steps - burn, thin, m_ord.data(), m_ls.data(), m_par.data(), m_lw.data(), m_acc.data(),
+                                           m_swaps.data(), nullptr, nullptr, nullptr, nullptr, &got) == ULG_OK
+                   : ulg_order_mcmc_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, seed, nullptr) == ULG_OK &&
+                         ulg_order_mcmc_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) ==
+                             ULG_OK &&
+                         ulg_order_mcmc_run(ctx, steps - burn, thin, m_ord.data(), m_ls.data(), m_par.data(), m_lw.data(), m_acc.data(),
+                                            nullptr, nullptr, &got) == ULG_OK;
+        if (!ran) {
             std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
             ulg_destroy(ctx);
             return 1;
@@ -298,7 +346,7 @@ int main(int argc, char **argv) {
             return 1;
         }
         long long accepted = 0;
-        for (int64_t a : m_acc) accepted += a;
+        for (size_t k = 0; k < m_acc.size(); k += (size_t)rungs) accepted += m_acc[k];  // the cold rung's (every chain's without --temper)
         // Gelman-Rubin over the (recs, chains) log scores: ulg.order_rhat, every sum over its index ascending
         double rhat = NAN;
         if (recs >= 2 && chains >= 2) {
@@ -322,12 +370,28 @@ int main(int argc, char **argv) {
             B = R * B / (C - 1);
             if (W > 0) rhat = std::sqrt(((R - 1) / R * W + B / R) / W);
         }
-        char line[256], rh[32];
+        char line[512], rh[32];
         if (std::isnan(rhat)) std::snprintf(rh, sizeof rh, "n/a");
         else std::snprintf(rh, sizeof rh, "%.3f", rhat);
         std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
                       steps, (double)accepted / ((double)chains * (double)steps), rh);
         mcmc_line = line;
+        if (temper) {
+            // pair (r, r + 1) is considered in the rounds x = 1 .. steps / E with x = r (mod 2)
+            const long long rounds = steps / swap_every;
+            mcmc_line.pop_back();
+            std::snprintf(line, sizeof line, ", %lld rungs, swap acceptance = ", rungs);
+            mcmc_line += line;
+            for (long long r = 0; r + 1 < rungs; ++r) {
+                const long long tried = r % 2 ? (rounds + 1) / 2 : rounds / 2;
+                long long sum = 0;
+                for (long long l = 0; l < chains; ++l) sum += m_swaps[(size_t)(l * (rungs - 1) + r)];
+                if (tried) std::snprintf(line, sizeof line, "%s%.3f", r ? "/" : "", (double)sum / ((double)chains * (double)tried));
+                else std::snprintf(line, sizeof line, "%sn/a", r ? "/" : "");
+                mcmc_line += line;
+            }
+            mcmc_line += "\n";
+        }
         if (rb) {
             // a table per chain where that gives a standard error and fits; sample k = record k / chains of chain k % chains
             const long long groups = chains >= 2 && samples >= chains && 8 * chains * n * n <= (1ll << 28) ? chains : 1;

@@ -105,6 +105,11 @@ def lib():
             L.ulg_order_mcmc_run.argtypes = [P, I64, I64, P, P, P, P, P, P, P, C.POINTER(I64)]
             L.ulg_order_mcmc_state.argtypes = [P, P, P, C.POINTER(I64)]
             L.ulg_order_score.argtypes = [P, I64, P, P]
+        if hasattr(L, "ulg_order_mc3_begin"):  # ... or from before the tempered ladders
+            L.ulg_order_mc3_begin.argtypes = [P, I, P, P, P, I, I64, I, P, I64, C.c_uint64, P]
+            L.ulg_order_mc3_begin_from_scores.argtypes = [P, I64, I, P, I64, C.c_uint64, P]
+            L.ulg_order_mc3_run.argtypes = [P, I64, I64] + [P] * 10 + [C.POINTER(I64)]
+            L.ulg_order_mc3_state.argtypes = [P, P, P, P, C.POINTER(I64)]
         if hasattr(L, "ulg_order_edges"):  # ... or from before the Rao-Blackwellised edges
             L.ulg_order_edges.argtypes = [P, I64, P, I64, P, C.POINTER(I64)]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
@@ -174,6 +179,17 @@ def uniform_prior_weights(log_ext):
         raise ULGError("uniform_prior_weights: a sample without a linear extension (log_ext not finite): not a sampled DAG")
     bits = min(52, 62 - (le.shape[0] - 1).bit_length())  # (K - 1).bit_length() = ceil(log2 K)
     return np.floor(np.ldexp(np.exp(le.min() - le), bits)).astype(np.uint64)
+
+
+def geometric_betas(rungs, beta_min=0.1):
+    """The inverse temperatures of a ladder of `rungs` rungs: beta_r = beta_min ** (r / (rungs - 1)), float64,
+    beta_0 = 1.0 exactly; [1.0] for one rung."""
+    rungs = int(rungs)
+    if rungs < 1 or not 0.0 < beta_min < 1.0:
+        raise ULGError("geometric_betas: rungs must be >= 1 and beta_min in (0, 1)")
+    b = np.array([float(beta_min) ** (r / max(rungs - 1, 1)) for r in range(rungs)], dtype=np.float64)
+    b[0] = 1.0
+    return b
 
 
 def order_rhat(log_score):
@@ -847,6 +863,107 @@ class Context:
         zero = C.c_int64()
         self._check(lib().ulg_order_edges(self._h, o.shape[0], _ptr(o), groups, _ptr(edge), C.byref(zero)), "ulg_order_edges")
         return edge, zero.value
+
+    # ---- tempered ladders (Metropolis-coupled order MCMC) ----------------------
+    def _mc3_args(self, who, ladders, rungs, betas, init_order, n):
+        ladders, rungs = int(ladders), int(rungs)
+        b = np.ascontiguousarray(betas, dtype=np.float64).ravel()
+        if len(b) == 0:
+            b = np.zeros(1)
+        init, ip = self._mcmc_init_arg(who, init_order, ladders * rungs, n)
+        return ladders, rungs, b, init, ip
+
+    def order_mc3_begin(self, offsets, sets, scores, ladders, betas, swap_every=10, seed=0, init_order=None, device_ptrs=False):
+        """ulg_order_mc3_begin: `ladders` ladders of len(betas) rungs (betas[0] == 1.0, strictly descending,
+        > 0; ulg.geometric_betas makes one), an exchange round after every `swap_every` steps.  init_order
+        uint8 (ladders * rungs, n): row l * rungs + r is the order of the replica that starts on rung r."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(o) - 1
+        if device_ptrs:
+            sp, cp, keep = C.c_void_p(int(sets)), C.c_void_p(int(scores)), None
+        else:
+            s = np.ascontiguousarray(sets, dtype=np.uint64)
+            c = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.size == 0:
+                s, c = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.float32)
+            sp, cp, keep = _ptr(s), _ptr(c), (s, c)
+        ladders, rungs, b, init, ip = self._mc3_args("order_mc3_begin", ladders, len(np.atleast_1d(betas)), betas, init_order, n)
+        self._mcmc = self._mc3 = None  # a refused call leaves neither chains nor ladders
+        self._check(lib().ulg_order_mc3_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, ladders, rungs, _ptr(b),
+                                              int(swap_every), int(seed), ip), "ulg_order_mc3_begin")
+        self._mcmc, self._mc3 = (n, ladders), (n, ladders, rungs, int(swap_every))
+        del keep, init
+
+    def order_mc3_begin_from_scores(self, ladders, betas, swap_every=10, seed=0, init_order=None):
+        """ulg_order_mc3_begin_from_scores: the same on the lists of the last scoring call."""
+        n = self.n or 1
+        ladders, rungs, b, init, ip = self._mc3_args("order_mc3_begin_from_scores", ladders, len(np.atleast_1d(betas)), betas,
+                                                     init_order, n)
+        self._mcmc = self._mc3 = None
+        self._check(lib().ulg_order_mc3_begin_from_scores(self._h, ladders, rungs, _ptr(b), int(swap_every), int(seed), ip),
+                    "ulg_order_mc3_begin_from_scores")
+        self._mcmc, self._mc3 = (n, ladders), (n, ladders, rungs, int(swap_every))
+        del init
+
+    def _mc3_shape(self, who):
+        """(n, ladders, rungs, swap_every) of the ladders this object began; the library refuses first when
+        it holds none (no begin, a refused one, or chains begun since)."""
+        step = C.c_int64()
+        self._check(lib().ulg_order_mc3_state(self._h, None, None, None, C.byref(step)), who)
+        if getattr(self, "_mc3", None) is None:
+            raise ULGError(f"{who}: status 3: the ladders were not begun through this object")
+        return self._mc3 + (step.value,)
+
+    def order_mc3_state(self):
+        """ulg_order_mc3_state -> (order uint8 (ladders, rungs, n) and terms float64 (ladders, rungs, n) by
+        rung, replica int64 (ladders, rungs): the index of the replica now on each rung, step)."""
+        n, L, R, _, _ = self._mc3_shape("ulg_order_mc3_state")
+        order = np.zeros((L, R, n), dtype=np.uint8)
+        terms = np.zeros((L, R, n), dtype=np.float64)
+        replica = np.zeros((L, R), dtype=np.int64)
+        step = C.c_int64()
+        self._check(lib().ulg_order_mc3_state(self._h, _ptr(order), _ptr(terms), _ptr(replica), C.byref(step)), "ulg_order_mc3_state")
+        return order, terms, replica, step.value
+
+    def order_mc3_run(self, steps, thin=1, want_order=True, want_score=True, want_parents=True, want_weight=True, trace=False):
+        """ulg_order_mc3_run: every ladder `steps` steps on; the keys of order_mcmc_run over ladders (the
+        records are rung 0's), with "accepted" int64 (ladders, rungs) by rung, "swaps" int64 (ladders,
+        rungs - 1) by pair, and with trace "trace_delta" / "trace_accept" (steps, ladders, rungs) and
+        "trace_swap_d" float64 / "trace_swap_accept" uint8 (rounds, ladders, rungs - 1): -inf / 0 for a
+        pair its round does not consider."""
+        n, L, R, E, t0 = self._mc3_shape("ulg_order_mc3_run")
+        steps, thin = int(steps), int(thin)
+        ok = steps >= 0 and thin >= 1
+        recs = (t0 + steps) // thin - t0 // thin if ok else 0
+        rounds = (t0 + steps) // E - t0 // E if ok else 0
+        want_weight = want_weight and want_parents
+        out = {}
+        try:
+            if want_order:
+                out["order"] = np.zeros((recs, L, n), dtype=np.uint8)
+            if want_score:
+                out["log_score"] = np.zeros((recs, L), dtype=np.float64)
+            if want_parents:
+                out["parents"] = np.zeros((recs, L, n), dtype=np.uint64)
+            if want_weight:
+                out["log_weight"] = np.zeros((recs, L), dtype=np.float64)
+            if trace:
+                out["trace_delta"] = np.zeros((max(steps, 0), L, R), dtype=np.float64)
+                out["trace_accept"] = np.zeros((max(steps, 0), L, R), dtype=np.uint8)
+                out["trace_swap_d"] = np.zeros((rounds, L, R - 1), dtype=np.float64)
+                out["trace_swap_accept"] = np.zeros((rounds, L, R - 1), dtype=np.uint8)
+        except (MemoryError, ValueError) as e:
+            raise ULGError(f"ulg_order_mc3_run: status 4: {recs} records of {L} ladders do not fit the host memory ({e})") from None
+        out["accepted"] = np.zeros((L, R), dtype=np.int64)
+        out["swaps"] = np.zeros((L, R - 1), dtype=np.int64)
+        got = C.c_int64()
+        arg = lambda name: _ptr(out[name]) if name in out and out[name].size else None  # noqa: E731
+        self._check(lib().ulg_order_mc3_run(self._h, steps, thin, arg("order"), arg("log_score"), arg("parents"), arg("log_weight"),
+                                            _ptr(out["accepted"]), arg("swaps"), arg("trace_delta"), arg("trace_accept"),
+                                            arg("trace_swap_d"), arg("trace_swap_accept"), C.byref(got)), "ulg_order_mc3_run")
+        assert got.value == recs
+        out["records"], out["step"] = recs, t0 + steps
+        return out
 
     def bestscore(self, variables, S):
         v = np.ascontiguousarray(variables, dtype=np.int32)

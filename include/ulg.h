@@ -1075,6 +1075,94 @@ int ulg_order_mc3_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *re
 int ulg_order_edges(ulg_ctx *ctx, int64_t count, const uint8_t *orders, int64_t groups,
                     uint64_t *edge, int64_t *zero);
 
+/* Partition MCMC (Kuipers & Moffa 2017): posterior DAG samples under the prior
+ * UNIFORM over DAGs of the stored families, 1 <= n <= 63, with no 2^n table.
+ * Every call above samples the order-modular posterior, in which a DAG counts
+ * once per linear extension; these chains do not.  A state is an ordered
+ * partition (B_0, .., B_{m-1}) of the variables, every part non-empty.  For v
+ * in B_j: A_v = B_0 | .. | B_{j-1} (allowed parents), R_v = B_{j-1} (required;
+ * 0 for j = 0).  A stored set P of v is ELIGIBLE iff P subset of A_v and
+ * (j = 0 or P & R_v != 0); in part 0 only the empty set is.  Every DAG of
+ * stored families belongs to exactly one (partition, eligible choice): B_0 is
+ * its sources, B_1 the sources of the rest, and so on.  With T_v = the sum of
+ * w_v(P) over eligible P the chain's law is p(partition) proportional to
+ * prod_v T_v, and P drawn with probability w_v(P) / T_v for every v gives the
+ * DAG with probability proportional to prod_v w_v(Pa_v).
+ * Input, validation, chains, seed: as "Order MCMC" above.
+ *   term       a_v = ln T_v: the order term's computation (m, q_i, the 128-bit
+ *              sum, a = m + log(y)) over the eligible entries; -inf without one.
+ *              A function of (v's list, A_v, R_v) alone.
+ *   draws      the order MCMC's Philox counter (lo32(t), hi32(t), c, d).
+ *              d = 0: the move of step t (w0..w3).  d = 65: U_acc = w0 | w1 <<
+ *              32 and the split mask r = w2 | w3 << 32.  d = 1 + v: the parent
+ *              set of variable v of a record, U_set = w0 | w1 << 32.
+ *   move       kind = w0 >> 30 of the d = 0 draw (the mix is untuned).
+ *              kind 0, swap: v = mulhi32(w1, n), w' = mulhi32(w2, n-1), w = w'
+ *                + (w' >= v).  Both in one part: a no-op.  Else v and w
+ *                exchange parts; rho = 1.
+ *              kind 1 or 2, relocate: v = mulhi32(w1, n), tau = mulhi32(w2,
+ *                2m+1).  tau odd: v joins part k = (tau-1)/2.  tau even: v
+ *                becomes a new singleton part at gap g = tau/2 (gap g lies
+ *                before part g, gap m after the last part; indices of the
+ *                state before the move).  v leaves its part j; an emptied part
+ *                is deleted.  A no-op if k = j, or if v was a singleton and g
+ *                is j or j+1.  rho = (2m+1) / (2m'+1), m' the new number of
+ *                parts.
+ *              kind 3: j = mulhi32(w1, m).  Bit 29 of w0 set, split: B_j
+ *                becomes L = B_j & r below U = B_j & ~r; a no-op if either is
+ *                empty; rho = 2^k m / (m+1), k = |B_j|.  Bit 29 clear, join:
+ *                B_j and B_j+1 become one part; a no-op if j = m-1; rho =
+ *                2^-k m / (m-1), k the size of the union.
+ *              n = 1: nothing is proposed.  A no-op counts as a rejected step.
+ *   acceptance D = the variables whose pair (A_v, R_v) differs between the two
+ *              states; their terms are recomputed as a'_v.  delta = ((sum_{v
+ *              in D ascending} a'_v) - (sum_{v in D ascending} a_v)) + ln rho,
+ *              FP64 in that order, ln rho by part_log_rho
+ *              (csrc/partition_mcmc_dev.h).  Rejected if any a'_v = -inf (delta
+ *              is then -inf); else the order MCMC's rule on (delta, U_acc).
+ *   records    after every step t with t mod thin = 0: part[idx n + v] = the
+ *              index of v's part, parts[idx] = m, log_score[idx] = sum_{v
+ *              ascending} a_v over all n and, if asked, a DAG: for each v,
+ *              x_i = (double) s_i - a_v over its entries in list order, 0
+ *              weight for an ineligible one, q = floor(exp(x_i) 2^52), the
+ *              sampler's pick with U_set; parents[idx n + v], log_weight[idx]
+ *              = sum over v ascending of (double) s_v(Pa_v).  idx = r chains +
+ *              c.  The variables by part, ascending within a part, are a
+ *              topological order of the record's DAG; ulg_dag_features takes
+ *              `parents` unchanged.
+ * Chain c depends on (lists, seed, c, its initial state) alone -- not on the
+ * number of chains, options "mcmc_waves" and "mcmc_launch_steps" (both serve
+ * these chains too) or the split over calls: run(a); run(b) equals run(a + b)
+ * bit for bit.
+ * init_part: chains n bytes, row c = chain c's part indices by variable, which
+ * must use exactly 0 .. m-1; NULL: every variable in part 0, the empty DAG.
+ * ulg_partition_mcmc_run: ulg_order_mcmc_run's outputs and sizes, with part
+ * (records chains n bytes) and parts (records chains int32) for order;
+ * trace_delta holds delta above (-inf for a no-op).  ulg_partition_mcmc_state:
+ * part, terms[c n + v] and *step as they stand.  ulg_partition_score:
+ * terms[k n + v] of `count` given partitions on the lists of the last begin,
+ * the same device function, the same bits.
+ * The chains are a struct of their own beside the order chains' and the
+ * ladders', on the same device copy of the lists; freed by the same events.  A
+ * begin of any of the three families ends the other two (a refused one too);
+ * run, state or score of the wrong family is ULG_ERR_STATE, as is
+ * ulg_order_score or ulg_order_edges after a partition begin.
+ * Errors: as ulg_order_mcmc_begin; ULG_ERR_ARG also for an init_part (or
+ * score) row that does not use exactly 0 .. m-1, and, naming the chain and the
+ * variable, for an initial state with a -inf term: with NULL, a variable whose
+ * list lacks the empty set. */
+int ulg_partition_mcmc_begin(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
+                             const float *scores, int device_ptrs, int64_t chains,
+                             uint64_t seed, const uint8_t *init_part);
+int ulg_partition_mcmc_begin_from_scores(ulg_ctx *ctx, int64_t chains, uint64_t seed,
+                                         const uint8_t *init_part);
+int ulg_partition_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *part,
+                           int32_t *parts, double *log_score, uint64_t *parents,
+                           double *log_weight, int64_t *accepted, double *trace_delta,
+                           uint8_t *trace_accept, int64_t *records);
+int ulg_partition_mcmc_state(ulg_ctx *ctx, uint8_t *part, double *terms, int64_t *step);
+int ulg_partition_score(ulg_ctx *ctx, int64_t count, const uint8_t *part, double *terms);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the

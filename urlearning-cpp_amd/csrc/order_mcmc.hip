@@ -46,6 +46,7 @@
 namespace ulg {
 
 void order_mcmc_delete(ulg_ctx *c) {
+    partition_mcmc_delete(c);  // its chains read these lists
     delete c->mcmc;
     c->mcmc = nullptr;
 }
@@ -613,21 +614,23 @@ int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_
 
 // The lists are on the device in s (variable order) with s.n and s.total set,
 // s.offsets their offsets on the host: the checks, the initial orders, the terms.
+// lists_only: the checks alone, for the partition MCMC (partition_mcmc.hip), which keeps its own chains.
 int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains, uint64_t seed, const uint8_t *init_order,
-          const char *what = "chain") {
+          const char *what = "chain", bool lists_only = false) {
     const std::vector<int64_t> &offs = s.offsets;
     const int n = s.n;
     s.ready = false;
     DevBuf<unsigned long long> table;  // the call's own
     const uint64_t slots = table_slots(s.total);
     int rc;
-    if ((rc = ensure(c, table, (size_t)slots)) || (rc = ensure(c, s.d_err, 2)) || (rc = ensure(c, s.d_order, (size_t)(chains * n))) ||
-        (rc = ensure(c, s.d_terms, (size_t)(chains * n))) || (rc = ensure(c, s.d_accepted, (size_t)chains)))
+    if ((rc = ensure(c, table, (size_t)slots)) || (rc = ensure(c, s.d_err, 2))) return rc;
+    if (!lists_only && ((rc = ensure(c, s.d_order, (size_t)(chains * n))) || (rc = ensure(c, s.d_terms, (size_t)(chains * n))) ||
+                        (rc = ensure(c, s.d_accepted, (size_t)chains))))
         return rc;
     static const unsigned int err0[2] = {0u, 0xFFFFFFFFu};  // static: the copy's source outlives every return
     ULG_HIP(c, hipMemcpyAsync(s.d_err.p, err0, sizeof err0, hipMemcpyHostToDevice, c->stream));
     ULG_HIP(c, hipMemsetAsync(table.p, 0, (size_t)slots * 8, c->stream));
-    ULG_HIP(c, hipMemsetAsync(s.d_accepted.p, 0, (size_t)chains * 8, c->stream));
+    if (!lists_only) ULG_HIP(c, hipMemsetAsync(s.d_accepted.p, 0, (size_t)chains * 8, c->stream));
     int64_t longest = 1;
     for (int v = 0; v < n; ++v) longest = std::max(longest, offs[v + 1] - offs[v]);
     prof_begin(c, "mcmc_check_lists");
@@ -646,6 +649,7 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
         msg.pop_back();
         return set_err(c, ULG_ERR_ARG, msg);
     }
+    if (lists_only) return ULG_OK;
     if (init_order) {
         ULG_HIP(c, hipMemcpyAsync(s.d_order.p, init_order, (size_t)(chains * n), hipMemcpyHostToDevice, c->stream));
         ULG_HIP(c, hipStreamSynchronize(c->stream));  // init_order is the caller's again, whatever returns below
@@ -684,7 +688,8 @@ void launch_run(ulg_ctx *c, const RunArgs &a) {
 // replicas of ladders: `what` names them in a refusal, per_chain is what a
 // ladder's replica holds beyond a chain's bytes)
 int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
-                   int device_ptrs, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what, double per_chain) {
+                   int device_ptrs, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what, double per_chain,
+                   bool lists_only = false) {
     if (!offsets) return set_err(c, ULG_ERR_ARG, who + ": bad arguments");
     if (int rc = check_begin_args(c, who, n, chains, init_order, what)) return rc;
     for (int v = 0; v < n; ++v)
@@ -710,12 +715,12 @@ int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *off
         ULG_HIP(c, hipMemcpyAsync(s.d_scores.p, scores + offsets[0], (size_t)total * 4, kind, c->stream));
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only);
 }
 
 // ... and on the lists of the last scoring call
 int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what,
-                    double per_chain) {
+                    double per_chain, bool lists_only = false) {
     if (int rc0 = finish_pending(c)) return rc0;
     if (!c->scored) return set_err(c, ULG_ERR_STATE, who + ": no scoring call yet");
     const int n = c->n;
@@ -756,7 +761,7 @@ int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t
         }
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only);
 }
 
 // ---- ladders
@@ -802,17 +807,35 @@ void launch_mc3(ulg_ctx *c, const OrderMcmcState &s, int64_t t_begin, int64_t ns
 
 }  // namespace
 
+namespace ulg {
+
+// The partition MCMC's lists: uploaded and checked as a begin's, kept in the
+// order MCMC's state with its chains ended.
+int order_mcmc_take_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
+                          int device_ptrs, int64_t chains) {
+    if (c->mcmc) c->mcmc->ready = false;
+    return begin_on_lists(c, who, n, offsets, sets, scores, device_ptrs, chains, 0, nullptr, "chain", 0.0, true);
+}
+int order_mcmc_take_scored(ulg_ctx *c, const std::string &who, int64_t chains) {
+    if (c->mcmc) c->mcmc->ready = false;
+    return begin_on_scored(c, who, chains, 0, nullptr, "chain", 0.0, true);
+}
+
+}  // namespace ulg
+
 extern "C" {
 
 int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_t *sets, const float *scores, int device_ptrs,
                          int64_t chains, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
+    partition_mcmc_end(c);  // a begin of either family ends the partition chains
     if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
     return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0);
 }
 
 int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
+    partition_mcmc_end(c);  // a begin of either family ends the partition chains
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
     return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0);
 }
@@ -948,6 +971,7 @@ int ulg_order_score(ulg_ctx *c, int64_t count, const uint8_t *orders, double *te
 int ulg_order_mc3_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_t *sets, const float *scores, int device_ptrs,
                         int64_t ladders, int rungs, const double *betas, int64_t swap_every, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
+    partition_mcmc_end(c);  // a begin of either family ends the partition chains
     const std::string who = "ulg_order_mc3_begin";
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin: a refused begin leaves neither chains nor ladders
     if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;
@@ -960,6 +984,7 @@ int ulg_order_mc3_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_
 int ulg_order_mc3_begin_from_scores(ulg_ctx *c, int64_t ladders, int rungs, const double *betas, int64_t swap_every, uint64_t seed,
                                     const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
+    partition_mcmc_end(c);  // a begin of either family ends the partition chains
     const std::string who = "ulg_order_mc3_begin_from_scores";
     if (c->mcmc) c->mcmc->ready = false;
     if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;

@@ -25,6 +25,7 @@ struct SearchState;
 struct PssState;
 struct PosteriorState;
 struct OrderMcmcState;
+struct PartitionMcmcState;
 
 struct ProfRec {
     std::string name;
@@ -187,6 +188,8 @@ struct ulg_ctx : ulg::CtxStreams {
     // ---- order MCMC (order_mcmc.hip): its lists and chains, apart from the model averaging's ----
     ulg::OrderMcmcState *mcmc = nullptr;
     int64_t edges_grid = 0;       // ulg_get_info("edges_grid"): workgroups the last ulg_order_edges launched (order_edges.hip)
+    // ---- partition MCMC (partition_mcmc.hip): its chains, on the lists the order MCMC's state holds ----
+    ulg::PartitionMcmcState *pmcmc = nullptr;
 
     // ---- profiling ----
     bool prof = false;
@@ -226,7 +229,13 @@ void prof_collect(ulg_ctx *c);  // after a stream sync
 void graph_reset(ulg_ctx *c);   // drop the captured scoring graph (cbic.hip)
 void pss_delete(ulg_ctx *c);   // delete the context's PssState (pss.hip, where the type is complete)
 void posterior_delete(ulg_ctx *c);  // ... and its PosteriorState (posterior.hip)
-void order_mcmc_delete(ulg_ctx *c);  // ... and its OrderMcmcState (order_mcmc.hip)
+void order_mcmc_delete(ulg_ctx *c);  // ... and its OrderMcmcState (order_mcmc.hip), the PartitionMcmcState with it
+void partition_mcmc_delete(ulg_ctx *c);  // partition_mcmc.hip
+void partition_mcmc_end(ulg_ctx *c);     // its chains end (a begin of the order families); the struct stays
+// the partition MCMC's lists, uploaded and checked into the OrderMcmcState, whose chains end (order_mcmc.hip)
+int order_mcmc_take_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
+                          int device_ptrs, int64_t chains);
+int order_mcmc_take_scored(ulg_ctx *c, const std::string &who, int64_t chains);
 
 // binomial table C(a, b), a < 64, b < kBinomK, clamped to uint32
 const std::vector<uint32_t> &host_binom();

@@ -83,8 +83,18 @@
 // acceptance printed is the cold rung's, and the line gains
 //   , R rungs, swap acceptance = a01/a12/...
 // the accepted share of each pair's rounds, averaged over the ladders.
+// --partition (with --mcmc) takes the samples from partition MCMC
+// (ulg_partition_mcmc_*): chains over ordered partitions whose DAGs follow the
+// prior UNIFORM over DAGs of the stored families, at every n <= 63, with no
+// linear-extension count.  --chains, --burn, --thin, --seed, -g, -o and the
+// feature files work as with --mcmc alone (the move mix, --burn and --thin are
+// untuned); a sample line lists the variables by part, ascending within a
+// part, which is a topological order of its DAG.  The line reads
+//   partition MCMC: C chains, <steps> steps each, acceptance = %.3f, mean parts = %.3f, R-hat(log score) = %.3f
+// Refused (exit 2) with --uniform and --uniform-edges -- the samples already
+// are uniform-prior -- and with --rb-edges and --temper, which are order-based.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
-// (--temper without --mcmc or outside 2..16, --beta-min or --swap-every without
+// (--partition without --mcmc or with the flags above; --temper without --mcmc or outside 2..16, --beta-min or --swap-every without
 // --temper or with a bad value;
 // --seed, -g, --uniform, --mcmc or a feature file without --sample,
 // --uniform-edges without --uniform, --chains, --burn or --thin without
@@ -142,6 +152,8 @@ int main(int argc, char **argv) {
                                        "occurs (with --sample)."},
             {"", "mcmc", false, "", "Take the samples from order MCMC instead of the exact tables: up to 63 variables, no ln Z "
                                     "(with --sample; not with -s)."},
+            {"", "partition", false, "", "Take the samples from partition MCMC: the prior uniform over DAGs, not the "
+                                         "order-modular one (with --mcmc; not with --uniform, --uniform-edges, --rb-edges, --temper)."},
             {"", "chains", true, "", "The number of chains, 1..1048576 (with --mcmc; default 256, an untuned starting point: "
                                      "read the R-hat that is printed)."},
             {"", "burn", true, "", "Steps every chain makes before its first record (with --mcmc; default 5000, untuned)."},
@@ -201,6 +213,16 @@ int main(int argc, char **argv) {
     const bool temper = args.has("temper");
     if ((temper && !mcmc) || (!temper && (args.has("beta-min") || args.has("swap-every")))) {
         std::fprintf(stderr, "posterior: --temper needs --mcmc, --beta-min and --swap-every need --temper\n");
+        return 2;
+    }
+    const bool partition = args.has("partition");
+    if (partition && !mcmc) {
+        std::fprintf(stderr, "posterior: --partition needs --mcmc\n");
+        return 2;
+    }
+    if (partition && (uniform || args.has("uniform-edges") || rb || temper)) {
+        std::fprintf(stderr, "posterior: --partition does not go with --uniform or --uniform-edges (its samples already follow the "
+                             "uniform prior), nor with --rb-edges or --temper (both are order-based)\n");
         return 2;
     }
     long long chains = 256, burn = 5000, thin = 100, rungs = 1, swap_every = 10;
@@ -323,8 +345,14 @@ int main(int argc, char **argv) {
             ulg_destroy(ctx);
             return 1;
         }
+        std::vector<int32_t> m_parts(partition ? (size_t)recs * chains : 0);
         const bool ran =
-            temper ? ulg_order_mc3_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, (int)rungs, betas.data(),
+            partition ? ulg_partition_mcmc_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, seed, nullptr) == ULG_OK &&
+                            ulg_partition_mcmc_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                   nullptr) == ULG_OK &&
+                            ulg_partition_mcmc_run(ctx, steps - burn, thin, m_ord.data(), m_parts.data(), m_ls.data(), m_par.data(),
+                                                   m_lw.data(), m_acc.data(), nullptr, nullptr, &got) == ULG_OK
+            : temper ? ulg_order_mc3_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, (int)rungs, betas.data(),
                                          swap_every, seed, nullptr) == ULG_OK &&
                          ulg_order_mc3_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                            nullptr, nullptr) == ULG_OK &&
@@ -344,6 +372,20 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "posterior: %lld records per chain, not %lld\n", (long long)got, recs);
             ulg_destroy(ctx);
             return 1;
+        }
+        double mean_parts = 0.0;
+        if (partition) {
+            // a record's part indices become the variables by part, ascending within a part: a topological order
+            std::vector<uint8_t> row((size_t)n);
+            for (size_t k = 0; k < (size_t)recs * chains; ++k) {
+                int at = 0;
+                for (int j = 0; j < m_parts[k]; ++j)
+                    for (int v = 0; v < n; ++v)
+                        if (m_ord[k * n + v] == j) row[(size_t)at++] = (uint8_t)v;
+                std::copy(row.begin(), row.end(), m_ord.begin() + k * n);
+                mean_parts += (double)m_parts[k];
+            }
+            mean_parts /= (double)recs * (double)chains;
         }
         long long accepted = 0;
         for (size_t k = 0; k < m_acc.size(); k += (size_t)rungs) accepted += m_acc[k];  // the cold rung's (every chain's without --temper)
@@ -373,8 +415,13 @@ int main(int argc, char **argv) {
         char line[512], rh[32];
         if (std::isnan(rhat)) std::snprintf(rh, sizeof rh, "n/a");
         else std::snprintf(rh, sizeof rh, "%.3f", rhat);
-        std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
-                      steps, (double)accepted / ((double)chains * (double)steps), rh);
+        if (partition)
+            std::snprintf(line, sizeof line, "partition MCMC: %lld chains, %lld steps each, acceptance = %.3f, mean parts = %.3f, "
+                                             "R-hat(log score) = %s\n",
+                          chains, steps, (double)accepted / ((double)chains * (double)steps), mean_parts, rh);
+        else
+            std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
+                          steps, (double)accepted / ((double)chains * (double)steps), rh);
         mcmc_line = line;
         if (temper) {
             // pair (r, r + 1) is considered in the rounds x = 1 .. steps / E with x = r (mod 2)

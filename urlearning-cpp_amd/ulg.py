@@ -112,6 +112,12 @@ def lib():
             L.ulg_order_mc3_state.argtypes = [P, P, P, P, C.POINTER(I64)]
         if hasattr(L, "ulg_order_edges"):  # ... or from before the Rao-Blackwellised edges
             L.ulg_order_edges.argtypes = [P, I64, P, I64, P, C.POINTER(I64)]
+        if hasattr(L, "ulg_partition_mcmc_begin"):  # ... or the partition MCMC
+            L.ulg_partition_mcmc_begin.argtypes = [P, I, P, P, P, I, I64, C.c_uint64, P]
+            L.ulg_partition_mcmc_begin_from_scores.argtypes = [P, I64, C.c_uint64, P]
+            L.ulg_partition_mcmc_run.argtypes = [P, I64, I64] + [P] * 8 + [C.POINTER(I64)]
+            L.ulg_partition_mcmc_state.argtypes = [P, P, P, C.POINTER(I64)]
+            L.ulg_partition_score.argtypes = [P, I64, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -843,6 +849,102 @@ class Context:
             raise ULGError(f"order_score: orders must be (count, {n}), not {o.shape}")
         terms = np.zeros(o.shape, dtype=np.float64)
         self._check(lib().ulg_order_score(self._h, o.shape[0], _ptr(o), _ptr(terms)), "ulg_order_score")
+        return terms
+
+    # ---- partition MCMC ------------------------------------------------------
+    def partition_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_part=None, device_ptrs=False):
+        """ulg_partition_mcmc_begin on per-variable lists (as Context.posterior takes them): `chains` chains of
+        seed `seed` over ordered partitions, each from its row of init_part uint8 (chains, n) -- the part
+        index of every variable, exactly 0 .. m-1 used -- or, with None, from the empty DAG (all in part 0);
+        step 0.  The records' DAGs follow the prior uniform over DAGs, not the order-modular one."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, chains = len(o) - 1, int(chains)
+        if device_ptrs:
+            sp, cp, keep = C.c_void_p(int(sets)), C.c_void_p(int(scores)), None
+        else:
+            s = np.ascontiguousarray(sets, dtype=np.uint64)
+            c = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.size == 0:
+                s, c = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.float32)
+            sp, cp, keep = _ptr(s), _ptr(c), (s, c)
+        init, ip = self._mcmc_init_arg("partition_mcmc_begin", init_part, chains, n)
+        self._pmcmc = self._mcmc = None  # a begin of one family ends the others; a refused one leaves none
+        self._check(lib().ulg_partition_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip),
+                    "ulg_partition_mcmc_begin")
+        self._pmcmc = (n, chains)
+        del keep, init
+
+    def partition_mcmc_begin_from_scores(self, chains, seed=0, init_part=None):
+        """ulg_partition_mcmc_begin_from_scores: the same on the lists of the last scoring call."""
+        n, chains = self.n or 1, int(chains)
+        init, ip = self._mcmc_init_arg("partition_mcmc_begin_from_scores", init_part, chains, n)
+        self._pmcmc = self._mcmc = None
+        self._check(lib().ulg_partition_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_partition_mcmc_begin_from_scores")
+        self._pmcmc = (n, chains)
+        del init
+
+    def _pmcmc_shape(self, who):
+        """(n, chains) of the partition chains this object began and the library still holds."""
+        self._check(lib().ulg_partition_mcmc_state(self._h, None, None, None), who)
+        if getattr(self, "_pmcmc", None) is None:
+            raise ULGError(f"{who}: status 3: the last partition_mcmc_begin through this object was refused")
+        return self._pmcmc
+
+    def partition_mcmc_state(self):
+        """ulg_partition_mcmc_state -> (part uint8 (chains, n): the part of every variable, terms float64
+        (chains, n) by variable, step)."""
+        n, chains = self._pmcmc_shape("ulg_partition_mcmc_state")
+        part = np.zeros((chains, n), dtype=np.uint8)
+        terms = np.zeros((chains, n), dtype=np.float64)
+        step = C.c_int64()
+        self._check(lib().ulg_partition_mcmc_state(self._h, _ptr(part), _ptr(terms), C.byref(step)), "ulg_partition_mcmc_state")
+        return part, terms, step.value
+
+    def partition_mcmc_run(self, steps, thin=1, want_part=True, want_score=True, want_parents=True, want_weight=True, trace=False):
+        """ulg_partition_mcmc_run: order_mcmc_run's dict with "part" uint8 (R, chains, n) and "parts" int32
+        (R, chains) in the place of "order"; ulg.order_rhat takes its "log_score"."""
+        n, chains = self._pmcmc_shape("ulg_partition_mcmc_run")
+        steps, thin = int(steps), int(thin)
+        t0 = C.c_int64()
+        self._check(lib().ulg_partition_mcmc_state(self._h, None, None, C.byref(t0)), "ulg_partition_mcmc_state")
+        ok = steps >= 0 and thin >= 1
+        R = (t0.value + steps) // thin - t0.value // thin if ok else 0
+        want_weight = want_weight and want_parents
+        out = {}
+        try:
+            if want_part:
+                out["part"] = np.zeros((R, chains, n), dtype=np.uint8)
+                out["parts"] = np.zeros((R, chains), dtype=np.int32)
+            if want_score:
+                out["log_score"] = np.zeros((R, chains), dtype=np.float64)
+            if want_parents:
+                out["parents"] = np.zeros((R, chains, n), dtype=np.uint64)
+            if want_weight:
+                out["log_weight"] = np.zeros((R, chains), dtype=np.float64)
+            if trace:
+                out["trace_delta"] = np.zeros((max(steps, 0), chains), dtype=np.float64)
+                out["trace_accept"] = np.zeros((max(steps, 0), chains), dtype=np.uint8)
+        except (MemoryError, ValueError) as e:
+            raise ULGError(f"ulg_partition_mcmc_run: status 4: {R} records of {chains} chains do not fit the host memory ({e})") from None
+        out["accepted"] = np.zeros(chains, dtype=np.int64)
+        recs = C.c_int64()
+        arg = lambda name: _ptr(out[name]) if name in out else None  # noqa: E731
+        self._check(lib().ulg_partition_mcmc_run(self._h, steps, thin, arg("part"), arg("parts"), arg("log_score"), arg("parents"),
+                                                 arg("log_weight"), _ptr(out["accepted"]), arg("trace_delta"), arg("trace_accept"),
+                                                 C.byref(recs)), "ulg_partition_mcmc_run")
+        assert recs.value == R
+        out["records"], out["step"] = R, t0.value + steps
+        return out
+
+    def partition_score(self, part):
+        """ulg_partition_score: part uint8 (count, n), each row the part indices of an ordered partition ->
+        terms float64 (count, n) by variable, on the lists of the last partition_mcmc_begin."""
+        n, _ = self._pmcmc_shape("ulg_partition_score")
+        p = np.ascontiguousarray(part, dtype=np.uint8)
+        if p.ndim != 2 or p.shape[1] != n:
+            raise ULGError(f"partition_score: part must be (count, {n}), not {p.shape}")
+        terms = np.zeros(p.shape, dtype=np.float64)
+        self._check(lib().ulg_partition_score(self._h, p.shape[0], _ptr(p), _ptr(terms)), "ulg_partition_score")
         return terms
 
     def order_edges(self, orders, groups=1):

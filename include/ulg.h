@@ -1163,6 +1163,94 @@ int ulg_partition_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *p
 int ulg_partition_mcmc_state(ulg_ctx *ctx, uint8_t *part, double *terms, int64_t *step);
 int ulg_partition_score(ulg_ctx *ctx, int64_t count, const uint8_t *part, double *terms);
 
+/* Order search (Teyssier & Koller 2005): the best DAG a tabu search over
+ * linear orders finds, 1 <= n <= 63, on the lists alone.  An order's score is
+ * the sum over its positions of the best stored parent set inside the
+ * predecessors, so its maximum over orders is the optimal network of the
+ * stored families; the search is a heuristic and proves nothing.
+ * Input, validation: as "Order MCMC" above (offsets, sets, scores,
+ * device_ptrs); a variable's list longer than 2^32 - 1 entries is
+ * ULG_ERR_UNSUPPORTED.
+ *   best term  for variable v with predecessor set U: b_v(U) = the maximum of
+ *              (double) s_i over the entries with P_i subset of U, its parent
+ *              set the compatible entry of that value with the LEAST list
+ *              index; b = -inf without a compatible entry.  Scores compare as
+ *              numbers (-0 = +0; a maximum of -0 reads +0).
+ *   score      S(<) = the sum of b over the positions ascending, FP64 in that
+ *              order.
+ *   searches   C independent searches, 1 <= C <= 2^20.  The initial order of
+ *              search c is row c of init_order or, with NULL, the order MCMC's
+ *              shuffle (the draws of t = 0, chain c).  S_best, the best order
+ *              and its parent sets start as the initial ones, the idle count
+ *              and every pair's stamp at 0.
+ *   step       t = 1, 2, ..  With x, y at positions p, p+1 and U the set before
+ *              p, for every p in 0 .. n-2:
+ *                gain_p = (b_y(U) + b_x(U + y)) - (term_p + term_{p+1}),
+ *              two FP64 adds, then one subtract.  Swap p is TABU iff the pair
+ *              {x, y} was swapped at a step >= t - tenure since the stamps were
+ *              last cleared, ADMISSIBLE iff gain_p is finite and it is not tabu
+ *              or S + gain_p > S_best (aspiration).  The admissible swap of
+ *              largest gain is applied, ties to the least p, even if its gain
+ *              is <= 0: S <- S + gain (one add), the two terms and their
+ *              entries are replaced, the pair's stamp becomes t.  Without an
+ *              admissible swap nothing moves.
+ *   best       then, if S > S_best: the best order, its parent sets and S_best
+ *              are replaced and the idle count is 0; else the idle count rises
+ *              by one.
+ *   kick       when the idle count reaches `patience`: the order becomes the
+ *              best order and max(2, n / 4) transpositions are applied in turn,
+ *              transposition k of step t exchanging positions i, j of the order
+ *              MCMC's move arithmetic on the draw (t, c, d = 1 + k); a later
+ *              one may undo an earlier one.  All terms are recomputed, S is
+ *              their ascending sum, the stamps and the idle count are cleared;
+ *              then S > S_best replaces the best as above, else the idle count
+ *              is 1.  If the kicked order has a -inf term the transpositions
+ *              are undone: the search stands on the best order, terms
+ *              recomputed, S their ascending sum, stamps and idle count
+ *              cleared, and the kick is not counted.
+ *   n = 1      nothing moves and nothing is kicked.
+ * Search c is a fixed function of (lists, seed, c, its initial order, tenure,
+ * patience): not of C, the launch geometry (option "mcmc_waves", which serves
+ * these searches too), the steps per launch ("mcmc_launch_steps") or the split
+ * of steps over calls: run(a); run(b) equals run(a + b) bit for bit.  Every
+ * value is a maximum of float32 scores or a fixed FP64 expression of such.
+ * ulg_order_search_begin / _begin_from_scores: tenure in 0 .. 2^20, patience in
+ * 1 .. 2^31 - 1, init_order C n bytes or NULL; step = 0.
+ * ulg_order_search_run advances every search by `steps`; the steps since begin
+ * stay below 2^32.  best_score[c] = S_best, best_order (C n bytes),
+ * best_parents[c n + v] = the parent mask of variable v under the best order,
+ * moves[c], kicks[c] = the applied swaps and the counted kicks since begin.
+ * trace_gain / trace_pos (tests): the applied gain and p of step t at
+ * [(t - t0 - 1) C + c], -inf and 255 when nothing moved.  Every output is a
+ * host pointer and may be NULL.
+ * ulg_order_search_state: order (C n bytes), terms[c n + p], score[c] = S and
+ * *step as they stand; each may be NULL.
+ * ulg_order_best: the max-plus ulg_order_score, on the lists of the last
+ * search begin: terms[k n + p] = b of position p of order k and
+ * parents[k n + v] = the chosen set of variable v (0 beside a term of -inf);
+ * either may be NULL.  The same device function as the run's: the same bits.
+ * The searches are a struct of their own beside the chains', on the same
+ * device copy of the lists, freed by the same events.  A begin of this family
+ * ends the order chains, the ladders and the partition chains, and theirs end
+ * the searches (a refused begin too); a call of the wrong family is
+ * ULG_ERR_STATE.
+ * Errors: as ulg_order_mcmc_begin, with "search" for "chain" (4 n^2 + 18 n + 40
+ * B per search); ULG_ERR_ARG also for tenure or patience out of range and a
+ * step count that would pass 2^32 - 1. */
+int ulg_order_search_begin(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
+                           const float *scores, int device_ptrs, int64_t searches, uint64_t seed,
+                           int64_t tenure, int64_t patience, const uint8_t *init_order);
+int ulg_order_search_begin_from_scores(ulg_ctx *ctx, int64_t searches, uint64_t seed,
+                                       int64_t tenure, int64_t patience,
+                                       const uint8_t *init_order);
+int ulg_order_search_run(ulg_ctx *ctx, int64_t steps, double *best_score, uint8_t *best_order,
+                         uint64_t *best_parents, int64_t *moves, int64_t *kicks,
+                         double *trace_gain, uint8_t *trace_pos);
+int ulg_order_search_state(ulg_ctx *ctx, uint8_t *order, double *terms, double *score,
+                           int64_t *step);
+int ulg_order_best(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms,
+                   uint64_t *parents);
+
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
  * unrolled presence gather (layers <= 6), bit 4 = two-pass layers (the

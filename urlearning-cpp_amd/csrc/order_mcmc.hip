@@ -47,6 +47,7 @@ namespace ulg {
 
 void order_mcmc_delete(ulg_ctx *c) {
     partition_mcmc_delete(c);  // its chains read these lists
+    order_search_delete(c);    // ... as do the searches
     delete c->mcmc;
     c->mcmc = nullptr;
 }
@@ -829,6 +830,7 @@ int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64
                          int64_t chains, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
+    order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
     return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0);
 }
@@ -836,6 +838,7 @@ int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64
 int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
+    order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
     return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0);
 }
@@ -972,6 +975,7 @@ int ulg_order_mc3_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64_
                         int64_t ladders, int rungs, const double *betas, int64_t swap_every, uint64_t seed, const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
+    order_search_end(c);    // ... and the searches
     const std::string who = "ulg_order_mc3_begin";
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin: a refused begin leaves neither chains nor ladders
     if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;
@@ -985,6 +989,7 @@ int ulg_order_mc3_begin_from_scores(ulg_ctx *c, int64_t ladders, int rungs, cons
                                     const uint8_t *init_order) {
     if (!c) return ULG_ERR_ARG;
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
+    order_search_end(c);    // ... and the searches
     const std::string who = "ulg_order_mc3_begin_from_scores";
     if (c->mcmc) c->mcmc->ready = false;
     if (int rc = mc3_check_args(c, who, ladders, rungs, betas, swap_every)) return rc;

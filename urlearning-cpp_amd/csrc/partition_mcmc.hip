@@ -456,6 +456,7 @@ int ulg_partition_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const ui
     if (!c) return ULG_ERR_ARG;
     const std::string who = "ulg_partition_mcmc_begin";
     partition_mcmc_end(c);  // a begin that is refused, for whatever reason, leaves no chains of any family
+    order_search_end(c);
     if (c->mcmc) c->mcmc->ready = false;
     if (int rc = check_init(c, who, n, chains, init_part)) return rc;
     if (int rc = order_mcmc_take_lists(c, who, n, offsets, sets, scores, device_ptrs, chains)) return rc;
@@ -466,6 +467,7 @@ int ulg_partition_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t se
     if (!c) return ULG_ERR_ARG;
     const std::string who = "ulg_partition_mcmc_begin_from_scores";
     partition_mcmc_end(c);
+    order_search_end(c);
     if (c->mcmc) c->mcmc->ready = false;
     if (int rc = check_init(c, who, c->n, chains, init_part)) return rc;
     if (int rc = order_mcmc_take_scored(c, who, chains)) return rc;

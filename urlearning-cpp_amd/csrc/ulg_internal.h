@@ -26,6 +26,7 @@ struct PssState;
 struct PosteriorState;
 struct OrderMcmcState;
 struct PartitionMcmcState;
+struct OrderSearchState;
 
 struct ProfRec {
     std::string name;
@@ -190,6 +191,8 @@ struct ulg_ctx : ulg::CtxStreams {
     int64_t edges_grid = 0;       // ulg_get_info("edges_grid"): workgroups the last ulg_order_edges launched (order_edges.hip)
     // ---- partition MCMC (partition_mcmc.hip): its chains, on the lists the order MCMC's state holds ----
     ulg::PartitionMcmcState *pmcmc = nullptr;
+    // ---- order search (order_search.hip): its searches, on the same lists ----
+    ulg::OrderSearchState *osearch = nullptr;
 
     // ---- profiling ----
     bool prof = false;
@@ -229,9 +232,11 @@ void prof_collect(ulg_ctx *c);  // after a stream sync
 void graph_reset(ulg_ctx *c);   // drop the captured scoring graph (cbic.hip)
 void pss_delete(ulg_ctx *c);   // delete the context's PssState (pss.hip, where the type is complete)
 void posterior_delete(ulg_ctx *c);  // ... and its PosteriorState (posterior.hip)
-void order_mcmc_delete(ulg_ctx *c);  // ... and its OrderMcmcState (order_mcmc.hip), the PartitionMcmcState with it
+void order_mcmc_delete(ulg_ctx *c);  // ... and its OrderMcmcState (order_mcmc.hip), the PartitionMcmcState and OrderSearchState with it
 void partition_mcmc_delete(ulg_ctx *c);  // partition_mcmc.hip
 void partition_mcmc_end(ulg_ctx *c);     // its chains end (a begin of the order families); the struct stays
+void order_search_delete(ulg_ctx *c);    // order_search.hip
+void order_search_end(ulg_ctx *c);       // its searches end (a begin of the chains' families); the struct stays
 // the partition MCMC's lists, uploaded and checked into the OrderMcmcState, whose chains end (order_mcmc.hip)
 int order_mcmc_take_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
                           int device_ptrs, int64_t chains);

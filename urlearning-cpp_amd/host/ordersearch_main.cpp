@@ -1,0 +1,119 @@
+// ordersearch -- the best network an order-space tabu search finds on a .pss
+// score cache, for up to 63 variables (ulg_order_search_*; contract:
+// include/ulg.h, "Order search").  Past n ~ 30, where astar's tables end, this
+// is the tool that names a DAG; it is a heuristic and proves no optimality.
+//
+//   ordersearch <in.pss> [-n netFile] [--searches C] [--steps T] [--tenure K]
+//               [--patience P] [--seed S] [-r]
+//
+// The .pss is read as astar reads it (read_pss); scores = -costs.  netFile and
+// netFile.csv are astar's: "Var v, parents .." lines in the best order, and
+// the 0/1 matrix with row v, column u = 1 for u -> v.  One line is printed.
+// The defaults -- 256 searches, 20 n^2 steps, tenure n / 2, patience 4 n -- are
+// untuned starting points.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../../include/ulg.h"
+#include "cli_common.h"
+#include "io.h"
+
+int main(int argc, char **argv) {
+    ulgcli::Args args(
+        {
+            {"n", "netFile", true, "", "The file to which the best network found is written (and netFile.csv, its 0/1 matrix)."},
+            {"", "searches", true, "", "The number of independent searches, 1..1048576 (default 256, untuned)."},
+            {"", "steps", true, "", "Steps of every search (default 20 n^2, untuned)."},
+            {"", "tenure", true, "", "Steps a swapped pair stays tabu, 0..1048576 (default n / 2, untuned)."},
+            {"", "patience", true, "", "Steps without a new best before a search is kicked off its best order (default 4 n, untuned)."},
+            {"", "seed", true, "0", "The seed of the initial orders and the kicks."},
+            {"r", "random", false, "", "Take the seed from the clock instead."},
+            {"d", "device", true, "0", "The GPU to use."},
+            {"h", "help", false, "", "Show this help message."},
+        },
+        {"scoreFile"});
+    std::string err;
+    if (!args.parse(argc, argv, err)) {
+        std::fprintf(stderr, "ordersearch: %s\n", err.c_str());
+        return 2;
+    }
+    if (args.has("help") || argc == 1 || !args.has("scoreFile")) {
+        args.usage(argv[0],
+                   "Learn a Bayesian network of up to 63 variables by tabu search over variable orders on an MI355X: the best "
+                   "network found, not a proven optimum.  Example usage: ordersearch big.pss -n big_net");
+        return args.has("help") || argc == 1 ? 0 : 2;
+    }
+    ulgio::PssData p;
+    if (!ulgio::read_pss(args.get("scoreFile"), p, err)) {
+        std::fprintf(stderr, "ordersearch: %s\n", err.c_str());
+        return 1;
+    }
+    const int n = (int)p.names.size();
+    if (n < 1) {
+        std::fprintf(stderr, "ordersearch: no variables in '%s'\n", args.get("scoreFile").c_str());
+        return 1;
+    }
+    auto number = [&](const char *name, long long def) { return args.get(name).empty() ? def : std::atoll(args.get(name).c_str()); };
+    const int64_t C = number("searches", 256), steps = number("steps", 20ll * n * n), tenure = number("tenure", n / 2),
+                  patience = number("patience", 4ll * n);
+    uint64_t seed = std::strtoull(args.get("seed").c_str(), nullptr, 10);
+    if (args.has("random")) seed = (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
+    if (C < 1 || steps < 0) {
+        std::fprintf(stderr, "ordersearch: --searches must be >= 1 and --steps >= 0\n");
+        return 2;
+    }
+    std::vector<float> scores(p.costs.size());
+    for (size_t i = 0; i < scores.size(); ++i) scores[i] = -p.costs[i];
+    const int dev = std::atoi(args.get("device").c_str());
+    ulg_ctx *ctx = nullptr;
+    if (ulg_create(&dev, 1, &ctx) != ULG_OK) {
+        std::fprintf(stderr, "ordersearch: no usable HIP device %d\n", dev);
+        return 1;
+    }
+    const double t0 = ulgcli::now_s();
+    std::vector<double> best((size_t)C);
+    std::vector<uint8_t> order((size_t)C * n);
+    std::vector<uint64_t> parents((size_t)C * n);
+    std::vector<int64_t> moves((size_t)C), kicks((size_t)C);
+    if (ulg_order_search_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, C, seed, tenure, patience, nullptr) != ULG_OK ||
+        ulg_order_search_run(ctx, steps, best.data(), order.data(), parents.data(), moves.data(), kicks.data(), nullptr, nullptr) !=
+            ULG_OK) {
+        std::fprintf(stderr, "ordersearch: %s\n", ulg_last_error(ctx));
+        ulg_destroy(ctx);
+        return 1;
+    }
+    const double t1 = ulgcli::now_s();
+    ulg_destroy(ctx);
+    int64_t at = 0, same = 0, all_moves = 0, all_kicks = 0;
+    for (int64_t c = 0; c < C; ++c) {
+        if (best[c] > best[at]) at = c;  // the least search among equals
+        all_moves += moves[c], all_kicks += kicks[c];
+    }
+    for (int64_t c = 0; c < C; ++c) same += best[c] == best[at];
+    std::printf("best score = %.6f, search %lld, %lld of %lld searches share it, %lld moves, %lld kicks\n", best[at], (long long)at,
+                (long long)same, (long long)C, (long long)all_moves, (long long)all_kicks);
+    std::fprintf(stderr,
+                 "ulg_metrics {\"tool\": \"ordersearch\", \"n\": %d, \"searches\": %lld, \"steps\": %lld, \"seed\": %llu, "
+                 "\"best_score\": %.6f, \"search_s\": %.6f}\n",
+                 n, (long long)C, (long long)steps, (unsigned long long)seed, best[at], t1 - t0);
+    const std::string net = args.get("netFile");
+    if (!net.empty()) {
+        const std::vector<uint64_t> vpar(parents.begin() + at * n, parents.begin() + (at + 1) * n);
+        std::string txt = "NumVars " + std::to_string(n) + "\n";  // astar's layout
+        for (int q = 0; q < n; ++q) {
+            const int v = order[at * n + q];
+            txt += "Var " + std::to_string(v + 1) + ", parents";
+            for (int i = 0; i < n; ++i)
+                if ((vpar[v] >> i) & 1ull) txt += ", " + std::to_string(i + 1);
+            txt += "\n";
+        }
+        if (!ulgio::write_text(net, txt) || !ulgio::write_net_csv(net + ".csv", vpar, n)) {
+            std::fprintf(stderr, "ordersearch: cannot write '%s'\n", net.c_str());
+            return 1;
+        }
+    }
+    return 0;
+}

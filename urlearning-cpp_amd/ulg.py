@@ -118,6 +118,12 @@ def lib():
             L.ulg_partition_mcmc_run.argtypes = [P, I64, I64] + [P] * 8 + [C.POINTER(I64)]
             L.ulg_partition_mcmc_state.argtypes = [P, P, P, C.POINTER(I64)]
             L.ulg_partition_score.argtypes = [P, I64, P, P]
+        if hasattr(L, "ulg_order_search_begin"):  # ... or the order search
+            L.ulg_order_search_begin.argtypes = [P, I, P, P, P, I, I64, C.c_uint64, I64, I64, P]
+            L.ulg_order_search_begin_from_scores.argtypes = [P, I64, C.c_uint64, I64, I64, P]
+            L.ulg_order_search_run.argtypes = [P, I64] + [P] * 7
+            L.ulg_order_search_state.argtypes = [P, P, P, P, C.POINTER(I64)]
+            L.ulg_order_best.argtypes = [P, I64, P, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -946,6 +952,94 @@ class Context:
         terms = np.zeros(p.shape, dtype=np.float64)
         self._check(lib().ulg_partition_score(self._h, p.shape[0], _ptr(p), _ptr(terms)), "ulg_partition_score")
         return terms
+
+    # ---- order search --------------------------------------------------------
+    def order_search_begin(self, offsets, sets, scores, searches, seed=0, tenure=0, patience=1, init_order=None, device_ptrs=False):
+        """ulg_order_search_begin on per-variable lists (as Context.posterior takes them): `searches` tabu
+        searches over linear orders, each from its row of init_order uint8 (searches, n) or, with None, from
+        the order MCMC's shuffle; step 0.  tenure: the steps a swapped pair stays tabu; patience: the steps
+        without a new best before a kick."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        n, searches = len(o) - 1, int(searches)
+        if device_ptrs:
+            sp, cp, keep = C.c_void_p(int(sets)), C.c_void_p(int(scores)), None
+        else:
+            s = np.ascontiguousarray(sets, dtype=np.uint64)
+            c = np.ascontiguousarray(scores, dtype=np.float32)
+            if s.size == 0:
+                s, c = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.float32)
+            sp, cp, keep = _ptr(s), _ptr(c), (s, c)
+        init, ip = self._mcmc_init_arg("order_search_begin", init_order, searches, n)
+        self._osearch = self._pmcmc = self._mcmc = None  # a begin of one family ends the others; a refused one leaves none
+        self._check(lib().ulg_order_search_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, searches, int(seed),
+                                                 int(tenure), int(patience), ip), "ulg_order_search_begin")
+        self._osearch = (n, searches)
+        del keep, init
+
+    def order_search_begin_from_scores(self, searches, seed=0, tenure=0, patience=1, init_order=None):
+        """ulg_order_search_begin_from_scores: the same on the lists of the last scoring call."""
+        n, searches = self.n or 1, int(searches)
+        init, ip = self._mcmc_init_arg("order_search_begin_from_scores", init_order, searches, n)
+        self._osearch = self._pmcmc = self._mcmc = None
+        self._check(lib().ulg_order_search_begin_from_scores(self._h, searches, int(seed), int(tenure), int(patience), ip),
+                    "ulg_order_search_begin_from_scores")
+        self._osearch = (n, searches)
+        del init
+
+    def _osearch_shape(self, who):
+        """(n, searches) of the searches this object began and the library still holds."""
+        self._check(lib().ulg_order_search_state(self._h, None, None, None, None), who)
+        if getattr(self, "_osearch", None) is None:
+            raise ULGError(f"{who}: status 3: the last order_search_begin through this object was refused")
+        return self._osearch
+
+    def order_search_state(self):
+        """ulg_order_search_state -> (order uint8 (searches, n), terms float64 (searches, n) by position, score
+        float64 (searches): S, step)."""
+        n, C_ = self._osearch_shape("ulg_order_search_state")
+        order = np.zeros((C_, n), dtype=np.uint8)
+        terms = np.zeros((C_, n), dtype=np.float64)
+        score = np.zeros(C_, dtype=np.float64)
+        step = C.c_int64()
+        self._check(lib().ulg_order_search_state(self._h, _ptr(order), _ptr(terms), _ptr(score), C.byref(step)), "ulg_order_search_state")
+        return order, terms, score, step.value
+
+    def order_search_run(self, steps, trace=False):
+        """ulg_order_search_run: every search `steps` steps on -> dict: "best_score" float64 (searches),
+        "best_order" uint8 (searches, n), "best_parents" uint64 (searches, n): [c, v] = the parent mask of v,
+        "moves", "kicks" int64 (searches) since begin, "step"; with trace also "trace_gain" float64 and
+        "trace_pos" uint8 (steps, searches): -inf and 255 where nothing moved."""
+        n, C_ = self._osearch_shape("ulg_order_search_run")
+        steps = int(steps)
+        out = {"best_score": np.zeros(C_, dtype=np.float64), "best_order": np.zeros((C_, n), dtype=np.uint8),
+               "best_parents": np.zeros((C_, n), dtype=np.uint64), "moves": np.zeros(C_, dtype=np.int64),
+               "kicks": np.zeros(C_, dtype=np.int64)}
+        if trace:
+            try:
+                out["trace_gain"] = np.zeros((max(steps, 0), C_), dtype=np.float64)
+                out["trace_pos"] = np.zeros((max(steps, 0), C_), dtype=np.uint8)
+            except (MemoryError, ValueError) as e:
+                raise ULGError(f"ulg_order_search_run: status 4: {steps} steps of {C_} searches do not fit the host memory ({e})") from None
+        arg = lambda name: _ptr(out[name]) if name in out else None  # noqa: E731
+        self._check(lib().ulg_order_search_run(self._h, steps, arg("best_score"), arg("best_order"), arg("best_parents"), arg("moves"),
+                                               arg("kicks"), arg("trace_gain"), arg("trace_pos")), "ulg_order_search_run")
+        step = C.c_int64()
+        self._check(lib().ulg_order_search_state(self._h, None, None, None, C.byref(step)), "ulg_order_search_state")
+        out["step"] = step.value
+        return out
+
+    def order_best(self, orders):
+        """ulg_order_best: orders uint8 (count, n), each a permutation -> (terms float64 (count, n): [k, p] =
+        the best stored parent set's score of position p, -inf without one; parents uint64 (count, n): [k, v]
+        = that set of variable v), on the lists of the last order_search_begin."""
+        n, _ = self._osearch_shape("ulg_order_best")
+        o = np.ascontiguousarray(orders, dtype=np.uint8)
+        if o.ndim != 2 or o.shape[1] != n:
+            raise ULGError(f"order_best: orders must be (count, {n}), not {o.shape}")
+        terms = np.zeros(o.shape, dtype=np.float64)
+        parents = np.zeros(o.shape, dtype=np.uint64)
+        self._check(lib().ulg_order_best(self._h, o.shape[0], _ptr(o), _ptr(terms), _ptr(parents)), "ulg_order_best")
+        return terms, parents
 
     def order_edges(self, orders, groups=1):
         """ulg_order_edges: orders uint8 (count, n), each a permutation -> (edge uint64 (groups, n, n), zero):

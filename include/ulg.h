@@ -1236,7 +1236,41 @@ int ulg_partition_score(ulg_ctx *ctx, int64_t count, const uint8_t *part, double
  * ULG_ERR_STATE.
  * Errors: as ulg_order_mcmc_begin, with "search" for "chain" (4 n^2 + 18 n + 40
  * B per search); ULG_ERR_ARG also for tenure or patience out of range and a
- * step count that would pass 2^32 - 1. */
+ * step count that would pass 2^32 - 1.
+ *
+ * ulg_order_window: exact window re-optimisation of `count` orders on the lists
+ * of the last search begin (ULG_ERR_STATE without one); the searches' own state
+ * is not touched.  orders: count n bytes on the host, in and out.  width in
+ * 2 .. 12, the effective width w = min(width, n); stride in 0 .. width, 0 =
+ * max(1, width / 2), the stride used min(stride, w); max_sweeps in 1 .. 2^20.
+ *   sweep    the window starts a_0 = 0, a_{k+1} = min(a_k + stride, n - w); the
+ *            sweep ends after the window at n - w.
+ *   window   at start a, with U the variables before position a, x_j =
+ *            order[a + j] and V(M) = {x_j : j in M} for a local mask M:
+ *              beta_j(M) = b_{x_j}(U + V(M)), j not in M;
+ *              F(0) = +0.0, F(M) = the maximum over j in M ascending of
+ *              F(M - j) + beta_j(M - j), one FP64 add each, compared as numbers;
+ *              c(M) = the least j that attains it (the least j of M when every
+ *              candidate is -inf);
+ *              present = ((0.0 + term[a]) + term[a + 1]) + .. over the window.
+ *            The window is accepted iff F(full) > present: from M = full,
+ *            position a + |M| - 1 takes x_{c(M)} and M loses c(M); the window's
+ *            terms are the beta along that path, every other term stands.  A
+ *            tie leaves the order as it is.  A -inf term of the input may so
+ *            be repaired.
+ *   stop     after the first sweep that accepts no window, or max_sweeps sweeps.
+ * accepted[k], sweeps[k]: the windows accepted and the sweeps run for order k;
+ * terms, parents: what ulg_order_best gives for the final orders, the same
+ * bits; score[k] = the ascending FP64 sum of order k's n terms from +0.0.
+ * Every output but orders may be NULL.  For w >= n a sweep is the exact optimum
+ * of the stored families; n = 1 moves nothing.  Order k's result is a fixed
+ * function of (lists, its input order, width, stride, max_sweeps): not of
+ * count, the grid or the waves (option "window_waves").
+ * Errors: ULG_ERR_ARG for width, stride or max_sweeps out of range, count < 0
+ * and a row that is not a permutation (the least such row is named);
+ * ULG_ERR_UNSUPPORTED when the width's tables (13 2^w + 4 w 2^(w-1) bytes of
+ * LDS, 137 KB at w = 12) exceed what the device gives a workgroup, before any
+ * launch, and when 17 n + 24 bytes per order do not fit the device. */
 int ulg_order_search_begin(ulg_ctx *ctx, int n, const int64_t *offsets, const uint64_t *sets,
                            const float *scores, int device_ptrs, int64_t searches, uint64_t seed,
                            int64_t tenure, int64_t patience, const uint8_t *init_order);
@@ -1250,6 +1284,9 @@ int ulg_order_search_state(ulg_ctx *ctx, uint8_t *order, double *terms, double *
                            int64_t *step);
 int ulg_order_best(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms,
                    uint64_t *parents);
+int ulg_order_window(ulg_ctx *ctx, int64_t count, uint8_t *orders, int width, int stride,
+                     int64_t max_sweeps, double *terms, double *score, uint64_t *parents,
+                     int64_t *accepted, int64_t *sweeps);
 
 /* ---- tuning knobs -------------------------------------------------------
  * "score_variant" (1, 49, 65, 113, 241; default 241): bit 0 = fully
@@ -1345,6 +1382,9 @@ int ulg_order_best(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *t
  * (order, position) pair per wave at a time) of ulg_order_edges' launches;
  * 0 = one per four pairs, at most 65536.  The tables are the same integers
  * either way.
+ * "window_waves" (1, 2, 4, 8 or 16; default 8, untuned): the waves of the
+ * workgroup that re-optimises one order in ulg_order_window.  No output bit
+ * depends on it.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU

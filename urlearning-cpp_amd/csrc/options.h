@@ -57,6 +57,8 @@ struct Options {
     int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most (ulg_order_mc3_run's too)
     int64_t mc3_waves = 16;          // ulg_order_mc3_run: waves of the workgroup that runs one ladder
     int64_t edges_grid = 0;          // ulg_order_edges: workgroups of its launches (0: the default rule)
+    // ---- order search ----
+    int64_t window_waves = 8;        // ulg_order_window: waves of the workgroup that re-optimises one order (untuned)
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -106,6 +108,7 @@ constexpr OptionRow kOptionRows[] = {
     {"mcmc_launch_steps", &Options::mcmc_launch_steps, 1, kOptMax, 0, {}, ">= 1"},
     {"mc3_waves", &Options::mc3_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
     {"edges_grid", &Options::edges_grid, 0, 65536, 0, {}, "0..65536"},
+    {"window_waves", &Options::window_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -52,38 +52,9 @@
 #include <cstdio>
 #include <vector>
 
-#include "order_mcmc_state.h"
-#include "order_search_dev.h"
+#include "order_search_state.h"
 
 namespace ulg {
-
-// What a context keeps of the search beside the order MCMC's state, which
-// holds the lists: per search the order, terms and entries, the best order
-// and its entries, the pair stamps, S, S_best and the counts; the global step;
-// the buffers a run's traces and ulg_order_best's orders pass through.
-struct OrderSearchState {
-    int n = 0;
-    int64_t searches = 0;
-    uint64_t seed = 0;
-    int64_t tenure = 0, patience = 1;
-    int64_t step = 0;
-    bool ready = false;
-    DevBuf<uint8_t> d_order, d_best_order;  // [searches][n]
-    DevBuf<double> d_terms;                 // [searches][n] by position
-    DevBuf<uint32_t> d_ent, d_best_ent;     // [searches][n] by position: the index in the variable's list
-    DevBuf<uint32_t> d_stamp;               // [searches][n][n]
-    DevBuf<double> d_score, d_best_score;   // [searches]
-    DevBuf<long long> d_idle, d_moves, d_kicks;  // [searches]
-    DevBuf<unsigned int> d_err;             // [1]: the least search with a -inf term
-    DevBuf<double> r_gain, r_terms;
-    DevBuf<uint8_t> r_pos, r_order;
-    DevBuf<uint64_t> r_parents;
-    size_t run_bytes() const { return (r_gain.cap + r_terms.cap + r_parents.cap) * 8 + r_pos.cap + r_order.cap; }
-    size_t held_bytes() const {
-        return d_order.cap + d_best_order.cap + d_terms.cap * 8 + (d_ent.cap + d_best_ent.cap + d_stamp.cap) * 4 +
-               (d_score.cap + d_best_score.cap + d_idle.cap + d_moves.cap + d_kicks.cap) * 8 + run_bytes();
-    }
-};
 
 void order_search_delete(ulg_ctx *c) {
     delete c->osearch;
@@ -100,7 +71,7 @@ using namespace ulg;
 
 namespace {
 
-constexpr int kWave = 64;
+constexpr int kWave = kSearchWave;
 constexpr int kB = 256;  // the small kernels' workgroup
 
 constexpr uint64_t kGridX = 1ull << 20;
@@ -113,24 +84,6 @@ __device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
 __global__ void __launch_bounds__(kB) osearch_shuffle_kernel(uint8_t *order, int64_t searches, int n, uint64_t seed) {
     const int64_t c = (int64_t)flat_block() * kB + threadIdx.x;
     if (c < searches) mcmc_shuffle(seed, (uint32_t)c, n, order + c * n);
-}
-
-// ---- the scan: one wave, every lane returns the same key (0: no compatible entry)
-__device__ __forceinline__ uint64_t wave_best(const uint64_t *sets, const float *scores, int64_t b, int64_t e, uint64_t U, int lane) {
-    const uint64_t outside = ~U;
-    uint64_t key = 0;
-    uint32_t low = 0xFFFFFFFFu - (uint32_t)lane;  // 2^32 - 1 - (i - b): a list holds at most 2^32 - 1 entries
-#pragma unroll 2
-    for (int64_t i = b + lane; i < e; i += kWave, low -= kWave) {
-        const uint64_t S = sets[i];
-        const uint64_t k = ((uint64_t)os_float_image(__float_as_uint(scores[i])) << 32) | low;
-        if (!(S & outside) && k > key) key = k;
-    }
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        const uint64_t o = __shfl_xor((unsigned long long)key, d, kWave);
-        key = o > key ? o : key;
-    }
-    return key;
 }
 
 // terms[k n + p], ent[k n + p] and parents[k n + v] of `count` orders: a wave
@@ -372,16 +325,7 @@ __global__ void __launch_bounds__(kWave *W) osearch_run_kernel(const SearchArgs 
 }
 
 // ---- host
-bool is_permutation(const uint8_t *row, int n) {
-    uint64_t seen = 0;
-    for (int p = 0; p < n; ++p) {
-        if (row[p] >= n || ((seen >> row[p]) & 1ull)) return false;
-        seen |= 1ull << row[p];
-    }
-    return true;
-}
-
-OrderSearchState *live(ulg_ctx *c) { return c->osearch && c->osearch->ready && c->mcmc ? c->osearch : nullptr; }
+OrderSearchState *live(ulg_ctx *c) { return order_search_live(c); }
 
 int launch_best(ulg_ctx *c, const OrderMcmcState &l, const uint8_t *d_orders, int64_t count, double *d_terms, uint32_t *d_ent,
                 uint64_t *d_parents) {

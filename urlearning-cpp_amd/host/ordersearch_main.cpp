@@ -5,12 +5,19 @@
 //
 //   ordersearch <in.pss> [-n netFile] [--searches C] [--steps T] [--tenure K]
 //               [--patience P] [--seed S] [-r]
+//               [--window W [--window-stride s] [--window-sweeps K] [--rounds R]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs.  netFile and
 // netFile.csv are astar's: "Var v, parents .." lines in the best order, and
 // the 0/1 matrix with row v, column u = 1 for u -> v.  One line is printed.
 // The defaults -- 256 searches, 20 n^2 steps, tenure n / 2, patience 4 n -- are
 // untuned starting points.
+//
+// --window W re-optimises the C best orders by exact windows of W positions
+// (ulg_order_window) after the run and reports those; with --rounds R the
+// searches begin again from the re-optimised orders (seed + round), run --steps
+// more and are re-optimised again, R times in all.  A second line is printed.
+// Without --window the tool's output is what it was before the option existed.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +38,10 @@ int main(int argc, char **argv) {
             {"", "patience", true, "", "Steps without a new best before a search is kicked off its best order (default 4 n, untuned)."},
             {"", "seed", true, "0", "The seed of the initial orders and the kicks."},
             {"r", "random", false, "", "Take the seed from the clock instead."},
+            {"", "window", true, "", "Re-optimise the best orders by exact windows of this many positions, 2..12 (default: none)."},
+            {"", "window-stride", true, "", "Positions between two window starts, 1..window (default window / 2, untuned)."},
+            {"", "window-sweeps", true, "", "Sweeps of a re-optimisation at most (default 64, untuned)."},
+            {"", "rounds", true, "", "Rounds of search and re-optimisation (default 1, untuned); needs --window."},
             {"d", "device", true, "0", "The GPU to use."},
             {"h", "help", false, "", "Show this help message."},
         },
@@ -65,6 +76,13 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "ordersearch: --searches must be >= 1 and --steps >= 0\n");
         return 2;
     }
+    const bool windowed = args.has("window");
+    const int width = (int)number("window", 0), wstride = (int)number("window-stride", 0);
+    const int64_t wsweeps = number("window-sweeps", 64), rounds = number("rounds", 1);
+    if (rounds < 1 || (!windowed && (args.has("window-stride") || args.has("window-sweeps") || args.has("rounds")))) {
+        std::fprintf(stderr, "ordersearch: --rounds must be >= 1; it, --window-stride and --window-sweeps need --window\n");
+        return 2;
+    }
     std::vector<float> scores(p.costs.size());
     for (size_t i = 0; i < scores.size(); ++i) scores[i] = -p.costs[i];
     const int dev = std::atoi(args.get("device").c_str());
@@ -78,12 +96,39 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> order((size_t)C * n);
     std::vector<uint64_t> parents((size_t)C * n);
     std::vector<int64_t> moves((size_t)C), kicks((size_t)C);
-    if (ulg_order_search_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, C, seed, tenure, patience, nullptr) != ULG_OK ||
-        ulg_order_search_run(ctx, steps, best.data(), order.data(), parents.data(), moves.data(), kicks.data(), nullptr, nullptr) !=
-            ULG_OK) {
+    auto fail = [&]() {
         std::fprintf(stderr, "ordersearch: %s\n", ulg_last_error(ctx));
         ulg_destroy(ctx);
         return 1;
+    };
+    if (ulg_order_search_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, C, seed, tenure, patience, nullptr) != ULG_OK ||
+        ulg_order_search_run(ctx, steps, best.data(), order.data(), parents.data(), moves.data(), kicks.data(), nullptr, nullptr) !=
+            ULG_OK)
+        return fail();
+    // --window: the best orders re-optimised, and with --rounds searched on from there
+    double window_s = 0, before = 0;
+    int64_t improved_windows = 0, improved_searches = 0;
+    if (windowed) {
+        std::vector<int64_t> accepted((size_t)C), m((size_t)C), k((size_t)C);
+        std::vector<char> improved((size_t)C, 0);
+        for (int64_t r = 0; r < rounds; ++r) {
+            if (r > 0) {
+                if (ulg_order_search_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, C, seed + (uint64_t)r, tenure, patience,
+                                           order.data()) != ULG_OK ||
+                    ulg_order_search_run(ctx, steps, best.data(), order.data(), nullptr, m.data(), k.data(), nullptr, nullptr) != ULG_OK)
+                    return fail();
+                for (int64_t c = 0; c < C; ++c) moves[c] += m[c], kicks[c] += k[c];
+            }
+            before = best[0];
+            for (int64_t c = 1; c < C; ++c) before = best[c] > before ? best[c] : before;
+            const double w0 = ulgcli::now_s();
+            if (ulg_order_window(ctx, C, order.data(), width, wstride, wsweeps, nullptr, best.data(), parents.data(), accepted.data(),
+                                 nullptr) != ULG_OK)
+                return fail();
+            window_s += ulgcli::now_s() - w0;
+            for (int64_t c = 0; c < C; ++c) improved_windows += accepted[c], improved[c] = improved[c] || accepted[c] > 0;
+        }
+        for (int64_t c = 0; c < C; ++c) improved_searches += improved[c];
     }
     const double t1 = ulgcli::now_s();
     ulg_destroy(ctx);
@@ -95,10 +140,15 @@ int main(int argc, char **argv) {
     for (int64_t c = 0; c < C; ++c) same += best[c] == best[at];
     std::printf("best score = %.6f, search %lld, %lld of %lld searches share it, %lld moves, %lld kicks\n", best[at], (long long)at,
                 (long long)same, (long long)C, (long long)all_moves, (long long)all_kicks);
+    if (windowed)
+        std::printf("window %d: %lld windows improved in %lld of %lld searches, best score before = %.6f\n", width,
+                    (long long)improved_windows, (long long)improved_searches, (long long)C, before);
+    char wmetrics[96] = "";
+    if (windowed) std::snprintf(wmetrics, sizeof wmetrics, ", \"window\": %d, \"window_s\": %.6f", width, window_s);
     std::fprintf(stderr,
                  "ulg_metrics {\"tool\": \"ordersearch\", \"n\": %d, \"searches\": %lld, \"steps\": %lld, \"seed\": %llu, "
-                 "\"best_score\": %.6f, \"search_s\": %.6f}\n",
-                 n, (long long)C, (long long)steps, (unsigned long long)seed, best[at], t1 - t0);
+                 "\"best_score\": %.6f, \"search_s\": %.6f%s}\n",
+                 n, (long long)C, (long long)steps, (unsigned long long)seed, best[at], t1 - t0, wmetrics);
     const std::string net = args.get("netFile");
     if (!net.empty()) {
         const std::vector<uint64_t> vpar(parents.begin() + at * n, parents.begin() + (at + 1) * n);

@@ -124,6 +124,8 @@ def lib():
             L.ulg_order_search_run.argtypes = [P, I64] + [P] * 7
             L.ulg_order_search_state.argtypes = [P, P, P, P, C.POINTER(I64)]
             L.ulg_order_best.argtypes = [P, I64, P, P, P]
+        if hasattr(L, "ulg_order_window"):  # ... or its window re-optimisation
+            L.ulg_order_window.argtypes = [P, I64, P, I, I, I64, P, P, P, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
         L.ulg_get_info.argtypes = [P, C.c_char_p, C.POINTER(I64)]
         L.ulg_profile_enable.argtypes = [P, I]
@@ -1040,6 +1042,25 @@ class Context:
         parents = np.zeros(o.shape, dtype=np.uint64)
         self._check(lib().ulg_order_best(self._h, o.shape[0], _ptr(o), _ptr(terms), _ptr(parents)), "ulg_order_best")
         return terms, parents
+
+    def order_window(self, orders, width, stride=0, max_sweeps=64):
+        """ulg_order_window: orders uint8 (count, n), each a permutation, re-optimised by exact windows of
+        `width` positions (2..12, at most n) every `stride` positions (0: max(1, width / 2)) until a sweep
+        accepts nothing or max_sweeps sweeps, on the lists of the last order_search_begin -> dict: "orders"
+        uint8 (count, n), "terms" float64 (count, n) by position, "score" float64 (count), "parents" uint64
+        (count, n) by variable, "accepted" and "sweeps" int64 (count).  The argument is not changed."""
+        n, _ = self._osearch_shape("ulg_order_window")
+        o = np.array(orders, dtype=np.uint8, order="C", copy=True)
+        if o.ndim != 2 or o.shape[1] != n:
+            raise ULGError(f"order_window: orders must be (count, {n}), not {o.shape}")
+        count = o.shape[0]
+        out = {"orders": o, "terms": np.zeros(o.shape, dtype=np.float64), "score": np.zeros(count, dtype=np.float64),
+               "parents": np.zeros(o.shape, dtype=np.uint64), "accepted": np.zeros(count, dtype=np.int64),
+               "sweeps": np.zeros(count, dtype=np.int64)}
+        self._check(lib().ulg_order_window(self._h, count, _ptr(o), int(width), int(stride), int(max_sweeps), _ptr(out["terms"]),
+                                           _ptr(out["score"]), _ptr(out["parents"]), _ptr(out["accepted"]), _ptr(out["sweeps"])),
+                    "ulg_order_window")
+        return out
 
     def order_edges(self, orders, groups=1):
         """ulg_order_edges: orders uint8 (count, n), each a permutation -> (edge uint64 (groups, n, n), zero):

@@ -1238,6 +1238,33 @@ int ulg_partition_score(ulg_ctx *ctx, int64_t count, const uint8_t *part, double
  * B per search); ULG_ERR_ARG also for tenure or patience out of range and a
  * step count that would pass 2^32 - 1.
  *
+ * Candidate-set tables (option "search_tables", 0 or 1, default 0; read by the
+ * two begins).  With 1 a begin builds for every variable v a dense table over
+ * the subsets of its candidate parents C_v, the OR of its stored sets, K_v =
+ * |C_v|: with rank_v(u) the members of C_v below u and idx_v(U) the sum over
+ * u in U & C_v of 1 << rank_v(u),
+ *   T_v[x] = the maximum, over the entries whose set lies inside the
+ *            x-selected members of C_v, of the 64-bit key (the float score's
+ *            order-preserving 32-bit image) * 2^32 + (2^32 - 1 - list index);
+ *            0 without such an entry;
+ * so that T_v[idx_v(U)] decodes to b_v(U) and its least index.  A variable
+ * with an empty list or the empty set alone has one slot; without the empty
+ * set T_v[0] = 0.  ulg_order_search_run, _state and ulg_order_best then read
+ * the tables -- a term is one load -- and give, a maximum of integers being
+ * what it is, the bits they give without: everything above holds unchanged,
+ * "mcmc_waves" alone has nothing to act on (a search is one wave).
+ * ulg_order_window keeps reading the lists, which stay on the device (the
+ * parent masks come from them).  The tables are freed by the events that free
+ * the searches, and by a begin with the option at 0.
+ * Errors: ULG_ERR_UNSUPPORTED, naming the variable and the bytes, when a K_v
+ * exceeds 26 or the sum of 8 2^K_v bytes (+ 16 n + 8 for C and the offsets)
+ * does not fit the free device memory beside the searches, decided before the
+ * tables are allocated; the begin is refused as any other.
+ * ulg_order_search_table (tests, as ulg_bestscore_table for the lattice):
+ * *candidates = C_v, *slots = 2^K_v, and keys[0 .. 2^K_v) = T_v when cap >=
+ * 2^K_v (each may be NULL); ULG_ERR_STATE without searches begun under the
+ * option, ULG_ERR_ARG for v out of range.
+ *
  * ulg_order_window: exact window re-optimisation of `count` orders on the lists
  * of the last search begin (ULG_ERR_STATE without one); the searches' own state
  * is not touched.  orders: count n bytes on the host, in and out.  width in
@@ -1284,6 +1311,8 @@ int ulg_order_search_state(ulg_ctx *ctx, uint8_t *order, double *terms, double *
                            int64_t *step);
 int ulg_order_best(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms,
                    uint64_t *parents);
+int ulg_order_search_table(ulg_ctx *ctx, int v, uint64_t *candidates, int64_t *slots,
+                           uint64_t *keys, int64_t cap);
 int ulg_order_window(ulg_ctx *ctx, int64_t count, uint8_t *orders, int width, int stride,
                      int64_t max_sweeps, double *terms, double *score, uint64_t *parents,
                      int64_t *accepted, int64_t *sweeps);
@@ -1385,6 +1414,9 @@ int ulg_order_window(ulg_ctx *ctx, int64_t count, uint8_t *orders, int width, in
  * "window_waves" (1, 2, 4, 8 or 16; default 8, untuned): the waves of the
  * workgroup that re-optimises one order in ulg_order_window.  No output bit
  * depends on it.
+ * "search_tables" (0 or 1; default 0, untuned): ulg_order_search_begin* build
+ * the dense candidate-set tables and the searches read those instead of
+ * scanning the lists ("Order search").  No output bit depends on it.
  * "time_limit_ms" (default 0 = none): the reference's -r running-time budget
  * (score: per calculateScores call, score_calculator.cpp:33-52,78,91; astar:
  * a watchdog over the search, astar_main.cpp:135-138,266,696-706).  The GPU

@@ -59,6 +59,7 @@ struct Options {
     int64_t edges_grid = 0;          // ulg_order_edges: workgroups of its launches (0: the default rule)
     // ---- order search ----
     int64_t window_waves = 8;        // ulg_order_window: waves of the workgroup that re-optimises one order (untuned)
+    int64_t search_tables = 0;       // ulg_order_search_begin*: build the dense candidate-set tables and search over them (untuned)
 };
 
 // What an option accepts: lo..hi, or (nlist > 0) one of list[0 .. nlist).
@@ -109,6 +110,7 @@ constexpr OptionRow kOptionRows[] = {
     {"mc3_waves", &Options::mc3_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
     {"edges_grid", &Options::edges_grid, 0, 65536, 0, {}, "0..65536"},
     {"window_waves", &Options::window_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
+    {"search_tables", &Options::search_tables, 0, 1, 0, {}, "0 or 1"},
 };
 
 inline const OptionRow *option_row(const char *name) {

@@ -140,25 +140,6 @@ __global__ void __launch_bounds__(kB) osearch_parents_kernel(const uint64_t *set
     parents[c * n + v] = e < (uint64_t)(offsets[v + 1] - b) ? sets[b + e] : 0ull;  // a best order's terms are finite
 }
 
-struct SearchArgs {
-    const uint64_t *sets;
-    const float *scores;
-    const int64_t *offsets;
-    uint8_t *order, *best_order;  // the searches' state ...
-    double *terms;
-    uint32_t *ent, *best_ent, *stamp;
-    double *score, *best_score;
-    long long *idle, *moves, *kicks;
-    int n;
-    int64_t searches;
-    uint64_t seed;
-    int64_t tenure, patience;
-    int64_t t_begin, nsteps;  // the launch makes steps t_begin + 1 .. t_begin + nsteps
-    int64_t t_call;           // the call began after step t_call: the traces are indexed from there
-    double *t_gain;           // each may be null
-    uint8_t *t_pos;
-};
-
 template <int W>
 __global__ void __launch_bounds__(kWave *W) osearch_run_kernel(const SearchArgs a) {
     __shared__ uint8_t ord[kWave], bord[kWave];  // the variable at each position; of the best order
@@ -360,11 +341,28 @@ int begin(ulg_ctx *c, const std::string &who, int64_t C, uint64_t seed, int64_t 
     if (!c->osearch) c->osearch = new OrderSearchState();
     OrderSearchState &s = *c->osearch;
     s.ready = false;
+    s.tables = false;
+    const bool tables = c->opt.search_tables != 0;
+    double table_need = 0.0;  // option "search_tables": the candidate sets and the tables' sizes, before anything is allocated for them
+    if (!tables) order_tables_drop(s);
+    else if (int rc = order_tables_plan(c, who, s, l, &table_need)) return rc;
     const size_t cells = (size_t)C * (size_t)n;
     {
         size_t free_b = 0, total_b = 0;
         ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
-        const double need = (double)C * (18.0 * n + 4.0 * n * n + 40.0) + 12 * 16.0 + 256.0, have = (double)free_b + (double)s.held_bytes();
+        const double need = (double)C * (18.0 * n + 4.0 * n * n + 40.0) + 12 * 16.0 + 256.0 + table_need,
+                     have = (double)free_b + (double)s.held_bytes();
+        if (need > have && tables) {
+            int big = 0;
+            for (int v = 1; v < n; ++v)
+                if (s.toff[v + 1] - s.toff[v] > s.toff[big + 1] - s.toff[big]) big = v;
+            char buf[320];
+            std::snprintf(buf, sizeof buf,
+                          "%s: the tables of option \"search_tables\" need %.0f bytes of device memory (the largest, variable %d's, %.0f) "
+                          "beside %.0f for %lld searches, %.0f are free",
+                          who.c_str(), table_need, big, 8.0 * (double)(s.toff[big + 1] - s.toff[big]), need - table_need, (long long)C, have);
+            return set_err(c, ULG_ERR_UNSUPPORTED, buf);
+        }
         if (need > have) {
             char buf[256];
             std::snprintf(buf, sizeof buf, "%s: %lld searches of n = %d need %.0f bytes of device memory, %.0f are free", who.c_str(),
@@ -389,7 +387,10 @@ int begin(ulg_ctx *c, const std::string &who, int64_t C, uint64_t seed, int64_t 
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
     }
-    if ((rc = launch_best(c, l, s.d_order.p, C, s.d_terms.p, s.d_ent.p, nullptr))) return rc;
+    if (tables && (rc = order_tables_build(c, s, l))) return rc;
+    if ((rc = s.tables ? order_tables_best(c, s, l, s.d_order.p, C, s.d_terms.p, s.d_ent.p, nullptr)
+                       : launch_best(c, l, s.d_order.p, C, s.d_terms.p, s.d_ent.p, nullptr)))
+        return rc;
     prof_begin(c, "osearch_init");
     osearch_init_kernel<<<flat_grid(((uint64_t)C + kB - 1) / kB), kB, 0, c->stream>>>(
         s.d_terms.p, s.d_order.p, s.d_ent.p, C, n, s.d_best_order.p, s.d_best_ent.p, s.d_score.p, s.d_best_score.p, s.d_idle.p,
@@ -491,12 +492,16 @@ int ulg_order_search_run(ulg_ctx *c, int64_t steps, double *best_score, uint8_t 
     for (int64_t done = 0; done < steps; done += a.nsteps) {
         a.t_begin = t0 + done;
         a.nsteps = std::min(cap, steps - done);
-        prof_begin(c, "osearch_run");
-        switch (c->opt.mcmc_waves) {
-            case 1: launch_run<1>(c, a); break;
-            case 2: launch_run<2>(c, a); break;
-            case 8: launch_run<8>(c, a); break;
-            default: launch_run<4>(c, a); break;
+        prof_begin(c, s.tables ? "otab_run" : "osearch_run");
+        if (s.tables) {
+            order_tables_run(c, s, a);
+        } else {
+            switch (c->opt.mcmc_waves) {
+                case 1: launch_run<1>(c, a); break;
+                case 2: launch_run<2>(c, a); break;
+                case 8: launch_run<8>(c, a); break;
+                default: launch_run<4>(c, a); break;
+            }
         }
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
@@ -567,12 +572,33 @@ int ulg_order_best(ulg_ctx *c, int64_t count, const uint8_t *orders, double *ter
         (parents && (rc = ensure(c, s.r_parents, cells))))
         return rc;
     ULG_HIP(c, hipMemcpyAsync(s.r_order.p, orders, cells, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_best(c, *c->mcmc, s.r_order.p, count, terms ? s.r_terms.p : nullptr, nullptr, parents ? s.r_parents.p : nullptr)))
+    double *const d_terms = terms ? s.r_terms.p : nullptr;
+    uint64_t *const d_parents = parents ? s.r_parents.p : nullptr;
+    if ((rc = s.tables ? order_tables_best(c, s, *c->mcmc, s.r_order.p, count, d_terms, nullptr, d_parents)
+                       : launch_best(c, *c->mcmc, s.r_order.p, count, d_terms, nullptr, d_parents)))
         return rc;
     if (terms) ULG_HIP(c, hipMemcpyAsync(terms, s.r_terms.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     if (parents) ULG_HIP(c, hipMemcpyAsync(parents, s.r_parents.p, cells * 8, hipMemcpyDeviceToHost, c->stream));
     ULG_HIP(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    return ULG_OK;
+}
+
+int ulg_order_search_table(ulg_ctx *c, int v, uint64_t *candidates, int64_t *slots, uint64_t *keys, int64_t cap) {
+    if (!c) return ULG_ERR_ARG;
+    const std::string who = "ulg_order_search_table";
+    if (!live(c)) return set_err(c, ULG_ERR_STATE, who + ": no ulg_order_search_begin");
+    OrderSearchState &s = *c->osearch;
+    if (!s.tables) return set_err(c, ULG_ERR_STATE, who + ": the searches were begun without option \"search_tables\"");
+    if (v < 0 || v >= s.n) return set_err(c, ULG_ERR_ARG, who + ": v out of range");
+    const int64_t count = s.toff[v + 1] - s.toff[v];
+    if (candidates) *candidates = s.cand[v];
+    if (slots) *slots = count;
+    if (keys && cap >= count) {
+        ULG_HIP(c, hipSetDevice(c->device));
+        ULG_HIP(c, hipMemcpyAsync(keys, s.d_table.p + s.toff[v], (size_t)count * 8, hipMemcpyDeviceToHost, c->stream));
+        ULG_HIP(c, hipStreamSynchronize(c->stream));
+    }
     return ULG_OK;
 }
 

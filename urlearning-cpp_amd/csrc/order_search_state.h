@@ -5,6 +5,8 @@
 // -- wave_best -- from which every term and chosen set of either file comes.
 #pragma once
 
+#include <string>
+
 #include "order_mcmc_state.h"
 #include "order_search_dev.h"
 
@@ -32,12 +34,19 @@ struct OrderSearchState {
     DevBuf<uint64_t> r_parents;
     DevBuf<double> r_wscore;      // ulg_order_window: [count] S
     DevBuf<long long> r_wcount;   // ... and [2][count]: the accepted windows, the sweeps
+    // the dense candidate-set tables of option "search_tables" (order_tables.hip); `tables` says the searches use them
+    bool tables = false;
+    std::vector<uint64_t> cand;   // [n] C_v
+    std::vector<int64_t> toff;    // [n + 1] the first slot of each variable's table
+    DevBuf<uint64_t> d_cand, d_table;
+    DevBuf<int64_t> d_toff;
+    size_t table_bytes() const { return (d_cand.cap + d_table.cap + d_toff.cap) * 8; }
     size_t run_bytes() const {
         return (r_gain.cap + r_terms.cap + r_parents.cap + r_wscore.cap + r_wcount.cap) * 8 + r_pos.cap + r_order.cap;
     }
     size_t held_bytes() const {
         return d_order.cap + d_best_order.cap + d_terms.cap * 8 + (d_ent.cap + d_best_ent.cap + d_stamp.cap) * 4 +
-               (d_score.cap + d_best_score.cap + d_idle.cap + d_moves.cap + d_kicks.cap) * 8 + run_bytes();
+               (d_score.cap + d_best_score.cap + d_idle.cap + d_moves.cap + d_kicks.cap) * 8 + run_bytes() + table_bytes();
     }
 };
 
@@ -54,6 +63,36 @@ inline bool is_permutation(const uint8_t *row, int n) {
 }
 
 constexpr int kSearchWave = 64;
+
+// What a launch of either run kernel (osearch_run_kernel, otab_run_kernel) reads
+struct SearchArgs {
+    const uint64_t *sets;
+    const float *scores;
+    const int64_t *offsets;
+    uint8_t *order, *best_order;  // the searches' state ...
+    double *terms;
+    uint32_t *ent, *best_ent, *stamp;
+    double *score, *best_score;
+    long long *idle, *moves, *kicks;
+    int n;
+    int64_t searches;
+    uint64_t seed;
+    int64_t tenure, patience;
+    int64_t t_begin, nsteps;  // the launch makes steps t_begin + 1 .. t_begin + nsteps
+    int64_t t_call;           // the call began after step t_call: the traces are indexed from there
+    double *t_gain;           // each may be null
+    uint8_t *t_pos;
+};
+
+// ---- order_tables.hip: the tables of option "search_tables"
+// C_v and the table offsets of the lists into s.cand, s.toff; refuses a K_v above kTableMaxK; *bytes = what the tables take
+int order_tables_plan(ulg_ctx *c, const std::string &who, OrderSearchState &s, const OrderMcmcState &l, double *bytes);
+int order_tables_build(ulg_ctx *c, OrderSearchState &s, const OrderMcmcState &l);  // allocates and fills them; s.tables
+void order_tables_drop(OrderSearchState &s);
+// osearch_best_kernel's outputs from the tables
+int order_tables_best(ulg_ctx *c, const OrderSearchState &s, const OrderMcmcState &l, const uint8_t *d_orders, int64_t count,
+                      double *d_terms, uint32_t *d_ent, uint64_t *d_parents);
+void order_tables_run(ulg_ctx *c, const OrderSearchState &s, const SearchArgs &a);  // one launch of the run kernel over tables
 
 #ifdef __HIPCC__
 // ---- the scan: one wave, every lane returns the same key (0: no compatible entry)

@@ -4,7 +4,7 @@
 // is the tool that names a DAG; it is a heuristic and proves no optimality.
 //
 //   ordersearch <in.pss> [-n netFile] [--searches C] [--steps T] [--tenure K]
-//               [--patience P] [--seed S] [-r]
+//               [--patience P] [--seed S] [-r] [--tables]
 //               [--window W [--window-stride s] [--window-sweeps K] [--rounds R]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs.  netFile and
@@ -18,6 +18,10 @@
 // searches begin again from the re-optimised orders (seed + round), run --steps
 // more and are re-optimised again, R times in all.  A second line is printed.
 // Without --window the tool's output is what it was before the option existed.
+//
+// --tables searches over the dense candidate-set tables (option
+// "search_tables"): the same searches bit for bit, for lists whose every
+// variable has at most 26 candidate parents.  Without the flag nothing changes.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +42,7 @@ int main(int argc, char **argv) {
             {"", "patience", true, "", "Steps without a new best before a search is kicked off its best order (default 4 n, untuned)."},
             {"", "seed", true, "0", "The seed of the initial orders and the kicks."},
             {"r", "random", false, "", "Take the seed from the clock instead."},
+            {"", "tables", false, "", "Search over dense candidate-set tables (at most 26 candidate parents per variable; untuned)."},
             {"", "window", true, "", "Re-optimise the best orders by exact windows of this many positions, 2..12 (default: none)."},
             {"", "window-stride", true, "", "Positions between two window starts, 1..window (default window / 2, untuned)."},
             {"", "window-sweeps", true, "", "Sweeps of a re-optimisation at most (default 64, untuned)."},
@@ -89,6 +94,11 @@ int main(int argc, char **argv) {
     ulg_ctx *ctx = nullptr;
     if (ulg_create(&dev, 1, &ctx) != ULG_OK) {
         std::fprintf(stderr, "ordersearch: no usable HIP device %d\n", dev);
+        return 1;
+    }
+    if (args.has("tables") && ulg_set_option(ctx, "search_tables", 1) != ULG_OK) {
+        std::fprintf(stderr, "ordersearch: %s\n", ulg_last_error(ctx));
+        ulg_destroy(ctx);
         return 1;
     }
     const double t0 = ulgcli::now_s();

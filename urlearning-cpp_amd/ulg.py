@@ -124,6 +124,8 @@ def lib():
             L.ulg_order_search_run.argtypes = [P, I64] + [P] * 7
             L.ulg_order_search_state.argtypes = [P, P, P, P, C.POINTER(I64)]
             L.ulg_order_best.argtypes = [P, I64, P, P, P]
+        if hasattr(L, "ulg_order_search_table"):  # ... or its candidate-set tables
+            L.ulg_order_search_table.argtypes = [P, I, P, P, P, I64]
         if hasattr(L, "ulg_order_window"):  # ... or its window re-optimisation
             L.ulg_order_window.argtypes = [P, I64, P, I, I, I64, P, P, P, P, P]
         L.ulg_set_option.argtypes = [P, C.c_char_p, I64]
@@ -956,11 +958,13 @@ class Context:
         return terms
 
     # ---- order search --------------------------------------------------------
-    def order_search_begin(self, offsets, sets, scores, searches, seed=0, tenure=0, patience=1, init_order=None, device_ptrs=False):
+    def order_search_begin(self, offsets, sets, scores, searches, seed=0, tenure=0, patience=1, init_order=None, device_ptrs=False,
+                           tables=False):
         """ulg_order_search_begin on per-variable lists (as Context.posterior takes them): `searches` tabu
         searches over linear orders, each from its row of init_order uint8 (searches, n) or, with None, from
         the order MCMC's shuffle; step 0.  tenure: the steps a swapped pair stays tabu; patience: the steps
-        without a new best before a kick."""
+        without a new best before a kick.  tables: this begin runs under option "search_tables" = 1 (the dense
+        candidate-set tables; the same bits), and the option is put back afterwards."""
         o = np.ascontiguousarray(offsets, dtype=np.int64)
         n, searches = len(o) - 1, int(searches)
         if device_ptrs:
@@ -973,8 +977,18 @@ class Context:
             sp, cp, keep = _ptr(s), _ptr(c), (s, c)
         init, ip = self._mcmc_init_arg("order_search_begin", init_order, searches, n)
         self._osearch = self._pmcmc = self._mcmc = None  # a begin of one family ends the others; a refused one leaves none
-        self._check(lib().ulg_order_search_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, searches, int(seed),
-                                                 int(tenure), int(patience), ip), "ulg_order_search_begin")
+        has = hasattr(lib(), "ulg_order_search_table")  # an A/B build from before the option knows no tables
+        if tables and not has:
+            raise ULGError("order_search_begin: status 4: this libulg.so has no option \"search_tables\"")
+        was = self.info("search_tables") if has else 0
+        if has:
+            self.set_option("search_tables", 1 if tables else 0)
+        try:
+            self._check(lib().ulg_order_search_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, searches, int(seed),
+                                                     int(tenure), int(patience), ip), "ulg_order_search_begin")
+        finally:
+            if has:
+                self.set_option("search_tables", was)
         self._osearch = (n, searches)
         del keep, init
 
@@ -1029,6 +1043,16 @@ class Context:
         self._check(lib().ulg_order_search_state(self._h, None, None, None, C.byref(step)), "ulg_order_search_state")
         out["step"] = step.value
         return out
+
+    def order_search_table(self, v):
+        """ulg_order_search_table -> (C_v as a Python int, keys uint64 (2^K_v)): the candidate-set table of
+        variable v of searches begun with tables=True."""
+        self._osearch_shape("ulg_order_search_table")
+        cand, slots = C.c_uint64(), C.c_int64()
+        self._check(lib().ulg_order_search_table(self._h, int(v), C.byref(cand), C.byref(slots), None, 0), "ulg_order_search_table")
+        keys = np.zeros(slots.value, dtype=np.uint64)
+        self._check(lib().ulg_order_search_table(self._h, int(v), None, None, _ptr(keys), slots.value), "ulg_order_search_table")
+        return int(cand.value), keys
 
     def order_best(self, orders):
         """ulg_order_best: orders uint8 (count, n), each a permutation -> (terms float64 (count, n): [k, p] =

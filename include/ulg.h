@@ -951,6 +951,52 @@ int ulg_order_mcmc_run(ulg_ctx *ctx, int64_t steps, int64_t thin, uint8_t *order
 int ulg_order_mcmc_state(ulg_ctx *ctx, uint8_t *order, double *terms, int64_t *step);
 int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *terms);
 
+/* Order MCMC over log-sum tables (option "mcmc_tables", 0 or 1, default 0;
+ * read by ulg_order_mcmc_begin and ulg_order_mcmc_begin_from_scores alone).
+ * With 1 a begin builds for every variable v a dense table over the subsets
+ * of its candidate parents C_v (the OR of its stored sets, K_v = |C_v|;
+ * rank_v, idx_v as under "Order search", csrc/order_tables_dev.h) that holds
+ * ln A_v of each subset, and the chains read a term with one load where the
+ * lists' chains scan v's list.  A second contract for the term -- a fixed FP64
+ * expression tree, not the integer sums above -- hence a mode of its own:
+ *   slots   L_v has 2^K_v doubles.  Slot idx_v(P_i) starts as (double) s_i
+ *           (stored sets are distinct, so are their slots), every other slot
+ *           as -inf.
+ *   rounds  for j = 0, 1, .., K_v - 1 in ascending order every slot x with
+ *           bit j becomes post_logaddexp(L[x], L[x ^ (1 << j)])
+ *           (csrc/posterior_dev.h: symmetric, max + log1p(exp(-gap)), the
+ *           maximum itself beyond 38 nats).  A round reads only slots without
+ *           bit j and writes only slots with it: a slot is one expression
+ *           tree whatever lanes, tiles or launches made it.  A slot without a
+ *           compatible entry stays -inf exactly; one with a single entry
+ *           holds that score's bits.
+ *   term    of position p: L_v[idx_v(pre_p)], v the variable there, pre_p the
+ *           variables before it.
+ * Everything else of "Order MCMC" stands word for word: the draws, delta as
+ * the two ascending FP64 sums over lo..hi, the accept rule, log_score as the
+ * ascending sum of the n terms, the refusal of an initial order with a -inf
+ * term, and a record's DAG as the sampler's pick over the LIST with a_p the
+ * position's table term (a list scan per recorded position).  A chain stays a
+ * function of (lists, seed, c, its initial order) alone, the same bits for any
+ * number of chains, any "mcmc_launch_steps" and any split of steps over calls;
+ * "mcmc_waves" has nothing to act on (a chain is one wave).
+ * ulg_order_mcmc_state returns the table terms.  They differ from
+ * ulg_order_score's, which keeps the lists as do ulg_order_edges,
+ * ulg_order_mc3_*, ulg_partition_mcmc_* and the searches (the lists stay on
+ * the device), by the two contracts' rounding: at most K_v (6.25 2^-52 +
+ * ulp/2 + e^-38) plus the list term's cap (tests/order_sumtables_ref.py).
+ * The tables are freed by what frees the chains and by a begin of this family
+ * with the option at 0.
+ * Errors: ULG_ERR_UNSUPPORTED, naming the variable and the bytes, when a K_v
+ * exceeds 26, or when the sum of 8 2^K_v bytes does not fit the free device
+ * memory, decided before the tables are allocated; the begin is refused as any
+ * other and leaves no chains.
+ * ulg_order_mcmc_table (tests): *candidates = C_v, *slots = 2^K_v and
+ * table[0 .. 2^K_v) = L_v; each may be NULL (table NULL: the size is asked
+ * for).  ULG_ERR_STATE without chains begun under the option, ULG_ERR_ARG for
+ * v outside 0..n-1. */
+int ulg_order_mcmc_table(ulg_ctx *ctx, int v, uint64_t *candidates, int64_t *slots, double *table);
+
 /* Metropolis-coupled order MCMC (MC^3, parallel tempering; Geyer 1991): the
  * order MCMC above in ladders of replicas whose neighbours exchange states, so
  * that a chain can leave the mode it started in.  Rung r of a ladder targets
@@ -1403,6 +1449,10 @@ int ulg_order_window(ulg_ctx *ctx, int64_t count, uint8_t *orders, int width, in
  * affects.  "mcmc_launch_steps" (>= 1, default 4096): the steps one launch of
  * it runs at most; the host loops launches over the chains' device state, so
  * no launch is unbounded.  Neither changes a bit of any output.
+ * "mcmc_tables" (0 or 1; default 0, untuned): ulg_order_mcmc_begin* build the
+ * dense log-sum tables and ulg_order_mcmc_run reads a term from them instead
+ * of scanning the list ("Order MCMC over log-sum tables"): the same law under
+ * the tables' own FP64 contract for the term, not the same bits.
  * "mc3_waves" (1, 2, 4, 8 or 16; default 16, the measured best): the waves of the workgroup that
  * runs one ladder of ulg_order_mc3_run; they share the pooled positions of the
  * ladder's moves ("mcmc_launch_steps" bounds its launches too).  No output bit

@@ -35,12 +35,15 @@
 // Plain vector stores only; no floating-point atomics, no communication
 // between workgroups.  The host bounds a launch by option "mcmc_launch_steps"
 // and loops launches over the chains' state in device memory.
+// Under option "mcmc_tables" the two begins build the log-sum tables of
+// order_sumtables.hip and ulg_order_mcmc_run launches its kernel instead.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <vector>
 
 #include "order_mcmc_dev.h"
+#include "order_mcmc_run.h"
 #include "order_mcmc_state.h"
 
 namespace ulg {
@@ -60,9 +63,6 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kB = 256;  // the small kernels' workgroup
-
-// bits of the error word (d_err[0]); d_err[1] = the least chain with a -inf term
-constexpr unsigned kErrSet = 1, kErrScore = 2, kErrDup = 4, kErrPick = 8;
 
 // blocks x threads along x stay below 2^32: larger launches spread over y
 constexpr uint64_t kGridX = 1ull << 20;
@@ -168,69 +168,6 @@ __global__ void __launch_bounds__(kB) mcmc_scan_kernel(const double *terms, int6
     for (int p = 0; p < n; ++p) bad = bad || !(terms[c * n + p] > neg_inf());
     if (bad) atomicMin(least, (unsigned int)c);
 }
-
-// ---- a record's parent set: the sampler's set step (posterior_sample.hip)
-__device__ __forceinline__ uint64_t wave_scan(uint64_t x, int lane) {
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t y = __shfl_up((unsigned long long)x, d, kWave);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-__device__ __forceinline__ int first_above(uint64_t C, uint64_t t) {
-    const unsigned long long hit = __ballot(C > t);
-    return hit ? __ffsll(hit) - 1 : -1;
-}
-// The entry of [b, e) chosen by u_set among those within U, weights
-// floor(exp((double) s - a) 2^52); -1 when every weight is 0 (wave-uniform)
-__device__ __forceinline__ int64_t wave_pick(const uint64_t *sets, const float *scores, int64_t b, int64_t e, uint64_t U, double a,
-                                             uint64_t u_set, int lane) {
-    const uint64_t outside = ~U;
-    auto weigh = [&](int64_t idx) -> uint64_t {
-        if (idx >= e) return 0;
-        if (sets[idx] & outside) return 0;
-        return post_weight_q((double)scores[idx] - a);
-    };
-    if (e - b <= kWave) {
-        const uint64_t C = wave_scan(weigh(b + lane), lane);
-        const uint64_t t = post_pick_threshold(u_set, __shfl((unsigned long long)C, kWave - 1, kWave));
-        const int j = first_above(C, t);
-        return j >= 0 ? b + j : -1;
-    }
-    uint64_t T = 0;
-    for (int64_t idx = b + lane; idx < e; idx += kWave) T += weigh(idx);
-    for (int s = kWave / 2; s > 0; s >>= 1) T += __shfl_xor((unsigned long long)T, s, kWave);
-    const uint64_t t = post_pick_threshold(u_set, T);
-    uint64_t base = 0;
-    for (int64_t c0 = b; c0 < e; c0 += kWave) {
-        const uint64_t C = base + wave_scan(weigh(c0 + lane), lane);
-        const int j = first_above(C, t);
-        if (j >= 0) return c0 + j;
-        base = __shfl((unsigned long long)C, kWave - 1, kWave);
-    }
-    return -1;
-}
-
-struct RunArgs {
-    const uint64_t *sets;
-    const float *scores;
-    const int64_t *offsets;
-    uint8_t *order;                 // [chains][n] the chains' state ...
-    double *terms;                  // [chains][n]
-    unsigned long long *accepted;   // [chains]
-    int n;
-    int64_t chains;
-    uint64_t seed;
-    int64_t t_begin, nsteps;  // the launch makes steps t_begin + 1 .. t_begin + nsteps
-    int64_t t_call, thin;     // the call began after step t_call: records and traces are indexed from there
-    uint8_t *r_order;         // each may be null
-    double *r_score;
-    uint64_t *r_parents;
-    double *r_weight;
-    double *t_delta;
-    uint8_t *t_accept;
-    unsigned int *err;
-};
 
 template <int W>
 __global__ void __launch_bounds__(kWave *W) mcmc_run_kernel(const RunArgs a) {
@@ -616,11 +553,14 @@ int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_
 // The lists are on the device in s (variable order) with s.n and s.total set,
 // s.offsets their offsets on the host: the checks, the initial orders, the terms.
 // lists_only: the checks alone, for the partition MCMC (partition_mcmc.hip), which keeps its own chains.
+// tables: option "mcmc_tables" of ulg_order_mcmc_begin* -- the log-sum tables are built and the chains' terms read from them.
 int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains, uint64_t seed, const uint8_t *init_order,
-          const char *what = "chain", bool lists_only = false) {
+          const char *what = "chain", bool lists_only = false, bool tables = false) {
     const std::vector<int64_t> &offs = s.offsets;
     const int n = s.n;
     s.ready = false;
+    s.tables = false;
+    if (!tables) order_sumtables_drop(s);
     DevBuf<unsigned long long> table;  // the call's own
     const uint64_t slots = table_slots(s.total);
     int rc;
@@ -651,6 +591,7 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
         return set_err(c, ULG_ERR_ARG, msg);
     }
     if (lists_only) return ULG_OK;
+    if (tables && ((rc = order_sumtables_plan(c, who, s)) || (rc = order_sumtables_build(c, s)))) return rc;
     if (init_order) {
         ULG_HIP(c, hipMemcpyAsync(s.d_order.p, init_order, (size_t)(chains * n), hipMemcpyHostToDevice, c->stream));
         ULG_HIP(c, hipStreamSynchronize(c->stream));  // init_order is the caller's again, whatever returns below
@@ -660,7 +601,7 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
     }
-    if ((rc = launch_score(c, s, s.d_order.p, chains, s.d_terms.p))) return rc;
+    if ((rc = s.tables ? order_sumtables_terms(c, s, chains) : launch_score(c, s, s.d_order.p, chains, s.d_terms.p))) return rc;
     prof_begin(c, "mcmc_scan");
     mcmc_scan_kernel<<<flat_grid(((uint64_t)chains + kB - 1) / kB), kB, 0, c->stream>>>(s.d_terms.p, chains, n, s.d_err.p + 1);
     prof_end(c);
@@ -690,7 +631,7 @@ void launch_run(ulg_ctx *c, const RunArgs &a) {
 // ladder's replica holds beyond a chain's bytes)
 int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
                    int device_ptrs, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what, double per_chain,
-                   bool lists_only = false) {
+                   bool lists_only = false, bool tables = false) {
     if (!offsets) return set_err(c, ULG_ERR_ARG, who + ": bad arguments");
     if (int rc = check_begin_args(c, who, n, chains, init_order, what)) return rc;
     for (int v = 0; v < n; ++v)
@@ -716,12 +657,12 @@ int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *off
         ULG_HIP(c, hipMemcpyAsync(s.d_scores.p, scores + offsets[0], (size_t)total * 4, kind, c->stream));
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what, lists_only);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables);
 }
 
 // ... and on the lists of the last scoring call
 int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what,
-                    double per_chain, bool lists_only = false) {
+                    double per_chain, bool lists_only = false, bool tables = false) {
     if (int rc0 = finish_pending(c)) return rc0;
     if (!c->scored) return set_err(c, ULG_ERR_STATE, who + ": no scoring call yet");
     const int n = c->n;
@@ -762,7 +703,7 @@ int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t
         }
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what, lists_only);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables);
 }
 
 // ---- ladders
@@ -832,7 +773,8 @@ int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
     order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
-    return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0);
+    return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0, false,
+                          c->opt.mcmc_tables != 0);
 }
 
 int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
@@ -840,7 +782,7 @@ int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, 
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
     order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
-    return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0);
+    return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0, false, c->opt.mcmc_tables != 0);
 }
 
 int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, double *log_score, uint64_t *parents,
@@ -895,12 +837,16 @@ int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, 
     for (int64_t done = 0; done < steps; done += a.nsteps) {
         a.t_begin = t0 + done;
         a.nsteps = std::min(cap, steps - done);
-        prof_begin(c, "mcmc_run");
-        switch (c->opt.mcmc_waves) {
-            case 1: launch_run<1>(c, a); break;
-            case 2: launch_run<2>(c, a); break;
-            case 8: launch_run<8>(c, a); break;
-            default: launch_run<4>(c, a); break;
+        prof_begin(c, s.tables ? "ostab_run" : "mcmc_run");
+        if (s.tables) {
+            order_sumtables_run(c, s, a);
+        } else {
+            switch (c->opt.mcmc_waves) {
+                case 1: launch_run<1>(c, a); break;
+                case 2: launch_run<2>(c, a); break;
+                case 8: launch_run<8>(c, a); break;
+                default: launch_run<4>(c, a); break;
+            }
         }
         prof_end(c);
         ULG_HIP(c, hipGetLastError());

@@ -70,13 +70,21 @@ struct OrderMcmcState {
     DevBuf<uint8_t> r_order, r_taccept, r_tswapacc;
     DevBuf<double> r_score, r_weight, r_tdelta, r_tswapd;
     DevBuf<uint64_t> r_parents;
+    // the dense log-sum tables of option "mcmc_tables" (order_sumtables.hip); `tables` says the chains read them
+    bool tables = false;
+    std::vector<uint64_t> cand;  // [n] C_v
+    std::vector<int64_t> toff;   // [n + 1] the first slot of each variable's table
+    DevBuf<uint64_t> d_cand;
+    DevBuf<int64_t> d_toff;
+    DevBuf<double> d_sumtable;
+    size_t table_bytes() const { return (d_cand.cap + d_toff.cap + d_sumtable.cap) * 8; }
     size_t run_bytes() const {
         return r_order.cap + r_taccept.cap + r_tswapacc.cap + (r_score.cap + r_weight.cap + r_tdelta.cap + r_tswapd.cap) * 8 +
                r_parents.cap * 8;
     }
     size_t held_bytes() const {
         return d_sets.cap * 8 + d_scores.cap * 4 + d_offsets.cap * 8 + d_order.cap + d_terms.cap * 8 + d_accepted.cap * 8 +
-               d_err.cap * 4 + d_perm.cap + d_swaps.cap * 8 + d_args.cap * sizeof(Mc3Args) + run_bytes();
+               d_err.cap * 4 + d_perm.cap + d_swaps.cap * 8 + d_args.cap * sizeof(Mc3Args) + run_bytes();  // the tables apart: order_sumtables_plan counts them
     }
 };
 

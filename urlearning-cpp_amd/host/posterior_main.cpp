@@ -6,7 +6,7 @@
 //   posterior scores.pss [-o edges.csv] [-s sets.txt] [-d device]
 //             [--sample K [--seed S] [-g dags.txt] [--uniform [--uniform-edges FILE]]
 //              [--paths FILE] [--blankets FILE] [--compelled FILE] [--vstructs FILE]
-//              [--mcmc [--chains C] [--burn B] [--thin T] [--rb-edges FILE]]]
+//              [--mcmc [--chains C] [--burn B] [--thin T] [--rb-edges FILE] [--tables]]]
 //
 // The .pss is read as astar reads it (read_pss); scores = -costs, taken as
 // natural-log weights, so the file should come from a Bayesian score
@@ -93,8 +93,17 @@
 //   partition MCMC: C chains, <steps> steps each, acceptance = %.3f, mean parts = %.3f, R-hat(log score) = %.3f
 // Refused (exit 2) with --uniform and --uniform-edges -- the samples already
 // are uniform-prior -- and with --rb-edges and --temper, which are order-based.
+// --tables (with --mcmc) runs the chains over the dense log-sum tables of
+// option "mcmc_tables" (include/ulg.h, "Order MCMC over log-sum tables"): a term
+// is one load, not a scan of the variable's list, by the tables' own FP64
+// contract, so the samples are another run of the same law, not the same
+// bits.  The order MCMC line gains
+//   , tables (K_max = %d, %lld bytes)
+// the largest candidate set and the tables' size.  A variable with more than
+// 26 candidate parents is refused (exit 1, the library's message).  Refused
+// (exit 2) with --temper and --partition, which have no tables.
 // Exit status: 0, 1 for a file or device error, 2 for a bad command line
-// (--partition without --mcmc or with the flags above; --temper without --mcmc or outside 2..16, --beta-min or --swap-every without
+// (--tables without --mcmc or with --temper or --partition; --partition without --mcmc or with the flags above; --temper without --mcmc or outside 2..16, --beta-min or --swap-every without
 // --temper or with a bad value;
 // --seed, -g, --uniform, --mcmc or a feature file without --sample,
 // --uniform-edges without --uniform, --chains, --burn or --thin without
@@ -158,6 +167,8 @@ int main(int argc, char **argv) {
                                      "read the R-hat that is printed)."},
             {"", "burn", true, "", "Steps every chain makes before its first record (with --mcmc; default 5000, untuned)."},
             {"", "thin", true, "", "A record after every this many steps (with --mcmc; default 100, untuned)."},
+            {"", "tables", false, "", "Run the chains over dense log-sum tables of each variable's candidate parents: a term is one "
+                                      "load (with --mcmc; not with --temper or --partition; at most 26 candidates a variable)."},
             {"", "temper", true, "", "Run every chain as a ladder of this many tempered rungs, 2..16, that exchange states "
                                      "(with --mcmc; --chains then counts ladders and only the cold rung is recorded)."},
             {"", "beta-min", true, "", "The hottest rung's inverse temperature, between 0 and 1; the rungs are geometric "
@@ -223,6 +234,11 @@ int main(int argc, char **argv) {
     if (partition && (uniform || args.has("uniform-edges") || rb || temper)) {
         std::fprintf(stderr, "posterior: --partition does not go with --uniform or --uniform-edges (its samples already follow the "
                              "uniform prior), nor with --rb-edges or --temper (both are order-based)\n");
+        return 2;
+    }
+    const bool tables = args.has("tables");
+    if (tables && (!mcmc || temper || partition)) {
+        std::fprintf(stderr, "posterior: --tables needs --mcmc and does not go with --temper or --partition (neither has tables)\n");
         return 2;
     }
     long long chains = 256, burn = 5000, thin = 100, rungs = 1, swap_every = 10;
@@ -346,6 +362,11 @@ int main(int argc, char **argv) {
             return 1;
         }
         std::vector<int32_t> m_parts(partition ? (size_t)recs * chains : 0);
+        if (tables && ulg_set_option(ctx, "mcmc_tables", 1) != ULG_OK) {
+            std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+            ulg_destroy(ctx);
+            return 1;
+        }
         const bool ran =
             partition ? ulg_partition_mcmc_begin(ctx, n, p.offsets.data(), p.sets.data(), scores.data(), 0, chains, seed, nullptr) == ULG_OK &&
                             ulg_partition_mcmc_run(ctx, burn, thin, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -423,6 +444,24 @@ int main(int argc, char **argv) {
             std::snprintf(line, sizeof line, "order MCMC: %lld chains, %lld steps each, acceptance = %.3f, R-hat(log score) = %s\n", chains,
                           steps, (double)accepted / ((double)chains * (double)steps), rh);
         mcmc_line = line;
+        if (tables) {
+            int k_max = 0;
+            long long slots_all = 0;
+            for (int v = 0; v < n; ++v) {
+                uint64_t cand = 0;
+                int64_t slots = 0;
+                if (ulg_order_mcmc_table(ctx, v, &cand, &slots, nullptr) != ULG_OK) {
+                    std::fprintf(stderr, "posterior: %s\n", ulg_last_error(ctx));
+                    ulg_destroy(ctx);
+                    return 1;
+                }
+                k_max = std::max(k_max, __builtin_popcountll(cand));
+                slots_all += slots;
+            }
+            mcmc_line.pop_back();
+            std::snprintf(line, sizeof line, ", tables (K_max = %d, %lld bytes)\n", k_max, 8 * slots_all);
+            mcmc_line += line;
+        }
         if (temper) {
             // pair (r, r + 1) is considered in the rounds x = 1 .. steps / E with x = r (mod 2)
             const long long rounds = steps / swap_every;

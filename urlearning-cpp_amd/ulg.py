@@ -124,6 +124,8 @@ def lib():
             L.ulg_order_search_run.argtypes = [P, I64] + [P] * 7
             L.ulg_order_search_state.argtypes = [P, P, P, P, C.POINTER(I64)]
             L.ulg_order_best.argtypes = [P, I64, P, P, P]
+        if hasattr(L, "ulg_order_mcmc_table"):  # ... or the order MCMC's log-sum tables
+            L.ulg_order_mcmc_table.argtypes = [P, I, P, P, P]
         if hasattr(L, "ulg_order_search_table"):  # ... or its candidate-set tables
             L.ulg_order_search_table.argtypes = [P, I, P, P, P, I64]
         if hasattr(L, "ulg_order_window"):  # ... or its window re-optimisation
@@ -763,10 +765,25 @@ class Context:
             raise ULGError(f"{who}: init_order must be ({chains}, {n}), not {o.shape}")
         return o, _ptr(o)
 
-    def order_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_order=None, device_ptrs=False):
+    def _with_mcmc_tables(self, who, tables, call):
+        """`call` under option "mcmc_tables" = tables, the option put back afterwards."""
+        has = hasattr(lib(), "ulg_order_mcmc_table")  # an A/B build from before the option knows no tables
+        if tables and not has:
+            raise ULGError(f"{who}: status 4: this libulg.so has no option \"mcmc_tables\"")
+        was = self.info("mcmc_tables") if has else 0
+        if has:
+            self.set_option("mcmc_tables", 1 if tables else 0)
+        try:
+            call()
+        finally:
+            if has:
+                self.set_option("mcmc_tables", was)
+
+    def order_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_order=None, device_ptrs=False, tables=False):
         """ulg_order_mcmc_begin on per-variable lists (as Context.posterior takes them): `chains` chains of
         seed `seed`, each from its row of init_order uint8 (chains, n) or, with None, from the contract's
-        shuffle; step 0."""
+        shuffle; step 0.  tables: this begin runs under option "mcmc_tables" = 1 (the dense log-sum tables:
+        a term is one load, by the tables' own FP64 contract), and the option is put back afterwards."""
         o = np.ascontiguousarray(offsets, dtype=np.int64)
         n, chains = len(o) - 1, int(chains)
         if device_ptrs:
@@ -779,20 +796,31 @@ class Context:
             sp, cp, keep = _ptr(s), _ptr(c), (s, c)
         init, ip = self._mcmc_init_arg("order_mcmc_begin", init_order, chains, n)
         self._mcmc = None  # a refused call leaves no chains
-        self._check(lib().ulg_order_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip),
-                    "ulg_order_mcmc_begin")
+        self._with_mcmc_tables("order_mcmc_begin", tables, lambda: self._check(
+            lib().ulg_order_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip), "ulg_order_mcmc_begin"))
         self._mcmc = (n, chains)
         del keep, init
 
-    def order_mcmc_begin_from_scores(self, chains, seed=0, init_order=None):
+    def order_mcmc_begin_from_scores(self, chains, seed=0, init_order=None, tables=False):
         """ulg_order_mcmc_begin_from_scores: the same on the lists of the last scoring call (every
         variable scored), scores as they are."""
         n, chains = self.n or 1, int(chains)
         init, ip = self._mcmc_init_arg("order_mcmc_begin_from_scores", init_order, chains, n)
         self._mcmc = None
-        self._check(lib().ulg_order_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_order_mcmc_begin_from_scores")
+        self._with_mcmc_tables("order_mcmc_begin_from_scores", tables, lambda: self._check(
+            lib().ulg_order_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_order_mcmc_begin_from_scores"))
         self._mcmc = (n, chains)
         del init
+
+    def order_mcmc_table(self, v):
+        """ulg_order_mcmc_table -> (C_v as a Python int, L_v float64 (2^K_v)): the log-sum table of variable v
+        of chains begun with tables=True."""
+        self._mcmc_shape("ulg_order_mcmc_table")
+        cand, slots = C.c_uint64(), C.c_int64()
+        self._check(lib().ulg_order_mcmc_table(self._h, int(v), C.byref(cand), C.byref(slots), None), "ulg_order_mcmc_table")
+        table = np.zeros(slots.value, dtype=np.float64)
+        self._check(lib().ulg_order_mcmc_table(self._h, int(v), None, None, _ptr(table)), "ulg_order_mcmc_table")
+        return int(cand.value), table
 
     def _mcmc_shape(self, who):
         """(n, chains) of the chains this object began; without them the library's own refusal is raised."""

@@ -997,6 +997,52 @@ int ulg_order_score(ulg_ctx *ctx, int64_t count, const uint8_t *orders, double *
  * v outside 0..n-1. */
 int ulg_order_mcmc_table(ulg_ctx *ctx, int v, uint64_t *candidates, int64_t *slots, double *table);
 
+/* Order MCMC: a record's DAG from the tables (option "mcmc_table_picks", 0 or
+ * 1, default 0; read by ulg_order_mcmc_begin and
+ * ulg_order_mcmc_begin_from_scores alone; it requires "mcmc_tables" = 1, else
+ * the begin is refused with ULG_ERR_ARG).  With 0 nothing changes by a bit.
+ * With 1 the tables, the chains, the orders, log_score and the traces are
+ * those of "Order MCMC over log-sum tables" bit for bit; a record's parent
+ * sets are drawn by a descent through the butterfly's intermediate states,
+ * six index bits per level, where the list pick scans v's list
+ * (csrc/order_picktables_dev.h).  With nch_v = max(1, ceil(K_v / 6)):
+ *   stages  S_{v,c}, c = 1 .. nch_v - 1: 2^K_v doubles, L_v as it stands after
+ *           rounds 0 .. 6c - 1 and before round 6c (copies of the same
+ *           expression trees).  Slot y holds ln of the summed weights of the
+ *           stored sets whose index bits >= 6c equal y's and whose bits < 6c
+ *           lie inside y's; -inf exactly without one.
+ *   map     E_v: 2^K_v int32; slot idx_v(P_i) holds i - offsets[v], every
+ *           other slot -1.  A list of more than 2^31 - 1 entries is refused.
+ *   pick    of position p (variable v, x = idx_v(pre_p), a = L_v[x], finite):
+ *           fixed = 0, a_cur = a; for c = nch_v - 1 down to 0, over lanes
+ *           l = 0 .. 63: lane l is compatible iff l & ~((x >> 6c) & 63) == 0
+ *           (and, for the top chunk, l < 2^(K_v - 6c)); its slot is
+ *           fixed | l << 6c | (x & ((1 << 6c) - 1)); its value S_{v,c}[slot]
+ *           for c >= 1, and for c = 0 (double) scores[offsets[v] + E_v[slot]],
+ *           -inf where E is -1; its weight post_weight_q(value - a_cur), 0 if
+ *           incompatible.  C = the inclusive sums in lane order, T the last;
+ *           the draw is that of domain d = 1 + p + 64 c of (seed, t, chain),
+ *           U = w0 | w1 << 32, j = the first lane with
+ *           C > post_pick_threshold(U, T); then fixed |= j << 6c and a_cur =
+ *           lane j's value.  T = 0 ends the pick as the list pick's does
+ *           (ULG_ERR_STATE from the run).  After c = 0 the entry is
+ *           offsets[v] + E_v[fixed]; parents, log_weight and the error word
+ *           are "Order MCMC"'s.
+ * A record is a function of (lists, seed, chain, initial order): the same bits
+ * for any number of chains, any "mcmc_launch_steps" and any split of steps
+ * over calls -- not the list pick's bits.  The law is the product over the
+ * levels of floor(. 2^52) conditionals of values within the tables' slot cap;
+ * each level's conditionals sum mathematically to the stage above, so
+ * p(P) = w(P) / A_v(U) up to that rounding (tests/order_picktables_ref.py).
+ * Memory: (8 nch_v + 4) 2^K_v bytes per variable where the tables alone take
+ * 8 2^K_v; ULG_ERR_UNSUPPORTED, naming the largest variable and the bytes,
+ * before anything is allocated.  K_v <= 26 as before.
+ * ulg_order_mcmc_stage_table (tests): *slots = 2^K_v; stage 1 .. nch_v - 1
+ * returns S_{v,stage} in table, stage 0 returns E_v in entries; a NULL output
+ * asks for the size only.  ULG_ERR_STATE without chains begun under the
+ * option, ULG_ERR_ARG for v or stage out of range. */
+int ulg_order_mcmc_stage_table(ulg_ctx *ctx, int v, int stage, int64_t *slots, double *table, int32_t *entries);
+
 /* Metropolis-coupled order MCMC (MC^3, parallel tempering; Geyer 1991): the
  * order MCMC above in ladders of replicas whose neighbours exchange states, so
  * that a chain can leave the mode it started in.  Rung r of a ladder targets
@@ -1453,6 +1499,11 @@ int ulg_order_window(ulg_ctx *ctx, int64_t count, uint8_t *orders, int width, in
  * dense log-sum tables and ulg_order_mcmc_run reads a term from them instead
  * of scanning the list ("Order MCMC over log-sum tables"): the same law under
  * the tables' own FP64 contract for the term, not the same bits.
+ * "mcmc_table_picks" (0 or 1; default 0, untuned; needs "mcmc_tables" = 1):
+ * the begin keeps the butterfly's stage tables and an entry map, and a
+ * record's DAG is drawn by descending them six index bits at a time instead
+ * of scanning the list ("Order MCMC: a record's DAG from the tables"): the
+ * same chains, another pick -- the same law, not the same DAG bits.
  * "mc3_waves" (1, 2, 4, 8 or 16; default 16, the measured best): the waves of the workgroup that
  * runs one ladder of ulg_order_mc3_run; they share the pooled positions of the
  * ladder's moves ("mcmc_launch_steps" bounds its launches too).  No output bit

@@ -56,6 +56,7 @@ struct Options {
     int64_t mcmc_waves = 4;          // ulg_order_mcmc_run: waves of the workgroup that runs one chain
     int64_t mcmc_launch_steps = 4096;  // ... and the steps of one launch at most (ulg_order_mc3_run's too)
     int64_t mcmc_tables = 0;         // ulg_order_mcmc_begin*: build the dense log-sum tables and run the chains over them (untuned)
+    int64_t mcmc_table_picks = 0;    // ... and keep the butterfly's stage tables: a record's DAG by chunked table descent (needs mcmc_tables; untuned)
     int64_t mc3_waves = 16;          // ulg_order_mc3_run: waves of the workgroup that runs one ladder
     int64_t edges_grid = 0;          // ulg_order_edges: workgroups of its launches (0: the default rule)
     // ---- order search ----
@@ -113,6 +114,7 @@ constexpr OptionRow kOptionRows[] = {
     {"window_waves", &Options::window_waves, 0, 0, 5, {1, 2, 4, 8, 16}, "1, 2, 4, 8 or 16"},
     {"search_tables", &Options::search_tables, 0, 1, 0, {}, "0 or 1"},
     {"mcmc_tables", &Options::mcmc_tables, 0, 1, 0, {}, "0 or 1"},
+    {"mcmc_table_picks", &Options::mcmc_table_picks, 0, 1, 0, {}, "0 or 1"},
 };
 
 inline const OptionRow *option_row(const char *name) {

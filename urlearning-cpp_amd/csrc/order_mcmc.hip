@@ -553,14 +553,16 @@ int refuse_size(ulg_ctx *c, const std::string &who, int n, int64_t total, int64_
 // The lists are on the device in s (variable order) with s.n and s.total set,
 // s.offsets their offsets on the host: the checks, the initial orders, the terms.
 // lists_only: the checks alone, for the partition MCMC (partition_mcmc.hip), which keeps its own chains.
-// tables: option "mcmc_tables" of ulg_order_mcmc_begin* -- the log-sum tables are built and the chains' terms read from them.
+// tables: option "mcmc_tables" of ulg_order_mcmc_begin* -- the log-sum tables are built and the chains' terms read from them;
+// picks: option "mcmc_table_picks" with it -- the build keeps the stage tables and the entry map for the records' DAGs.
 int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains, uint64_t seed, const uint8_t *init_order,
-          const char *what = "chain", bool lists_only = false, bool tables = false) {
+          const char *what = "chain", bool lists_only = false, bool tables = false, bool picks = false) {
     const std::vector<int64_t> &offs = s.offsets;
     const int n = s.n;
     s.ready = false;
     s.tables = false;
     if (!tables) order_sumtables_drop(s);
+    if (!picks) order_picktables_drop(s);
     DevBuf<unsigned long long> table;  // the call's own
     const uint64_t slots = table_slots(s.total);
     int rc;
@@ -591,7 +593,11 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
         return set_err(c, ULG_ERR_ARG, msg);
     }
     if (lists_only) return ULG_OK;
-    if (tables && ((rc = order_sumtables_plan(c, who, s)) || (rc = order_sumtables_build(c, s)))) return rc;
+    s.table_picks = tables && picks;  // read by the plan and the build
+    if (tables && ((rc = order_sumtables_plan(c, who, s)) || (rc = order_sumtables_build(c, s)))) {
+        order_picktables_drop(s);  // a refused begin keeps no stage table or map
+        return rc;
+    }
     if (init_order) {
         ULG_HIP(c, hipMemcpyAsync(s.d_order.p, init_order, (size_t)(chains * n), hipMemcpyHostToDevice, c->stream));
         ULG_HIP(c, hipStreamSynchronize(c->stream));  // init_order is the caller's again, whatever returns below
@@ -621,6 +627,13 @@ int begin(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int64_t chains,
     return ULG_OK;
 }
 
+// option "mcmc_table_picks" descends the tables of option "mcmc_tables": refused without them
+int check_table_picks(ulg_ctx *c, const std::string &who) {
+    if (c->opt.mcmc_table_picks && !c->opt.mcmc_tables)
+        return set_err(c, ULG_ERR_ARG, who + ": option \"mcmc_table_picks\" requires option \"mcmc_tables\" = 1");
+    return ULG_OK;
+}
+
 template <int W>
 void launch_run(ulg_ctx *c, const RunArgs &a) {
     mcmc_run_kernel<W><<<dim3((unsigned)a.chains), kWave * W, 0, c->stream>>>(a);
@@ -631,7 +644,7 @@ void launch_run(ulg_ctx *c, const RunArgs &a) {
 // ladder's replica holds beyond a chain's bytes)
 int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *offsets, const uint64_t *sets, const float *scores,
                    int device_ptrs, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what, double per_chain,
-                   bool lists_only = false, bool tables = false) {
+                   bool lists_only = false, bool tables = false, bool picks = false) {
     if (!offsets) return set_err(c, ULG_ERR_ARG, who + ": bad arguments");
     if (int rc = check_begin_args(c, who, n, chains, init_order, what)) return rc;
     for (int v = 0; v < n; ++v)
@@ -657,12 +670,12 @@ int begin_on_lists(ulg_ctx *c, const std::string &who, int n, const int64_t *off
         ULG_HIP(c, hipMemcpyAsync(s.d_scores.p, scores + offsets[0], (size_t)total * 4, kind, c->stream));
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables, picks);
 }
 
 // ... and on the lists of the last scoring call
 int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t seed, const uint8_t *init_order, const char *what,
-                    double per_chain, bool lists_only = false, bool tables = false) {
+                    double per_chain, bool lists_only = false, bool tables = false, bool picks = false) {
     if (int rc0 = finish_pending(c)) return rc0;
     if (!c->scored) return set_err(c, ULG_ERR_STATE, who + ": no scoring call yet");
     const int n = c->n;
@@ -703,7 +716,7 @@ int begin_on_scored(ulg_ctx *c, const std::string &who, int64_t chains, uint64_t
         }
     }
     ULG_HIP(c, hipMemcpyAsync(s.d_offsets.p, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables);
+    return begin(c, who, s, chains, seed, init_order, what, lists_only, tables, picks);
 }
 
 // ---- ladders
@@ -773,8 +786,9 @@ int ulg_order_mcmc_begin(ulg_ctx *c, int n, const int64_t *offsets, const uint64
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
     order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // a begin that is refused, for whatever reason, leaves no chains
+    if (int rc = check_table_picks(c, "ulg_order_mcmc_begin")) return rc;
     return begin_on_lists(c, "ulg_order_mcmc_begin", n, offsets, sets, scores, device_ptrs, chains, seed, init_order, "chain", 0.0, false,
-                          c->opt.mcmc_tables != 0);
+                          c->opt.mcmc_tables != 0, c->opt.mcmc_table_picks != 0);
 }
 
 int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, const uint8_t *init_order) {
@@ -782,7 +796,9 @@ int ulg_order_mcmc_begin_from_scores(ulg_ctx *c, int64_t chains, uint64_t seed, 
     partition_mcmc_end(c);  // a begin of either family ends the partition chains
     order_search_end(c);    // ... and the searches
     if (c->mcmc) c->mcmc->ready = false;  // as ulg_order_mcmc_begin
-    return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0, false, c->opt.mcmc_tables != 0);
+    if (int rc = check_table_picks(c, "ulg_order_mcmc_begin_from_scores")) return rc;
+    return begin_on_scored(c, "ulg_order_mcmc_begin_from_scores", chains, seed, init_order, "chain", 0.0, false, c->opt.mcmc_tables != 0,
+                           c->opt.mcmc_table_picks != 0);
 }
 
 int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, double *log_score, uint64_t *parents,
@@ -837,8 +853,10 @@ int ulg_order_mcmc_run(ulg_ctx *c, int64_t steps, int64_t thin, uint8_t *order, 
     for (int64_t done = 0; done < steps; done += a.nsteps) {
         a.t_begin = t0 + done;
         a.nsteps = std::min(cap, steps - done);
-        prof_begin(c, s.tables ? "ostab_run" : "mcmc_run");
-        if (s.tables) {
+        prof_begin(c, s.table_picks ? "opick_run" : s.tables ? "ostab_run" : "mcmc_run");
+        if (s.table_picks) {
+            order_picktables_run(c, s, a);
+        } else if (s.tables) {
             order_sumtables_run(c, s, a);
         } else {
             switch (c->opt.mcmc_waves) {

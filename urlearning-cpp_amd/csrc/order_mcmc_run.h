@@ -45,6 +45,13 @@ void order_sumtables_drop(OrderMcmcState &s);
 int order_sumtables_terms(ulg_ctx *c, OrderMcmcState &s, int64_t chains);  // d_terms of the chains' d_order from the tables
 void order_sumtables_run(ulg_ctx *c, const OrderMcmcState &s, const RunArgs &a);  // one launch of the run kernel over tables
 
+// ---- order_picktables.hip: a record's DAG from the tables (option "mcmc_table_picks"; s.table_picks is set by the begin)
+// s.soff and the memory of every table, stage table and entry map against what is free (big: the variable of the largest K);
+// allocates d_soff, d_stage, d_entry.  Called by order_sumtables_plan in place of its own count.
+int order_picktables_plan(ulg_ctx *c, const std::string &who, OrderMcmcState &s, int big);
+void order_picktables_drop(OrderMcmcState &s);
+void order_picktables_run(ulg_ctx *c, const OrderMcmcState &s, const RunArgs &a);  // one launch of the run kernel that picks from the tables
+
 #ifdef __HIPCC__
 // ---- a record's parent set: the sampler's set step (posterior_sample.hip)
 __device__ __forceinline__ uint64_t wave_scan(uint64_t x, int lane) {

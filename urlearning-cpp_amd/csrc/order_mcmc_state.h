@@ -77,7 +77,13 @@ struct OrderMcmcState {
     DevBuf<uint64_t> d_cand;
     DevBuf<int64_t> d_toff;
     DevBuf<double> d_sumtable;
-    size_t table_bytes() const { return (d_cand.cap + d_toff.cap + d_sumtable.cap) * 8; }
+    // ... and what option "mcmc_table_picks" adds for a record's DAG (order_picktables.hip); `table_picks` says the records descend them
+    bool table_picks = false;
+    std::vector<int64_t> soff;  // [n + 1] the first slot of each variable's stage tables S_{v,1} .. S_{v,nch-1}
+    DevBuf<int64_t> d_soff;
+    DevBuf<double> d_stage;
+    DevBuf<int32_t> d_entry;    // E_v at toff[v]
+    size_t table_bytes() const { return (d_cand.cap + d_toff.cap + d_sumtable.cap + d_soff.cap + d_stage.cap) * 8 + d_entry.cap * 4; }
     size_t run_bytes() const {
         return r_order.cap + r_taccept.cap + r_tswapacc.cap + (r_score.cap + r_weight.cap + r_tdelta.cap + r_tswapd.cap) * 8 +
                r_parents.cap * 8;

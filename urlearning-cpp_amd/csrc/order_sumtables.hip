@@ -29,7 +29,11 @@
 //              returns stay branches: a wave whose pairs are all -inf or more
 //              than 38 nats apart -- most waves of a sparse table -- skips
 //              exp and log1p.
-//   ostab_terms_kernel    one wave per chain, lane p = position p: the
+//     snapshots  under option "mcmc_table_picks" (order_picktables.hip; every
+//              pointer of it is null otherwise) the rounds 6, 12, 18 and 24
+//              also store the pair's old values into the stage tables, and
+//              the clears and scatters fill the entry map.
+//   ostab_terms_kernel   one wave per chain, lane p = position p: the
 //                         predecessor masks by a prefix OR across the lanes,
 //                         one load per term (the begin's terms)
 //   ostab_run_kernel      one wave per chain, four chains to a workgroup, all
@@ -56,16 +60,14 @@
 #include <cmath>
 #include <cstdio>
 
-#include "order_mcmc_run.h"
-#include "order_sumtables_dev.h"
+#include "order_picktables_dev.h"
+#include "order_sumtables_wave.h"
 
 using namespace ulg;
 
 namespace {
 
-constexpr int kWave = kMcmcWave;
 constexpr int kB = 256;
-constexpr int kRunWaves = 4;  // chains per workgroup of the run kernel
 constexpr int kLdsSlots = 1 << kTableLdsK;
 
 constexpr uint64_t kGridX = 1ull << 20;
@@ -73,18 +75,6 @@ inline dim3 flat_grid(uint64_t blocks) {
     return dim3((unsigned)std::min<uint64_t>(blocks, kGridX), (unsigned)((blocks + kGridX - 1) / kGridX));
 }
 __device__ __forceinline__ uint64_t flat_block() { return (uint64_t)blockIdx.y * gridDim.x + blockIdx.x; }
-__device__ __forceinline__ double neg_inf() { return -__builtin_huge_val(); }
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t x, int d) { return __shfl_xor((unsigned long long)x, d, kWave); }
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t x, int d) { return __shfl_up((unsigned long long)x, d, kWave); }
-
-// lane r's value in every lane, r wave-uniform: two scalar reads, no LDS crossbar
-__device__ __forceinline__ int lane_get(int x, int r) { return __builtin_amdgcn_readlane(x, r); }
-__device__ __forceinline__ uint64_t lane_get64(uint64_t x, int r) {
-    const uint32_t lo = (uint32_t)lane_get((int)(uint32_t)x, r), hi = (uint32_t)lane_get((int)(uint32_t)(x >> 32), r);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ double lane_getd(double x, int r) { return __longlong_as_double((long long)lane_get64((uint64_t)__double_as_longlong(x), r)); }
-
 __global__ void __launch_bounds__(kB) ostab_cand_kernel(const uint64_t *sets, const int64_t *offsets, uint64_t *cand) {
     __shared__ uint64_t part[kB / kWave];
     const int v = blockIdx.x, tid = threadIdx.x;
@@ -98,7 +88,11 @@ __global__ void __launch_bounds__(kB) ostab_cand_kernel(const uint64_t *sets, co
 
 // Rounds 0 .. K-1 on L[0 .. 2^K) in LDS, K <= kTableLdsK, by the kB lanes of the
 // workgroup, all of which call it.  Begins and ends on a barrier.
-__device__ __forceinline__ void lds_butterfly(double *L, int K, int tid) {
+// snap6, snap12 (option "mcmc_table_picks"; null: no stores but L's): where the
+// image goes as it stands before round 6 and before round 12.  The lane of a
+// pair holds both of its slots' old values just then, and the pairs cover the
+// image: two stores beside the round's own, in runs of 2^j slots, no barrier.
+__device__ __forceinline__ void lds_butterfly(double *L, int K, int tid, double *snap6, double *snap12) {
     const int slots = 1 << K, lane = tid & (kWave - 1), low = K < 6 ? K : 6;
     __syncthreads();
     for (int base = 0; base < slots; base += kB) {
@@ -112,92 +106,107 @@ __device__ __forceinline__ void lds_butterfly(double *L, int K, int tid) {
     }
     __syncthreads();
     for (int j = 6; j < K; ++j) {
+        double *snap = j == kPickBits ? snap6 : j == 2 * kPickBits ? snap12 : nullptr;
         for (int q = tid; q < slots / 2; q += kB) {
             const int x = ((q >> j) << (j + 1)) | (1 << j) | (q & ((1 << j) - 1));
-            L[x] = ost_round(L[x], L[x ^ (1 << j)]);
+            const double with = L[x], without = L[x ^ (1 << j)];
+            if (snap) snap[x] = with, snap[x ^ (1 << j)] = without;
+            L[x] = ost_round(with, without);
         }
         __syncthreads();
     }
 }
 
+// What option "mcmc_table_picks" has the build kernels write beside the table
+// (all null without it): the stage tables S_{v,c} at stage[soff[v] + (c - 1) 2^K_v]
+// and the entry map E_v at entry[toff[v]].
+struct Snap {
+    double *stage;
+    const int64_t *soff;
+    int32_t *entry;
+};
+
 __global__ void __launch_bounds__(kB) ostab_small_kernel(const uint64_t *sets, const float *scores, const int64_t *offsets,
-                                                         const uint64_t *cand, const int64_t *toff, double *table) {
+                                                         const uint64_t *cand, const int64_t *toff, double *table, const Snap sn) {
     __shared__ double L[kLdsSlots];
     const int v = blockIdx.x, tid = threadIdx.x;
     const uint64_t C = cand[v];
     const int K = ot_popcount(C);
     if (K > kTableLdsK) return;  // the whole workgroup
     const int slots = 1 << K;
-    for (int x = tid; x < slots; x += kB) L[x] = neg_inf();
+    int32_t *ent = sn.entry ? sn.entry + toff[v] : nullptr;
+    for (int x = tid; x < slots; x += kB) {
+        L[x] = neg_inf();
+        if (ent) ent[x] = -1;  // ordered before the entries' stores by the barrier, as L's are
+    }
     __syncthreads();
-    for (int64_t i = offsets[v] + tid, e = offsets[v + 1]; i < e; i += kB) L[ot_index(C, sets[i])] = (double)scores[i];
-    lds_butterfly(L, K, tid);
+    for (int64_t b = offsets[v], i = b + tid, e = offsets[v + 1]; i < e; i += kB) {
+        const uint32_t x = ot_index(C, sets[i]);
+        L[x] = (double)scores[i];
+        if (ent) ent[x] = (int32_t)(i - b);
+    }
+    double *s6 = sn.stage ? sn.stage + sn.soff[v] : nullptr;
+    lds_butterfly(L, K, tid, s6, s6 ? s6 + slots : nullptr);
     double *out = table + toff[v];
     for (int x = tid; x < slots; x += kB) out[x] = L[x];
 }
 
 // grid (2^Kmax / kB, n): every slot of every variable with K > kTableLdsK
-__global__ void __launch_bounds__(kB) ostab_clear_kernel(const uint64_t *cand, const int64_t *toff, double *table) {
+__global__ void __launch_bounds__(kB) ostab_clear_kernel(const uint64_t *cand, const int64_t *toff, double *table, int32_t *entry) {
     const int v = blockIdx.y;
     const int K = ot_popcount(cand[v]);
     const int64_t x = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (K <= kTableLdsK || x >= ot_slots(K)) return;
     table[toff[v] + x] = neg_inf();
+    if (entry) entry[toff[v] + x] = -1;
 }
 
 // grid (any, n): the entries of every variable with K > kTableLdsK
 __global__ void __launch_bounds__(kB) ostab_scatter_kernel(const uint64_t *sets, const float *scores, const int64_t *offsets,
-                                                           const uint64_t *cand, const int64_t *toff, double *table) {
+                                                           const uint64_t *cand, const int64_t *toff, double *table, int32_t *entry) {
     const int v = blockIdx.y;
     const uint64_t C = cand[v];
     if (ot_popcount(C) <= kTableLdsK) return;
     double *out = table + toff[v];
-    for (int64_t i = offsets[v] + (int64_t)blockIdx.x * kB + threadIdx.x, e = offsets[v + 1]; i < e; i += (int64_t)gridDim.x * kB)
-        out[ot_index(C, sets[i])] = (double)scores[i];
+    int32_t *ent = entry ? entry + toff[v] : nullptr;
+    for (int64_t b = offsets[v], i = b + (int64_t)blockIdx.x * kB + threadIdx.x, e = offsets[v + 1]; i < e; i += (int64_t)gridDim.x * kB) {
+        const uint32_t x = ot_index(C, sets[i]);
+        out[x] = (double)scores[i];
+        if (ent) ent[x] = (int32_t)(i - b);
+    }
 }
 
 // grid (2^(Kmax - kTableLdsK), n): tile blockIdx.x of variable blockIdx.y
-__global__ void __launch_bounds__(kB) ostab_tile_kernel(const uint64_t *cand, const int64_t *toff, double *table) {
+__global__ void __launch_bounds__(kB) ostab_tile_kernel(const uint64_t *cand, const int64_t *toff, double *table, double *stage,
+                                                        const int64_t *soff) {
     __shared__ double L[kLdsSlots];
     const int v = blockIdx.y, tid = threadIdx.x;
     const int K = ot_popcount(cand[v]);
     if (K <= kTableLdsK || (int64_t)blockIdx.x >= ot_slots(K - kTableLdsK)) return;
     double *tile = table + toff[v] + (int64_t)blockIdx.x * kLdsSlots;
     for (int x = tid; x < kLdsSlots; x += kB) L[x] = tile[x];
-    lds_butterfly(L, kTableLdsK, tid);
+    double *s6 = stage ? stage + soff[v] + (int64_t)blockIdx.x * kLdsSlots : nullptr;  // this tile of S_{v,1}, and of S_{v,2} behind it
+    lds_butterfly(L, kTableLdsK, tid, s6, s6 ? s6 + ot_slots(K) : nullptr);
     for (int x = tid; x < kLdsSlots; x += kB) tile[x] = L[x];
 }
 
-// grid (2^(Kmax - 1) / kB, n): round j >= kTableLdsK, a lane per pair of slots
-__global__ void __launch_bounds__(kB) ostab_high_kernel(const uint64_t *cand, const int64_t *toff, double *table, int j) {
+// grid (2^(Kmax - 1) / kB, n): round j >= kTableLdsK, a lane per pair of slots.
+// stage (non-null in rounds 18 and 24 under "mcmc_table_picks"): the pair's old
+// values go to S_{v, j / 6} as the round reads them -- the copy fused into the pass.
+__global__ void __launch_bounds__(kB) ostab_high_kernel(const uint64_t *cand, const int64_t *toff, double *table, int j, double *stage,
+                                                        const int64_t *soff) {
     const int v = blockIdx.y;
     const int K = ot_popcount(cand[v]);
     const int64_t q = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (K <= j || q >= ot_slots(K - 1)) return;
     const int64_t bit = (int64_t)1 << j, x = ((q >> j) << (j + 1)) | bit | (q & (bit - 1));
     double *L = table + toff[v];
-    L[x] = ost_round(L[x], L[x ^ bit]);
-}
-
-// What lane p holds of the variable v at its position: C_v, the table's first
-// slot, the variables at the lanes below and their table index (on: lane < n).
-struct Place {
-    uint64_t C, pre;
-    int64_t base;
-    uint32_t idx;
-};
-__device__ __forceinline__ Place place_of(const uint64_t *cand, const int64_t *toff, int v, bool on, int lane) {
-    const uint64_t own = on ? 1ull << v : 0ull;
-    uint64_t U = own;  // the prefix OR across the lanes, this one included
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t o = shfl_up64(U, d);
-        if (lane >= d) U |= o;
+    const double with = L[x], without = L[x ^ bit];
+    if (stage) {
+        double *snap = stage + soff[v] + (int64_t)(j / kPickBits - 1) * ot_slots(K);
+        snap[x] = with, snap[x ^ bit] = without;
     }
-    Place r;
-    r.C = on ? cand[v] : 0ull, r.base = on ? toff[v] : 0;
-    r.pre = U & ~own;
-    r.idx = ot_index(r.C, r.pre);
-    return r;
+    L[x] = ost_round(with, without);
 }
 
 // terms[c n + p] of every chain's order: a wave per chain
@@ -321,6 +330,7 @@ __global__ void __launch_bounds__(kWave *kRunWaves) ostab_run_kernel(const RunAr
 namespace ulg {
 
 void order_sumtables_drop(OrderMcmcState &s) {
+    order_picktables_drop(s);
     s.tables = false;
     s.d_sumtable.reset();
     s.d_cand.reset();
@@ -354,11 +364,14 @@ int order_sumtables_plan(ulg_ctx *c, const std::string &who, OrderMcmcState &s) 
         s.toff[v + 1] = s.toff[v] + ot_slots(K);
         if (K > ot_popcount(s.cand[big])) big = v;
     }
+    if (s.table_picks) {  // its own count, of every table, stage table and map together, stands for the one below
+        if (int rc2 = order_picktables_plan(c, who, s, big)) return rc2;
+    }
     // decided before the tables are allocated (an earlier begin's table is reused or replaced)
     size_t free_b = 0, total_b = 0;
     ULG_HIP(c, hipMemGetInfo(&free_b, &total_b));
     const double need = 8.0 * (double)s.toff[n] + 16.0, have = (double)free_b + 8.0 * (double)s.d_sumtable.cap;
-    if (need > have) {
+    if (!s.table_picks && need > have) {
         char buf[320];
         std::snprintf(buf, sizeof buf,
                       "%s: the tables of option \"mcmc_tables\" need %.0f bytes of device memory (the largest, variable %d's, %.0f), %.0f "
@@ -379,28 +392,34 @@ int order_sumtables_build(ulg_ctx *c, OrderMcmcState &s) {
     const uint64_t *cand = s.d_cand.p;
     const int64_t *toff = s.d_toff.p;
     double *table = s.d_sumtable.p;
+    Snap sn{nullptr, nullptr, nullptr};
+    if (s.table_picks) {  // allocated by order_picktables_plan
+        sn.stage = s.d_stage.p, sn.soff = s.d_soff.p, sn.entry = s.d_entry.p;
+    }
     if (Kmax > kTableLdsK) {  // the large tables: cleared, the scores stored, the low rounds by tiles
         prof_begin(c, "ostab_clear");
-        ostab_clear_kernel<<<dim3((unsigned)(ot_slots(Kmax) / kB), (unsigned)n), kB, 0, c->stream>>>(cand, toff, table);
+        ostab_clear_kernel<<<dim3((unsigned)(ot_slots(Kmax) / kB), (unsigned)n), kB, 0, c->stream>>>(cand, toff, table, sn.entry);
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
         prof_begin(c, "ostab_scatter");
-        ostab_scatter_kernel<<<dim3(64, (unsigned)n), kB, 0, c->stream>>>(s.d_sets.p, s.d_scores.p, s.d_offsets.p, cand, toff, table);
+        ostab_scatter_kernel<<<dim3(64, (unsigned)n), kB, 0, c->stream>>>(s.d_sets.p, s.d_scores.p, s.d_offsets.p, cand, toff, table, sn.entry);
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
         prof_begin(c, "ostab_tile");
-        ostab_tile_kernel<<<dim3((unsigned)ot_slots(Kmax - kTableLdsK), (unsigned)n), kB, 0, c->stream>>>(cand, toff, table);
+        ostab_tile_kernel<<<dim3((unsigned)ot_slots(Kmax - kTableLdsK), (unsigned)n), kB, 0, c->stream>>>(cand, toff, table, sn.stage,
+                                                                                                                  sn.soff);
         prof_end(c);
         ULG_HIP(c, hipGetLastError());
         for (int j = kTableLdsK; j < Kmax; ++j) {  // ... and the high rounds in ascending order, one pass each
             prof_begin(c, "ostab_high");
-            ostab_high_kernel<<<dim3((unsigned)(ot_slots(Kmax - 1) / kB), (unsigned)n), kB, 0, c->stream>>>(cand, toff, table, j);
+            ostab_high_kernel<<<dim3((unsigned)(ot_slots(Kmax - 1) / kB), (unsigned)n), kB, 0, c->stream>>>(
+                cand, toff, table, j, j % kPickBits == 0 ? sn.stage : nullptr, sn.soff);
             prof_end(c);
             ULG_HIP(c, hipGetLastError());
         }
     }
     prof_begin(c, "ostab_small");
-    ostab_small_kernel<<<dim3((unsigned)n), kB, 0, c->stream>>>(s.d_sets.p, s.d_scores.p, s.d_offsets.p, cand, toff, table);
+    ostab_small_kernel<<<dim3((unsigned)n), kB, 0, c->stream>>>(s.d_sets.p, s.d_scores.p, s.d_offsets.p, cand, toff, table, sn);
     prof_end(c);
     ULG_HIP(c, hipGetLastError());
     s.tables = true;

@@ -3,7 +3,8 @@
 // existed.  The record below is data of this program: it was read from the 26
 // hand-written blocks the table replaced and is not derived from the table
 // (score_narrow, bge_prune, posterior_keep, linext_batch, dagfeat_grid,
-// mcmc_waves, mcmc_launch_steps, edges_grid, mc3_waves, window_waves, search_tables and mcmc_tables, added since, are
+// mcmc_waves, mcmc_launch_steps, edges_grid, mc3_waves, window_waves, search_tables, mcmc_tables and
+// mcmc_table_picks, added since, are
 // recorded the same way).
 // Built with AddressSanitizer + UBSan by `make sanitize` (tests/test_sanitize.py).
 #include <cstdio>
@@ -79,6 +80,7 @@ const std::vector<Want> kWant = {
     {"window_waves", {1, 2, 4, 8, 16}, 0, 0, 8, "1, 2, 4, 8 or 16"},
     {"search_tables", {0, 1}, 0, 0, 0, "0 or 1"},
     {"mcmc_tables", {0, 1}, 0, 0, 0, "0 or 1"},
+    {"mcmc_table_picks", {0, 1}, 0, 0, 0, "0 or 1"},
 };
 
 bool accepted(const Want &w, int64_t v) {
@@ -114,7 +116,7 @@ void check_accepted(const Want &w, int64_t v) {
 }  // namespace
 
 int main() {
-    CHECK(kWant.size() == 38);
+    CHECK(kWant.size() == 39);
     CHECK(sizeof(kOptionRows) / sizeof(kOptionRows[0]) == kWant.size());
     CHECK(sizeof(Options) == kWant.size() * sizeof(int64_t));  // one member per option, nothing else
     // names: unique on both sides, and the same ones

@@ -126,6 +126,8 @@ def lib():
             L.ulg_order_best.argtypes = [P, I64, P, P, P]
         if hasattr(L, "ulg_order_mcmc_table"):  # ... or the order MCMC's log-sum tables
             L.ulg_order_mcmc_table.argtypes = [P, I, P, P, P]
+        if hasattr(L, "ulg_order_mcmc_stage_table"):  # ... or the descent through them for a record's DAG
+            L.ulg_order_mcmc_stage_table.argtypes = [P, I, I, P, P, P]
         if hasattr(L, "ulg_order_search_table"):  # ... or its candidate-set tables
             L.ulg_order_search_table.argtypes = [P, I, P, P, P, I64]
         if hasattr(L, "ulg_order_window"):  # ... or its window re-optimisation
@@ -765,25 +767,36 @@ class Context:
             raise ULGError(f"{who}: init_order must be ({chains}, {n}), not {o.shape}")
         return o, _ptr(o)
 
-    def _with_mcmc_tables(self, who, tables, call):
-        """`call` under option "mcmc_tables" = tables, the option put back afterwards."""
+    def _with_mcmc_tables(self, who, tables, call, table_picks=False):
+        """`call` under options "mcmc_tables" = tables and "mcmc_table_picks" = table_picks, both put back afterwards."""
         has = hasattr(lib(), "ulg_order_mcmc_table")  # an A/B build from before the option knows no tables
+        has_picks = hasattr(lib(), "ulg_order_mcmc_stage_table")
         if tables and not has:
             raise ULGError(f"{who}: status 4: this libulg.so has no option \"mcmc_tables\"")
+        if table_picks and not has_picks:
+            raise ULGError(f"{who}: status 4: this libulg.so has no option \"mcmc_table_picks\"")
         was = self.info("mcmc_tables") if has else 0
+        was_picks = self.info("mcmc_table_picks") if has_picks else 0
         if has:
             self.set_option("mcmc_tables", 1 if tables else 0)
+        if has_picks:
+            self.set_option("mcmc_table_picks", 1 if table_picks else 0)
         try:
             call()
         finally:
             if has:
                 self.set_option("mcmc_tables", was)
+            if has_picks:
+                self.set_option("mcmc_table_picks", was_picks)
 
-    def order_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_order=None, device_ptrs=False, tables=False):
+    def order_mcmc_begin(self, offsets, sets, scores, chains, seed=0, init_order=None, device_ptrs=False, tables=False,
+                         table_picks=False):
         """ulg_order_mcmc_begin on per-variable lists (as Context.posterior takes them): `chains` chains of
         seed `seed`, each from its row of init_order uint8 (chains, n) or, with None, from the contract's
         shuffle; step 0.  tables: this begin runs under option "mcmc_tables" = 1 (the dense log-sum tables:
-        a term is one load, by the tables' own FP64 contract), and the option is put back afterwards."""
+        a term is one load, by the tables' own FP64 contract), and the option is put back afterwards.
+        table_picks: likewise option "mcmc_table_picks" = 1 (a record's DAG by descending the tables; the
+        library refuses it without tables)."""
         o = np.ascontiguousarray(offsets, dtype=np.int64)
         n, chains = len(o) - 1, int(chains)
         if device_ptrs:
@@ -797,18 +810,19 @@ class Context:
         init, ip = self._mcmc_init_arg("order_mcmc_begin", init_order, chains, n)
         self._mcmc = None  # a refused call leaves no chains
         self._with_mcmc_tables("order_mcmc_begin", tables, lambda: self._check(
-            lib().ulg_order_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip), "ulg_order_mcmc_begin"))
+            lib().ulg_order_mcmc_begin(self._h, n, _ptr(o), sp, cp, 1 if device_ptrs else 0, chains, int(seed), ip), "ulg_order_mcmc_begin"),
+            table_picks)
         self._mcmc = (n, chains)
         del keep, init
 
-    def order_mcmc_begin_from_scores(self, chains, seed=0, init_order=None, tables=False):
+    def order_mcmc_begin_from_scores(self, chains, seed=0, init_order=None, tables=False, table_picks=False):
         """ulg_order_mcmc_begin_from_scores: the same on the lists of the last scoring call (every
         variable scored), scores as they are."""
         n, chains = self.n or 1, int(chains)
         init, ip = self._mcmc_init_arg("order_mcmc_begin_from_scores", init_order, chains, n)
         self._mcmc = None
         self._with_mcmc_tables("order_mcmc_begin_from_scores", tables, lambda: self._check(
-            lib().ulg_order_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_order_mcmc_begin_from_scores"))
+            lib().ulg_order_mcmc_begin_from_scores(self._h, chains, int(seed), ip), "ulg_order_mcmc_begin_from_scores"), table_picks)
         self._mcmc = (n, chains)
         del init
 
@@ -821,6 +835,17 @@ class Context:
         table = np.zeros(slots.value, dtype=np.float64)
         self._check(lib().ulg_order_mcmc_table(self._h, int(v), None, None, _ptr(table)), "ulg_order_mcmc_table")
         return int(cand.value), table
+
+    def order_mcmc_stage_table(self, v, stage):
+        """ulg_order_mcmc_stage_table of chains begun with table_picks=True -> stage 1 .. nch_v - 1: the stage
+        table S_{v,stage} float64 (2^K_v); stage 0: the entry map E_v int32 (2^K_v)."""
+        self._mcmc_shape("ulg_order_mcmc_stage_table")
+        slots = C.c_int64()
+        self._check(lib().ulg_order_mcmc_stage_table(self._h, int(v), int(stage), C.byref(slots), None, None), "ulg_order_mcmc_stage_table")
+        out = np.zeros(slots.value, dtype=np.int32 if stage == 0 else np.float64)
+        self._check(lib().ulg_order_mcmc_stage_table(self._h, int(v), int(stage), None, None if stage == 0 else _ptr(out),
+                                                     _ptr(out) if stage == 0 else None), "ulg_order_mcmc_stage_table")
+        return out
 
     def _mcmc_shape(self, who):
         """(n, chains) of the chains this object began; without them the library's own refusal is raised."""
